@@ -8,12 +8,22 @@ GEMMs, batch 256 per GPU, dropout 0.1, AdamW) on N MI355X GPUs, synthetic data.
 
 A step = zero_grad -> mask draw -> forward -> L1 -> backward -> (RCCL gradient
 all-reduce, overlapped) -> AdamW, i.e. SimMIMViT.train_step.  Rank 0 prints ONE JSON
-line.  `value` is whole-job images/s; `roofline` is the dominant kernel family (the
-bf16 MFMA GEMMs) timed live with HIP events on the launch stream; `cpu_baseline` is the
-CPU oracle timed on this host's cores on a bounded sample (rank 0, N=1 only).  On one GPU the
-default run then times the other BASELINE.json configurations (ViT-S/16 batch 256, ViT-L/16
-batch 128 in bf16 and with the fp8 weight path, ViT-B/16 DINO batch 64; 5 + 10 steps each) and
-appends them as `other_configs` -- after the headline's timed region, never inside it."""
+line.  `value` is whole-job images/s and `ms_per_step` the wall time of one timed step.
+
+A plain run only sets up, warms up, times the --steps steps, writes --dump-outputs and prints
+the line.  Everything else is measured with --full (after the headline's timed region, never
+inside it): `roofline` is the dominant kernel family (the bf16 MFMA GEMMs) timed live with HIP
+events on the launch stream in one extra step; `cpu_baseline` is the CPU oracle timed on this
+host's cores on a bounded sample (rank 0, N=1 only); the fused loss of the last timed step is
+re-checked by torch; on N>1 the exposed communication is timed in extra steps; on one GPU the
+other BASELINE.json configurations (ViT-S/16 batch 256, ViT-L/16 batch 128 in bf16 and with the
+fp8 weight path, ViT-B/16 DINO batch 64; 5 + 10 steps each) are appended as `other_configs`.
+
+--dump-outputs DIR writes what the last timed step returned to its caller, as float32 / float64
+.npy files: loss (the step's L1 loss), pred and targets (the masked-patch predictions and their
+pixel targets), params (the parameters after the AdamW update) and grads (the step's gradients).
+Arrays above DUMP_CAP elements are reduced to a fixed sample (flat indices drawn from a generator
+seeded with DUMP_SEED, sorted), so that two builds can be compared output for output."""
 import argparse
 import json
 import os
@@ -37,6 +47,8 @@ MODELS = {  # standard ViT families
 PEAK_BF16_TFLOPS = 2500.0  # dense bf16 MFMA peak, MI355X_MICROARCH.md
 PEAK_FP8_TFLOPS = 5000.0   # dense fp8 MFMA peak (K = 128 f8f6f4 form), MI355X_MICROARCH.md
 PEAK_HBM_TBS = 8.0         # HBM3E spec (6.29 TB/s measured copy ceiling), MI355X_MICROARCH.md
+DUMP_CAP = 1 << 21         # --dump-outputs: elements kept per array (8 MB in float32; five arrays stay under 64 MB)
+DUMP_SEED = 20260101
 
 
 def cpu_quota():
@@ -307,6 +319,20 @@ def other_configs(dev, steps=10, warmup=5):
     return rows
 
 
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each named tensor as out_dir/<name>.npy (float64 stays float64, everything else becomes float32);
+    one above DUMP_CAP elements is reduced to the same seeded sample of flat indices in every run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_CAP:
+            idx = torch.randint(0, t.numel(), (DUMP_CAP,), generator=torch.Generator().manual_seed(DUMP_SEED)).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        a = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -321,11 +347,16 @@ def main():
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp8"],
                     help="operand type of the Linear GEMMs of the encoder blocks (fp8 = OCP e4m3, BASELINE configs[4]; attention and "
                          "everything else stay bf16).  The headline metric is bf16.")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timing", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: CPU baseline, live kernel timing "
+                         "(roofline), loss re-check, exposed communication (N>1), the other BASELINE configurations (one GPU)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (loss, pred, targets, params, grads)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="with --full: skip the live kernel timing")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the side runs of the other BASELINE configurations (ViT-S, ViT-L bf16 / fp8, DINO) that follow the "
-                         "headline's timed region on one GPU")
+                    help="with --full: skip the side runs of the other BASELINE configurations (ViT-S, ViT-L bf16 / fp8, DINO) that "
+                         "follow the headline's timed region on one GPU")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to rehearse the N>1 path on one GPU)")
     ap.add_argument("--share-gpu", action="store_true", help="rehearsal: all ranks use cuda:0")
     args = ap.parse_args()
@@ -358,7 +389,7 @@ def main():
     # The CPU baseline runs FIRST (rank 0, N = 1): the GPU phase then ends the process, where the
     # driver's utilisation sampler can see it.
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(cfg, args.img, args.patch, args.mask_ratio)
     # Host hygiene for the GPU phase: a GPU job gets a small CPU share; torch's default
     # (one OpenMP worker per core, spin-waiting after every parallel CPU op) exhausts it and
@@ -407,14 +438,20 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt)
     final_loss = float(loss)
-    # the fused loss of the last timed step equals mean|pred - target| recomputed by torch on its outputs
-    recomputed = float((model.last_pred - model.last_targets).abs().mean())
-    if not (final_loss == final_loss and abs(recomputed - final_loss) <= 1e-4 * max(1.0, abs(final_loss))):
-        raise SystemExit(f"bench sanity: fused loss {final_loss} vs recomputed {recomputed}")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"loss": torch.tensor([final_loss], dtype=torch.float64), "pred": model.last_pred,
+                                         "targets": model.last_targets, "params": store.flat, "grads": store.gflat})
+    if args.full:
+        # the fused loss of the last timed step equals mean|pred - target| recomputed by torch on its outputs
+        recomputed = float((model.last_pred - model.last_targets).abs().mean())
+        if not (final_loss == final_loss and abs(recomputed - final_loss) <= 1e-4 * max(1.0, abs(final_loss))):
+            raise SystemExit(f"bench sanity: fused loss {final_loss} vs recomputed {recomputed}")
     if world > 1:
+        nb, nbytes = reducer.stats()
+        dp.update(buckets_per_step=nb, reduced_bytes_per_step=nbytes)
+    if world > 1 and args.full:
         # exposed communication = step with the overlapped all-reduce - the same step without any reduction
         # (diagnostic only, after the timed region; the un-reduced steps de-synchronise nothing: same data per rank)
-        nb, nbytes = reducer.stats()
         k = max(3, min(10, args.steps))
         sync()
         t1 = time.perf_counter()
@@ -436,8 +473,9 @@ def main():
         dp["buckets"] = reducer.bucket_times()
         reducer.timing = False
         sync()
-        dp.update(buckets_per_step=nb, reduced_bytes_per_step=nbytes, ms_step_with_allreduce=round(with_comm * 1e3, 3),
-                  ms_step_without_allreduce=round(without * 1e3, 3), exposed_comm_ms=round((with_comm - without) * 1e3, 3))
+        dp.update(ms_step_with_allreduce=round(with_comm * 1e3, 3), ms_step_without_allreduce=round(without * 1e3, 3),
+                  exposed_comm_ms=round((with_comm - without) * 1e3, 3))
+    if world > 1:
         print(f"[bench rank {rank}] {json.dumps(dp)}", file=sys.stderr, flush=True)
 
     N = (args.img // args.patch) ** 2
@@ -451,7 +489,7 @@ def main():
     # ---- live kernel timing of one instrumented step (HIP events on the launch stream)
     roofline = None
     kernels = {}
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         fam, hbm, kernels = instrumented(lambda: model.train_step(x, opt, reducer))
         dom = max(fam.items(), key=lambda kv: kv[1][1])
         name, (fl, ms, cnt) = dom
@@ -479,7 +517,7 @@ def main():
     # ---- the other BASELINE configurations, after (never inside) the headline's timed region; one GPU only
     others = None
     headline = (args.model, args.batch, args.dtype, args.img, args.patch) == ("vit_b", 256, "bf16", 224, 16)
-    if world == 1 and headline and not args.no_other_configs:
+    if args.full and world == 1 and headline and not args.no_other_configs:
         import gc
         last = (model.last_pred, model.last_targets)
         del model, store, opt, x, last

@@ -11,7 +11,7 @@
  * Conventions
  *   - every entry returns 0 on success, <0 on error; vitssl_last_error() gives text
  *   - no allocation, no ownership transfer: all pointers are device pointers owned
- *     by the caller (torch-allocated); shapes are passed explicitly
+ *     by the caller (torch-allocated), scratch workspaces included; shapes are passed explicitly
  *   - kernels are enqueued on `stream` (a hipStream_t passed as void*); no entry
  *     synchronises the device
  *   - bf16 tensors are passed as void* (raw uint16 storage), fp32 as float*
@@ -34,7 +34,7 @@ extern "C" {
 #define VITSSL_ERR_LAUNCH (-2)  /* HIP launch error */
 
 const char* vitssl_last_error(void);
-int vitssl_version(void);
+int vitssl_version(void);   /* 3 */
 
 /* ---- CUs left to other kernels (data parallelism; no reference counterpart: the reference is single-device,
  *      utils/train_utils.py:12-16) -------------------------------------------------------------------------
@@ -76,16 +76,17 @@ int vitssl_layernorm_fwd(const float* x, const float* gamma, const float* beta, 
  *   g_res        [rows,cols] fp32 residual-branch gradient, may be NULL
  *   g_out        [rows,cols] fp32, may alias g_res
  *   gm_bf16      [rows,cols] bf16 = keepmask(drop) * g_out / (1-p), may be NULL
- *   dgamma/dbeta [cols] fp32, ATOMICALLY ACCUMULATED (caller zeroes)
- *   gm_colsum    [cols] fp32 accumulated column sums of gm_bf16, may be NULL */
+ *   dgamma/dbeta [cols] fp32, ACCUMULATED (caller zeroes)
+ *   gm_colsum    [cols] fp32 accumulated column sums of gm_bf16, may be NULL
+ *   workspace    at least vitssl_sum_workspace_floats(rows, cols) floats of scratch (may be NULL when no sum is asked for) */
 int vitssl_layernorm_bwd(const void* dy_bf16, const float* x, const float* mean, const float* rstd,
                          const float* gamma, const float* g_res, float* g_out, void* gm_bf16,
                          float* dgamma, float* dbeta, float* gm_colsum, vitssl_dropout_t drop,
-                         int64_t rows, int cols, void* stream);
+                         int64_t rows, int cols, float* workspace, int64_t workspace_floats, void* stream);
 
-/* Standalone "mask + cast + column-sum" of an fp32 gradient (top of the backward chain). */
+/* Standalone "mask + cast + column-sum" of an fp32 gradient (top of the backward chain); workspace as above. */
 int vitssl_grad_mask_cast(const float* g, void* gm_bf16, float* gm_colsum, vitssl_dropout_t drop,
-                          int64_t rows, int cols, void* stream);
+                          int64_t rows, int cols, float* workspace, int64_t workspace_floats, void* stream);
 
 /* ---- bf16 MFMA GEMM, C[M,N] = A[M,K] . B[N,K]^T, fp32 accumulate ----------------
  * (nn.Linear at vit_core/attention.py:54-58,82-84,105; feed_forward.py:14-15,26-28;
@@ -127,6 +128,8 @@ typedef struct {
   float* colsum;            /* [N] accumulated column sums of out0 (bias grad), or NULL */
   vitssl_dropout_t drop;
   vitssl_embed_t embed;
+  float* workspace;         /* with colsum: at least vitssl_sum_workspace_floats(M, N) floats of scratch, else may be NULL */
+  int64_t workspace_floats;
 } vitssl_gemm_t;
 
 int vitssl_gemm_bf16_nt(const vitssl_gemm_t* g, void* stream);
@@ -175,9 +178,10 @@ int vitssl_layernorm_fwd_fp8(const float* x, const float* gamma, const float* be
 int vitssl_layernorm_bwd_fp8(const void* dy_bf16, const float* x, const float* mean, const float* rstd, const float* gamma,
                              const float* g_res, float* g_out, void* gm_bf16, void* gm_fp8, const float* qscale, float* qamax,
                              float* dgamma, float* dbeta, float* gm_colsum, vitssl_dropout_t drop, int64_t rows, int cols,
-                             void* stream);
+                             float* workspace, int64_t workspace_floats, void* stream);
 int vitssl_grad_mask_cast_fp8(const float* g, void* gm_bf16, void* gm_fp8, const float* qscale, float* qamax, float* gm_colsum,
-                              vitssl_dropout_t drop, int64_t rows, int cols, void* stream);
+                              vitssl_dropout_t drop, int64_t rows, int cols, float* workspace, int64_t workspace_floats,
+                              void* stream);
 /* Per-step fp8 refresh of a table of weights in one call (three launches): per tensor j,
  * amax_j = max|src|, k_j = floor(log2(448 / amax_j)) (0 when amax_j = 0; a power-of-two scale is exact),
  * dst_fp8 [R,C] = e4m3(src * 2^k_j) (forward operand), dst_t_fp8 [C,R] = its transpose (input-gradient operand),
@@ -262,24 +266,35 @@ int vitssl_scatter_cls_f32(const float* gcls, float* g, int B, int T, int D, voi
  * of the projection wgrad (masked rows zeroed, CLS rows dropped) and accumulate
  * d(pos) [T_out, D], d(mask_token) [D], d(bias) [D], d(cls_token) [D]. */
 int64_t vitssl_embed_bwd_workspace_floats(int B, int tokens, int tok_offset, int D);
-/* workspace (may be NULL = atomics only): vitssl_embed_bwd_workspace_floats() floats of scratch
- * through which the single-row accumulators d(mask_token) / d(bias) are reduced without
- * thousands of colliding atomics. */
+/* workspace: vitssl_embed_bwd_workspace_floats() floats of scratch (required) through which every
+ * accumulated gradient is summed in a fixed order. */
 int vitssl_embed_bwd(const float* dtok, const uint8_t* mask, void* dproj_bf16, float* dpos, float* dmask_token,
                      float* dbias, float* dcls, int B, int tokens, int tok_offset, int D, float* workspace,
                      int64_t workspace_floats, void* stream);
 
 /* ---- losses ------------------------------------------------------------------- */
 /* nn.L1Loss(mean) (configs/simmim/training.yaml:2-5): loss_sum += sum|p-t| (caller zeroes,
- * divides by n); dpred_bf16 = sign(p-t) * gscale (gscale = upstream_grad / n) or NULL. */
+ * divides by n); dpred_bf16 = sign(p-t) * gscale (gscale = upstream_grad / n) or NULL;
+ * workspace: at least vitssl_sum_workspace_floats(n, 1) floats. */
 int vitssl_l1_loss(const float* pred, const float* target, float* loss_sum, void* dpred_bf16, float gscale,
-                   int64_t n, void* stream);
+                   int64_t n, float* workspace, int64_t workspace_floats, void* stream);
 /* nn.CrossEntropyLoss(mean) on f32 logits [B,C]; dlogits_bf16 = (softmax - onehot) * gscale */
 int vitssl_cross_entropy(const float* logits, const int64_t* labels, float* loss_sum, void* dlogits_bf16,
                          float gscale, int B, int C, void* stream);
 
-/* out[cols] (fp32, ACCUMULATED) += column sums of x bf16 [rows, cols] (bias gradients). */
-int vitssl_colsum_bf16(const void* x_bf16, float* out, int64_t rows, int cols, void* stream);
+/* out[cols] (fp32, ACCUMULATED) += column sums of x bf16 [rows, cols] (bias gradients); workspace: at least
+ * vitssl_sum_workspace_floats(rows, cols) floats. */
+int vitssl_colsum_bf16(const void* x_bf16, float* out, int64_t rows, int cols, float* workspace, int64_t workspace_floats,
+                       void* stream);
+
+/* Deterministic sums (ABI version 3).  Every sum that many workgroups feed -- column sums (bias gradients) of
+ * vitssl_gemm_bf16_nt / vitssl_gemm_fp8_nt, dgamma / dbeta / gm_colsum of the LayerNorm backward and of
+ * vitssl_grad_mask_cast(_fp8), vitssl_colsum_bf16, the L1 loss, and the embedding gradients of vitssl_embed_bwd -- is
+ * formed without float atomics: each workgroup stores its partial in the caller's workspace and one reduce launch adds
+ * the partials in a fixed order, so the same inputs give the same bits in every run.  The workspace is the caller's
+ * memory; two calls may share one only if they are ordered (one stream).  vitssl_sum_workspace_floats(rows, cols):
+ * floats that suffice for any of these calls summing a [rows, cols] matrix over its rows (for the L1 loss: n, 1). */
+int64_t vitssl_sum_workspace_floats(int64_t rows, int cols);
 
 /* ---- parameter plumbing ----------------------------------------------------------- */
 int vitssl_cast_bf16(const float* src, void* dst, int64_t n, void* stream);

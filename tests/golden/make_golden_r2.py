@@ -17,8 +17,10 @@ needs /root/reference).  Adds to make_golden.py's fixtures:
     (so keys carry the ``_orig_mod.`` prefix the reference really emits) after 3 AdamW steps,
     and the state the reference's own load_weights (utils/model_builder.py:11-89) produces
     from the un-prefixed tensors in a reference fine-tuning ViT.
+  * ``ref_simmim_layout``: the state_dict layout (key -> shape) of a reference SimMIMViT, the
+    target a checkpoint written by this package must load into with strict=True.
 
-    python tests/golden/make_golden_r2.py
+    python tests/golden/make_golden_r2.py [case ...]      (no case: all of them)
 """
 import importlib.util
 import os
@@ -221,10 +223,16 @@ def checkpoint_case():
     save("ckpt_ref_expected", **arrs)
 
 
+def simmim_layout_case():
+    model = SimMIMViT(num_blocks=2, input_shape=(3, 32, 32), embed_dim=64, patch_size=8, num_heads=2, mlp_dim=128,
+                      dropout=0.1, mask_ratio=0.6)
+    save("ref_simmim_layout", **{k: np.array(v.shape, dtype=np.int64) for k, v in model.state_dict().items()})
+
+
+CASES = {"ops_drop": ops_drop_case, "simmim_drop": simmim_drop_case, "manual_embed": manual_embed_case,
+         "dino_trainer_sched": dino_trainer_sched_case, "checkpoint": checkpoint_case, "simmim_layout": simmim_layout_case}
+
 if __name__ == "__main__":
     torch.set_num_threads(4)
-    ops_drop_case()
-    simmim_drop_case()
-    manual_embed_case()
-    dino_trainer_sched_case()
-    checkpoint_case()
+    for case in sys.argv[1:] or CASES:
+        CASES[case]()

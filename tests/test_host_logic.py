@@ -240,31 +240,29 @@ def test_reference_written_checkpoint_loads_like_the_reference(tmp_path):
         assert torch.equal(sim.state_dict()[k], v), k
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/vit_core"), reason="needs the reference checkout (build container only)")
 def test_checkpoint_written_here_loads_into_the_reference(tmp_path):
-    """The other direction: a trainer checkpoint of THIS package (same dict layout) is taken by
-    the reference modules' load_state_dict(strict=True).  Runs the reference in a subprocess."""
-    import subprocess
-    import sys
+    """The other direction: a trainer checkpoint of THIS package (same dict layout) is taken by load_state_dict(strict=True)
+    of a module laid out as the reference SimMIMViT (every state_dict key and shape, recorded from the reference itself:
+    tests/golden/ref_simmim_layout.npz, make_golden_r2.py)."""
     from vit_core.ssl.simmim import SimMIMViT
     torch.manual_seed(5)
     sim = SimMIMViT(2, (3, 32, 32), 64, 8, 2, 128, 0.1, 0.6)
     path = os.path.join(tmp_path, "last_model.pth")
     torch.save({"epoch": 1, "model_state_dict": sim.state_dict(), "optimizer_state_dict": {}, "config": {}}, path)
-    code = (
-        "import sys, torch\n"
-        "sys.path.insert(0, '/root/reference')\n"
-        "from vit_core.ssl.simmim.model import SimMIMViT\n"
-        "m = SimMIMViT(num_blocks=2, input_shape=(3, 32, 32), embed_dim=64, patch_size=8, num_heads=2, mlp_dim=128, dropout=0.1, mask_ratio=0.6)\n"
-        f"ck = torch.load({path!r}, map_location='cpu', weights_only=False)\n"
-        "r = m.load_state_dict(ck['model_state_dict'], strict=True)\n"
-        "assert not r.missing_keys and not r.unexpected_keys\n"
-        "print('ok', float(sum(p.double().sum() for p in m.parameters())))\n")
-    env = {k: v for k, v in os.environ.items() if k != "PYTHONPATH"}
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, cwd=str(tmp_path))
-    assert r.returncode == 0, r.stderr[-2000:]
-    total = float(sum(p.double().sum() for p in sim.parameters()))
-    assert abs(float(r.stdout.split()[1]) - total) < 1e-9 * max(1.0, abs(total))
+    ref = torch.nn.Module()
+    for key, shape in load_golden("ref_simmim_layout").items():
+        *parents, leaf = key.split(".")
+        m = ref
+        for name in parents:
+            if name not in m._modules:
+                m.add_module(name, torch.nn.Module())
+            m = m._modules[name]
+        m.register_parameter(leaf, torch.nn.Parameter(torch.zeros(tuple(int(d) for d in shape))))
+    ck = torch.load(path, map_location="cpu", weights_only=False)
+    r = ref.load_state_dict(ck["model_state_dict"], strict=True)
+    assert not r.missing_keys and not r.unexpected_keys
+    total = float(sum(p.detach().double().sum() for p in sim.parameters()))
+    assert abs(float(sum(p.detach().double().sum() for p in ref.parameters())) - total) < 1e-9 * max(1.0, abs(total))
 
 
 def test_weight_cache_is_hit_until_a_parameter_changes(monkeypatch):
@@ -431,3 +429,25 @@ def test_bench_quotes_pmc_traffic_only_for_these_kernel_sources(tmp_path):
                                                                      "kernel_sources_sha16": sha}))
     assert abs(bench.pmc_clock_ghz("gemm_nt", str(tmp_path)) - 1.9) < 1e-9
     assert bench.pmc_clock_ghz("attn", str(tmp_path)) is None
+
+
+def test_bench_dump_outputs_writes_a_fixed_sample_under_the_cap(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float64 stays float64, everything else is written as float32; an array above DUMP_CAP
+    elements becomes the same sorted, seeded sample of its flat indices in every run, so two builds compare element for element."""
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    monkeypatch.setattr(bench, "DUMP_CAP", 1000)
+    big = torch.arange(5000, dtype=torch.float32).reshape(50, 100)
+    arrays = {"loss": torch.tensor([0.25], dtype=torch.float64), "small": torch.arange(12, dtype=torch.bfloat16).reshape(3, 4),
+              "big": big}
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), {k: v.clone() for k, v in arrays.items()})
+    got = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in arrays}
+    assert sorted(os.listdir(tmp_path / "a")) == ["big.npy", "loss.npy", "small.npy"]
+    assert got["loss"].dtype == np.float64 and got["loss"].tolist() == [0.25]
+    assert got["small"].dtype == np.float32 and np.array_equal(got["small"], np.arange(12, dtype=np.float32).reshape(3, 4))
+    b = got["big"]
+    assert b.dtype == np.float32 and b.shape == (1000,) and np.all(np.diff(b) >= 0) and len(np.unique(b)) > 800
+    for k in arrays:
+        assert np.array_equal(got[k], np.load(tmp_path / "b" / f"{k}.npy")), k

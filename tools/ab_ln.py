@@ -36,13 +36,14 @@ def main():
     gamma, beta = torch.ones(D, device=DEV), torch.zeros(D, device=DEV)
     dgam, dbet, cs = torch.zeros(D, device=DEV), torch.zeros(D, device=DEV), torch.zeros(D, device=DEV)
     mo, ro = torch.empty(M, device=DEV), torch.empty(M, device=DEV)
+    ws = torch.empty(int(L.lib().vitssl_sum_workspace_floats(M, D)), device=DEV)      # scratch of the fixed-order column sums
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
     nodrop, drop = L.Dropout(0.0, 0, 0), L.Dropout(0.1, 2, 1)
     cases = {
         "ln_fwd": (6, lambda lib: lib.vitssl_layernorm_fwd(p(x), p(gamma), p(beta), p(y), p(mo), p(ro), M, D, 1e-5, st)),
-        "ln_bwd": (16, lambda lib: lib.vitssl_layernorm_bwd(p(dy), p(x), p(mo), p(ro), p(gamma), p(gres), p(gout), p(gm), p(dgam), p(dbet), None, nodrop, M, D, st)),
-        "ln_bwd+cs+drop": (16, lambda lib: lib.vitssl_layernorm_bwd(p(dy), p(x), p(mo), p(ro), p(gamma), p(gres), p(gout), p(gm), p(dgam), p(dbet), p(cs), drop, M, D, st)),
+        "ln_bwd": (16, lambda lib: lib.vitssl_layernorm_bwd(p(dy), p(x), p(mo), p(ro), p(gamma), p(gres), p(gout), p(gm), p(dgam), p(dbet), None, nodrop, M, D, p(ws), ws.numel(), st)),
+        "ln_bwd+cs+drop": (16, lambda lib: lib.vitssl_layernorm_bwd(p(dy), p(x), p(mo), p(ro), p(gamma), p(gres), p(gout), p(gm), p(dgam), p(dbet), p(cs), drop, M, D, p(ws), ws.numel(), st)),
     }
     libs[0].vitssl_layernorm_fwd(p(x), p(gamma), p(beta), p(y), p(mo), p(ro), M, D, 1e-5, st)
     print("variants:", " ".join(names), flush=True)

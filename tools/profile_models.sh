@@ -15,9 +15,9 @@ run() {  # name, then the program and its arguments
   find $out/$name -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} gpurun_out/${tag}_${name}_kernel_stats.csv
   echo "profiled $name" >&2
 }
-python3 bench.py --model vit_s --no-cpu-baseline --no-other-configs >> $log 2>/dev/null
-python3 bench.py --model vit_l --batch 128 --no-cpu-baseline --no-other-configs >> $log 2>/dev/null
-python3 bench.py --model vit_l --batch 128 --dtype fp8 --no-cpu-baseline --no-other-configs >> $log 2>/dev/null
+python3 bench.py --model vit_s --no-cpu-baseline --no-other-configs --full >> $log 2>/dev/null
+python3 bench.py --model vit_l --batch 128 --no-cpu-baseline --no-other-configs --full >> $log 2>/dev/null
+python3 bench.py --model vit_l --batch 128 --dtype fp8 --no-cpu-baseline --no-other-configs --full >> $log 2>/dev/null
 python3 tools/bench_dino.py >> $log 2>/dev/null
 python3 tools/bench_dino.py --raw >> $log 2>/dev/null || true
 run vit_s bench.py --model vit_s --steps 8 --warmup 3 --no-cpu-baseline --no-other-configs --no-kernel-timing

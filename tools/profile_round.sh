@@ -3,7 +3,8 @@
 #   gpurun_out/<tag>_kernel_stats.csv   rocprofv3 --kernel-trace --stats of `bench.py` (11 steps)
 #   gpurun_out/<tag>_pmc_traffic.json   FETCH_SIZE / WRITE_SIZE / SQ_BUSY_CYCLES (+ dispatch durations: the clock held) per kernel
 #                                       family, collected in SEPARATE --pmc passes of the same command (MI355X_MICROARCH.md)
-#   gpurun_out/<tag>_bench.json         the plain bench line (with cpu_baseline), taken last so that it carries the PMC traffic
+#   <tag>_bench.json                    (same folder) the `bench.py --full` line (with cpu_baseline), taken last so that it
+#                                       carries the PMC traffic
 # usage: bash tools/profile_round.sh r01_final
 set -e
 tag=${1:-rNN}
@@ -52,9 +53,9 @@ json.dump(res, open(dst, "w"), indent=1)
 print(json.dumps({c: {k: round(v["sum_kb"] / max(v["dispatches"], 1)) for k, v in res[c].items()} for c in ("FETCH_SIZE", "WRITE_SIZE")}))
 print("clock held (GHz):", json.dumps({k: round(v["sum"] / 32.0 / v["duration_ns"], 3) for k, v in res["SQ_BUSY_CYCLES"].items() if v["duration_ns"] > 0}))
 PY
-# the plain bench line LAST, on the same box: bench.py quotes roofline.traffic only from a profiles/*_pmc_traffic.json stamped with
+# the --full bench line LAST, on the same box: bench.py quotes roofline.traffic only from a profiles/*_pmc_traffic.json stamped with
 # these kernel sources, so the summary just made goes where it looks (the copy under profiles/ of the GPU box is scratch: commit
 # the one merged back into gpurun_out/)
 cp gpurun_out/${tag}_pmc_traffic.json profiles/${tag}_pmc_traffic.json
-python3 bench.py > gpurun_out/${tag}_bench.json 2> gpurun_out/${tag}_bench.err
-tail -c 600 gpurun_out/${tag}_bench.json
+python3 bench.py --full > $out/../${tag}_bench.json 2> $out/../${tag}_bench.err
+tail -c 600 $out/../${tag}_bench.json

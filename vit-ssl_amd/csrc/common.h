@@ -64,6 +64,24 @@ typedef std::atomic<bool> VsOnce;   // "hipFuncSetAttribute already done" flags:
     }                                                                                \
   } while (0)
 
+// ---------------------------------------------------------------- deterministic sums
+// Sums fed by many workgroups (bias and LayerNorm-parameter gradients, embedding gradients, the loss) are not accumulated
+// with float atomics, whose order -- and so whose rounding -- changes from run to run: each contributor stores its partial
+// in a slot of the caller's workspace and vs_reduce_parts adds the slots to the target in a fixed order, so that the same
+// inputs give the same bits (include/vitssl_hip.h, vitssl_sum_workspace_floats).
+// vs_parts: the workspace if it holds `need` floats, else nullptr with the error set.
+float* vs_parts(float* workspace, int64_t workspace_floats, long long need, const char* who);
+// target[c] += sum over p = 0 .. nparts-1 of parts[p * stride + c], c < n, always summed in the same order; up to three
+// (target, parts) pairs of one shape in one launch (null targets are skipped)
+struct VsSums {
+  float* target[3];
+  const float* parts[3];
+};
+int vs_reduce_parts(const VsSums& sums, int nparts, long long n, long long stride, hipStream_t s);
+inline int vs_reduce_parts(float* target, const float* parts, int nparts, long long n, long long stride, hipStream_t s) {
+  return vs_reduce_parts(VsSums{{target, nullptr, nullptr}, {parts, nullptr, nullptr}}, nparts, n, stride, s);
+}
+
 // ---------------------------------------------------------------- vector types
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;

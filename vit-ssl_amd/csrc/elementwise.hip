@@ -108,7 +108,7 @@ __global__ void scatter_cls_kernel(const float* __restrict__ gcls, float* __rest
 __global__ void embed_bwd_kernel(const float* __restrict__ dtok, const unsigned char* __restrict__ mask,
                                  bf16_t* __restrict__ dproj, float* __restrict__ dpos, float* __restrict__ dmask_token,
                                  float* __restrict__ dbias, float* __restrict__ dcls, int B, int tokens, int tok_offset, int D,
-                                 float* __restrict__ ws) {
+                                 float* __restrict__ ws, float* __restrict__ pos_parts) {
   const int t = blockIdx.x;
   const int T_out = tokens + tok_offset;
   const int per = (B + gridDim.y - 1) / gridDim.y;
@@ -141,20 +141,10 @@ __global__ void embed_bwd_kernel(const float* __restrict__ dtok, const unsigned 
         }
       }
     }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      if (dpos) atomicAdd(dpos + (long long)t * D + c + r, pos[r]);
-      if (t >= tok_offset) {
-        if (ws) continue;   // single-row accumulators go through the workspace (below)
-        if (dmask_token) atomicAdd(dmask_token + c + r, mt[r]);
-        if (dbias) atomicAdd(dbias + c + r, bias[r]);
-      } else if (dcls) {
-        atomicAdd(dcls + c + r, pos[r]);
-      }
-    }
+    // d(pos) of token t and d(cls) (token 0 with a class token): this split's slot, summed in order by vitssl_embed_bwd
+    if (pos_parts) *(f32x4*)(pos_parts + ((long long)blockIdx.y * T_out + t) * D + c) = pos;
     if (ws && t >= tok_offset) {
-      // d(mask_token) and d(bias) are single rows fed by EVERY block (~2000 adders per
-      // address: the atomic path ran 250-420 us); each block parks its partials instead and
+      // d(mask_token) and d(bias) are single rows fed by EVERY block: each block parks its partials and
       // embed_bwd_reduce_kernel sums them
       float* slot = ws + ((long long)(blockIdx.y * gridDim.x + t) * 2) * D + c;
       *(f32x4*)slot = mt;
@@ -163,10 +153,10 @@ __global__ void embed_bwd_kernel(const float* __restrict__ dtok, const unsigned 
   }
 }
 
-// column sums of the parked partials: ws [nblk][2][D] -> dmask_token[D], dbias[D]; rows of
-// blocks with t < tok_offset were never written and are skipped
-__global__ void embed_bwd_reduce_kernel(const float* __restrict__ ws, float* __restrict__ dmask_token, float* __restrict__ dbias,
-                                        int T_out, int tok_offset, int nblk, int D) {
+// column sums of the parked partials: ws [nblk][2][D] -> one slot row [2][D] (d(mask_token), d(bias)) per row split y, the
+// blocks i = y, y + gridDim.y, ... in order; rows of blocks with t < tok_offset were never written and are skipped
+__global__ void embed_bwd_reduce_kernel(const float* __restrict__ ws, float* __restrict__ parts, int T_out, int tok_offset, int nblk,
+                                        int D) {
   const int c = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
   if (c >= D) return;
   f32x4 mt = {0.f, 0.f, 0.f, 0.f}, bias = mt;
@@ -177,11 +167,9 @@ __global__ void embed_bwd_reduce_kernel(const float* __restrict__ ws, float* __r
     mt += *(const f32x4*)slot;
     bias += *(const f32x4*)(slot + D);
   }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    if (dmask_token) atomicAdd(dmask_token + c + r, mt[r]);
-    if (dbias) atomicAdd(dbias + c + r, bias[r]);
-  }
+  float* slot = parts + (long long)blockIdx.y * 2 * D + c;      // this split's slot row; vitssl_embed_bwd sums them in order
+  *(f32x4*)slot = mt;
+  *(f32x4*)(slot + D) = bias;
 }
 
 // ------------------------------------------------------------------ losses
@@ -206,7 +194,7 @@ __global__ void l1_loss_kernel(const float* __restrict__ pred, const float* __re
   if (threadIdx.x == 0) {
     float s = 0.f;
     for (int w = 0; w < EW_THREADS / 64; ++w) s += part[w];
-    atomicAdd(loss_sum, s);
+    loss_sum[blockIdx.x] = s;                     // this block's slot; vitssl_l1_loss sums the slots in order
   }
 }
 
@@ -372,7 +360,7 @@ __global__ void colsum_bf16_kernel(const bf16_t* __restrict__ x, float* __restri
     acc += f32x4{bf_lo(w[0]), bf_hi(w[0]), bf_lo(w[1]), bf_hi(w[1])};
   }
 #pragma unroll
-  for (int k = 0; k < 4; ++k) atomicAdd(out + c + k, acc[k]);
+  for (int k = 0; k < 4; ++k) out[(long long)blockIdx.y * cols + c + k] = acc[k];     // this split's slot row
 }
 
 inline unsigned stream_grid(long long n4) {
@@ -383,6 +371,66 @@ inline unsigned stream_grid(long long n4) {
 }
 
 }  // namespace
+
+
+// ------------------------------------------------------------------ deterministic sums (common.h)
+// block = CX columns x (256 / CX) slot lanes: lane y sums slots y, y + PY, ... in order, then a fixed tree over the lanes
+__global__ void reduce_parts_kernel(VsSums sums, int nparts, long long n, long long stride) {
+  __shared__ float red[256];
+  float* target = sums.target[blockIdx.y];
+  const float* parts = sums.parts[blockIdx.y];
+  const int CX = blockDim.x, PY = blockDim.y;
+  const long long c = (long long)blockIdx.x * CX + threadIdx.x;
+  float a = 0.f;
+  if (c < n) {
+#pragma unroll 8
+    for (int p = threadIdx.y; p < nparts; p += PY) a += parts[p * stride + c];
+  }
+  red[threadIdx.y * CX + threadIdx.x] = a;
+  __syncthreads();
+  for (int h = PY >> 1; h > 0; h >>= 1) {
+    if ((int)threadIdx.y < h) red[threadIdx.y * CX + threadIdx.x] += red[(threadIdx.y + h) * CX + threadIdx.x];
+    __syncthreads();
+  }
+  if (threadIdx.y == 0 && c < n) target[c] += red[threadIdx.x];
+}
+
+float* vs_parts(float* workspace, int64_t workspace_floats, long long need, const char* who) {
+  if (!workspace || workspace_floats < need) {
+    vitssl_set_error("%s: workspace of %lld floats, need %lld (vitssl_sum_workspace_floats)", who, (long long)(workspace ? workspace_floats : 0),
+                     need);
+    return nullptr;
+  }
+  return workspace;
+}
+
+extern "C" int64_t vitssl_sum_workspace_floats(int64_t rows, int cols) {
+  if (rows <= 0 || cols <= 0) return 0;
+  const long long c = cols;
+  long long ln = (rows + 3) / 4, cap = 2LL * vitssl_persistent_cus();
+  if (ln > cap) ln = cap;
+  long long need = 3 * ln * c;                                   // LayerNorm backward: three sums, one slot row per block
+  const long long nt = ((rows + 95) / 96 + 2) * c;               // NT GEMM: one slot row per wave row group (>= 96 rows)
+  const long long cs = (rows + 127) / 128 < 512 ? (rows + 127) / 128 * c : 512 * c;   // colsum_bf16: one slot row per split
+  if (nt > need) need = nt;
+  if (cs > need) need = cs;
+  return need > 2048 ? need : 2048;                              // the L1 loss: one slot per block (<= 2048)
+}
+
+int vs_reduce_parts(const VsSums& sums, int nparts, long long n, long long stride, hipStream_t s) {
+  VsSums packed = {};
+  int k = 0;
+  for (int i = 0; i < 3; ++i)
+    if (sums.target[i]) {
+      packed.target[k] = sums.target[i];
+      packed.parts[k++] = sums.parts[i];
+    }
+  if (k == 0) return VITSSL_OK;
+  const int cx = n >= 16 ? 16 : 1;
+  hipLaunchKernelGGL(reduce_parts_kernel, dim3((unsigned)((n + cx - 1) / cx), k), dim3(cx, 256 / cx), 0, s, packed, nparts, n, stride);
+  VS_CHECK_LAUNCH("reduce_parts");
+  return VITSSL_OK;
+}
 
 extern "C" int vitssl_dropout_mask(uint8_t* keep, int64_t rows, int64_t cols, vitssl_dropout_t d, void* stream) {
   VS_CHECK_ARG(keep && rows > 0 && cols > 0 && cols % 4 == 0, "dropout_mask: cols must be a multiple of 4");
@@ -459,10 +507,18 @@ static int embed_bwd_splits(int B, int T_out) {
   return bs;
 }
 
+// [bs * T_out][2][D] parked partials of d(mask_token) / d(bias), then the slot rows of the fixed-order sums
+constexpr int EMBED_YSPLITS = 128;                   // row splits of embed_bwd_reduce_kernel
+static long long embed_slots_floats(int bs, int T_out, int D) {
+  const long long a = (long long)bs * T_out * D, b = (long long)EMBED_YSPLITS * 2 * D;
+  return a > b ? a : b;
+}
+static int64_t embed_ws_floats(int bs, int T_out, int D) { return (int64_t)bs * T_out * 2 * D + embed_slots_floats(bs, T_out, D); }
+
 extern "C" int64_t vitssl_embed_bwd_workspace_floats(int B, int tokens, int tok_offset, int D) {
   if (B <= 0 || tokens <= 0 || D <= 0) return 0;
   const int T_out = tokens + tok_offset;
-  return (int64_t)embed_bwd_splits(B, T_out) * T_out * 2 * D;
+  return embed_ws_floats(embed_bwd_splits(B, T_out), T_out, D);
 }
 
 extern "C" int vitssl_embed_bwd(const float* dtok, const uint8_t* mask, void* dproj_bf16, float* dpos, float* dmask_token,
@@ -473,29 +529,39 @@ extern "C" int vitssl_embed_bwd(const float* dtok, const uint8_t* mask, void* dp
   VS_CHECK_ARG(!mask || dmask_token, "embed_bwd: mask without dmask_token");
   const int T_out = tokens + tok_offset;
   const int bs = embed_bwd_splits(B, T_out);
-  const int64_t need = (int64_t)bs * T_out * 2 * D;
-  VS_CHECK_ARG(!workspace || workspace_floats >= need, "embed_bwd: workspace of %lld floats, need %lld", (long long)workspace_floats,
-               (long long)need);
-  float* ws = (dmask_token || dbias) ? workspace : nullptr;   // NULL workspace = atomics fallback
+  const int ysplits = EMBED_YSPLITS;
+  if (!vs_parts(workspace, workspace_floats, embed_ws_floats(bs, T_out, D), "embed_bwd")) return VITSSL_ERR_ARG;
+  float* ws = (dmask_token || dbias) ? workspace : nullptr;
+  float* parts = workspace + (long long)bs * T_out * 2 * D;
+  const bool pos_sums = dpos || (dcls && tok_offset == 1);
   hipLaunchKernelGGL(embed_bwd_kernel, dim3(T_out, bs), dim3(EW_THREADS), 0, (hipStream_t)stream, dtok, mask, (bf16_t*)dproj_bf16,
-                     dpos, dmask_token, dbias, dcls, B, tokens, tok_offset, D, ws);
+                     dpos, dmask_token, dbias, dcls, B, tokens, tok_offset, D, ws, pos_sums ? parts : nullptr);
   VS_CHECK_LAUNCH("embed_bwd");
+  const long long rows = (long long)T_out * D;
+  if (dpos && vs_reduce_parts(dpos, parts, bs, rows, rows, (hipStream_t)stream) != VITSSL_OK) return VITSSL_ERR_LAUNCH;
+  if (dcls && tok_offset == 1 && vs_reduce_parts(dcls, parts, bs, D, rows, (hipStream_t)stream) != VITSSL_OK) return VITSSL_ERR_LAUNCH;
   if (ws) {
     const int nblk = bs * T_out;
-    hipLaunchKernelGGL(embed_bwd_reduce_kernel, dim3((D / 4 + 63) / 64, 128), dim3(64), 0, (hipStream_t)stream, ws, dmask_token, dbias,
+    hipLaunchKernelGGL(embed_bwd_reduce_kernel, dim3((D / 4 + 63) / 64, ysplits), dim3(64), 0, (hipStream_t)stream, ws, parts,
                        T_out, tok_offset, nblk, D);
     VS_CHECK_LAUNCH("embed_bwd_reduce");
+    if (vs_reduce_parts(VsSums{{dmask_token, dbias, nullptr}, {parts, parts + D, nullptr}}, ysplits, D, 2LL * D, (hipStream_t)stream) !=
+        VITSSL_OK)
+      return VITSSL_ERR_LAUNCH;
   }
   return VITSSL_OK;
 }
 
 extern "C" int vitssl_l1_loss(const float* pred, const float* target, float* loss_sum, void* dpred_bf16, float gscale,
-                              int64_t n, void* stream) {
+                              int64_t n, float* workspace, int64_t workspace_floats, void* stream) {
   VS_CHECK_ARG(pred && target && loss_sum && n > 0 && n % 4 == 0, "l1_loss: n=%lld must be a positive multiple of 4", (long long)n);
-  hipLaunchKernelGGL(l1_loss_kernel, dim3(stream_grid(n / 4)), dim3(EW_THREADS), 0, (hipStream_t)stream, pred, target, loss_sum,
+  const unsigned grid = stream_grid(n / 4);
+  float* parts = vs_parts(workspace, workspace_floats, grid, "l1_loss");
+  if (!parts) return VITSSL_ERR_ARG;
+  hipLaunchKernelGGL(l1_loss_kernel, dim3(grid), dim3(EW_THREADS), 0, (hipStream_t)stream, pred, target, parts,
                      (bf16_t*)dpred_bf16, gscale, (long long)(n / 4));
   VS_CHECK_LAUNCH("l1_loss");
-  return VITSSL_OK;
+  return vs_reduce_parts(loss_sum, parts, (int)grid, 1, 1, (hipStream_t)stream);
 }
 
 extern "C" int vitssl_cross_entropy(const float* logits, const int64_t* labels, float* loss_sum, void* dlogits_bf16,
@@ -507,14 +573,17 @@ extern "C" int vitssl_cross_entropy(const float* logits, const int64_t* labels, 
   return VITSSL_OK;
 }
 
-extern "C" int vitssl_colsum_bf16(const void* x_bf16, float* out, int64_t rows, int cols, void* stream) {
+extern "C" int vitssl_colsum_bf16(const void* x_bf16, float* out, int64_t rows, int cols, float* workspace, int64_t workspace_floats,
+                                  void* stream) {
   VS_CHECK_ARG(x_bf16 && out && rows > 0 && cols > 0 && cols % 4 == 0, "colsum_bf16: bad args");
   int splits = (int)((rows + 127) / 128);
   if (splits > 512) splits = 512;
+  float* parts = vs_parts(workspace, workspace_floats, (long long)splits * cols, "colsum_bf16");
+  if (!parts) return VITSSL_ERR_ARG;
   hipLaunchKernelGGL(colsum_bf16_kernel, dim3((cols / 4 + EW_THREADS - 1) / EW_THREADS, splits), dim3(EW_THREADS), 0,
-                     (hipStream_t)stream, (const bf16_t*)x_bf16, out, (long long)rows, cols);
+                     (hipStream_t)stream, (const bf16_t*)x_bf16, parts, (long long)rows, cols);
   VS_CHECK_LAUNCH("colsum_bf16");
-  return VITSSL_OK;
+  return vs_reduce_parts(out, parts, splits, cols, cols, (hipStream_t)stream);
 }
 
 extern "C" int vitssl_cast_bf16(const float* src, void* dst, int64_t n, void* stream) {

@@ -152,6 +152,8 @@ struct NtParams {
   void* out0;
   void* out1;
   float* colsum;
+  float* workspace;          // slot rows of the column sums (caller's, vitssl_gemm_t.workspace)
+  int64_t workspace_floats;
   DropKey dk;
   int drop_on;
   vitssl_embed_t embed;
@@ -752,10 +754,9 @@ __device__ __forceinline__ void nt_epilogue(const NtParams& p, f32x4 (&acc)[4][C
       }
     }
     if (tls) {
-      // One atomic instruction per wave and tile, 64 lanes on 256 contiguous bytes (the float-atomic path's full-rate shape),
-      // instead of sixteen with four active lanes each: the 64 column sums of the wave pass through its LDS window (column
-      // 16 j + 4 g + r of lane group g -> float slot of that column).  Round 4: the sixteen-instruction form cost ~10 us of a
-      // 266 us dGELU launch (the atomics are paced per instruction, ~50 ns per CU).
+      // One store instruction per wave and tile, 64 lanes on 256 contiguous bytes of the wave's slot row, instead of sixteen
+      // with four active lanes each: the 64 column sums of the wave pass through its LDS window (column 16 j + 4 g + r of lane
+      // group g -> float slot of that column).
       if ((lane & 15) == 0) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) *(f32x4*)(xs + (16 * j + 4 * g4) * 4) = red[j];
@@ -763,14 +764,14 @@ __device__ __forceinline__ void nt_epilogue(const NtParams& p, f32x4 (&acc)[4][C
       asm volatile("" ::: "memory");                  // (the wave's LDS operations execute in order; this keeps hipcc from reordering them)
       const float v = *(const volatile float*)(xs + lane * 4);
       const int n = n0 + wn * 64 + lane;
-      if (n < p.N) atomicAdd(p.colsum + n, v);
+      if (n < p.N) p.colsum[(m0 / CFG::WROWS + wm) * p.N + n] = v;      // the wave's slot row (launch_cfg sums them)
     } else {
 #pragma unroll
       for (int j = 0; j < 4; ++j)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int n = n0 + wn * 64 + j * 16 + 4 * (lane >> 4) + r;
-          if ((lane & 15) == 0 && n < p.N) atomicAdd(p.colsum + n, red[j][r]);
+          if ((lane & 15) == 0 && n < p.N) p.colsum[(m0 / CFG::WROWS + wm) * p.N + n] = red[j][r];
         }
     }
   }
@@ -1406,7 +1407,7 @@ int launch_pp(NtParams p, hipStream_t s) {
 }
 
 template <int EPI, typename CFG>
-int launch_cfg(NtParams p, hipStream_t s) {
+int launch_cfg_parts(NtParams p, hipStream_t s) {
   static VsOnce attr_done{false};
   if (!attr_done.load(std::memory_order_relaxed) && CFG::LDS_BYTES > 48 * 1024) {
     hipError_t e = hipFuncSetAttribute((const void*)gemm_nt_kernel<EPI, CFG>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1495,7 +1496,22 @@ int launch_splitk_f32(NtParams p, hipStream_t s, bool* done) {
     return VITSSL_ERR_LAUNCH;
   }
   *done = true;
-  return launch_cfg<EPI_F32_SPLITK, NtSmall>(p, s);
+  return launch_cfg_parts<EPI_F32_SPLITK, NtSmall>(p, s);      // no column sums here
+}
+
+
+// Column sums (bias gradients): every wave stores its sums in the slot row of its row group (tile row x waves along M, rows past M
+// included, as zeros), and the slot rows are added to p.colsum in a fixed order (common.h, deterministic sums).
+template <int EPI, typename CFG>
+int launch_cfg(NtParams p, hipStream_t s) {
+  float* colsum = p.colsum;
+  if (!colsum) return launch_cfg_parts<EPI, CFG>(p, s);
+  const int groups = (int)ceil_div64(p.M, CFG::BM) * (CFG::BM / CFG::WROWS);
+  p.colsum = vs_parts(p.workspace, p.workspace_floats, (long long)groups * p.N, "gemm_nt column sums");
+  if (!p.colsum) return VITSSL_ERR_ARG;
+  const int rc = launch_cfg_parts<EPI, CFG>(p, s);
+  if (rc != VITSSL_OK) return rc;
+  return vs_reduce_parts(colsum, p.colsum, groups, p.N, p.N, s);
 }
 
 template <int EPI>
@@ -1618,6 +1634,8 @@ static int gemm_nt_entry(const vitssl_gemm_t* g, int esz, const vitssl_fp8_gemm_
   p.out0 = g->out0;
   p.out1 = g->out1;
   p.colsum = g->colsum;
+  p.workspace = g->workspace;
+  p.workspace_floats = g->workspace_floats;
   p.dk = make_drop_key(g->drop);
   p.drop_on = p.dk.thr != 0;
   p.embed = g->embed;

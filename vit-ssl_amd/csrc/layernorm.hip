@@ -326,7 +326,7 @@ __global__ __launch_bounds__(LN_THREADS, ln_bwd_blocks(V, HAS_LN, HAS_CS)) void 
       if (lane == 0 && __float_as_uint(qmax) > __builtin_nontemporal_load(slot)) atomicMax(slot, __float_as_uint(qmax));
     }
   }
-  // cross-wave column reduction, one atomic per column per block (LDS buffer reused)
+  // cross-wave column reduction into this block's slot row of each sum (LDS buffer reused); launch_ln_bwd sums the slots
 #pragma unroll
   for (int qty = 0; qty < 3; ++qty) {
     if (qty < 2 && !HAS_LN) continue;
@@ -345,17 +345,18 @@ __global__ __launch_bounds__(LN_THREADS, ln_bwd_blocks(V, HAS_LN, HAS_CS)) void 
     if constexpr (PAIR) {                            // a column's two slots: columns c and c + cols / 2 of the pair
       const int ch = cols >> 1;
       for (int c = threadIdx.x; c < ch; c += LN_THREADS)
-        atomicAdd(target + c, (red[0][c] + red[1][c] + red[2][c] + red[3][c]) +
-                                  (red[0][c + ch] + red[1][c + ch] + red[2][c + ch] + red[3][c + ch]));
+        target[(long long)blockIdx.x * ch + c] = (red[0][c] + red[1][c] + red[2][c] + red[3][c]) +
+                                                 (red[0][c + ch] + red[1][c + ch] + red[2][c + ch] + red[3][c + ch]);
     } else {
       for (int c = threadIdx.x; c < cols; c += LN_THREADS)
-        atomicAdd(target + c, red[0][c] + red[1][c] + red[2][c] + red[3][c]);
+        target[(long long)blockIdx.x * cols + c] = red[0][c] + red[1][c] + red[2][c] + red[3][c];
     }
     __syncthreads();
   }
 }
 
-// Blocks of 4 rows, grid-stride.  Backward: every block ends with one atomic per column per accumulated vector, and
+// Blocks of 4 rows, grid-stride.  Backward: every block ends with one slot row per accumulated vector (summed in order by a
+// reduce launch; the measurements below were taken when it was one atomic per column), and
 // the register budget admits 2-4 blocks per CU, so a grid larger than what is resident at once only adds such tails:
 // one block per CU (two for rows of <= 512 columns) is fastest now that the next row is prefetched (MI355X, interleaved
 // A/B against the former cap of 2048: M = 50176, D = 768: 123 -> 110 us, with column sums 126 -> 111; D = 1024,
@@ -377,7 +378,7 @@ inline int ln_grid(long long rows, bool fwd = false, int cols = 1024) {
 }
 
 template <bool HAS_LN, bool Q8 = false>
-int launch_ln_bwd(const void* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
+int launch_ln_bwd_parts(const void* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
                   const float* g_res, float* g_out, void* gm, float* dgamma, float* dbeta, float* gm_colsum,
                   vitssl_dropout_t drop, int64_t rows, int cols, hipStream_t s, void* gm8 = nullptr,
                   const float* qscale = nullptr, float* qamax = nullptr) {
@@ -420,6 +421,31 @@ int launch_ln_bwd(const void* dy, const float* x, const float* mean, const float
 #undef VS_LNB
   VS_CHECK_LAUNCH("layernorm_bwd");
   return VITSSL_OK;
+}
+
+// The kernel writes one slot row per block for each column sum (dgamma, dbeta, gm_colsum); they are then added to the targets
+// in a fixed order (common.h, deterministic sums).
+template <bool HAS_LN, bool Q8 = false>
+int launch_ln_bwd(const void* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
+                  const float* g_res, float* g_out, void* gm, float* dgamma, float* dbeta, float* gm_colsum,
+                  vitssl_dropout_t drop, int64_t rows, int cols, float* workspace, int64_t workspace_floats, hipStream_t s,
+                  void* gm8 = nullptr, const float* qscale = nullptr, float* qamax = nullptr) {
+  const bool pair = HAS_LN && !Q8 && LN_PREFETCH && LN_ROW_PAIRS && cols == 384 && (rows & 1) == 0;
+  const int grid = pair ? ln_grid(rows / 2, false, 768) : ln_grid(rows, false, cols);
+  const long long slab = (long long)grid * cols;
+  if (!((HAS_LN && (dgamma || dbeta)) || gm_colsum))
+    return launch_ln_bwd_parts<HAS_LN, Q8>(dy, x, mean, rstd, gamma, g_res, g_out, gm, nullptr, nullptr, nullptr, drop, rows, cols, s, gm8,
+                                           qscale, qamax);
+  float* parts = vs_parts(workspace, workspace_floats, 3 * slab, "layernorm_bwd / grad_mask_cast");
+  if (!parts) return VITSSL_ERR_ARG;
+  float* pg = HAS_LN && dgamma ? parts : nullptr;
+  float* pb = HAS_LN && dbeta ? parts + slab : nullptr;
+  float* pc = gm_colsum ? parts + 2 * slab : nullptr;
+  const int rc = launch_ln_bwd_parts<HAS_LN, Q8>(dy, x, mean, rstd, gamma, g_res, g_out, gm, pg, pb, pc, drop, rows, cols, s, gm8,
+                                                 qscale, qamax);
+  if (rc != VITSSL_OK) return rc;
+  return vs_reduce_parts(VsSums{{pg ? dgamma : nullptr, pb ? dbeta : nullptr, pc ? gm_colsum : nullptr}, {pg, pb, pc}}, grid, cols,
+                         cols, s);
 }
 
 }  // namespace
@@ -465,36 +491,36 @@ extern "C" int vitssl_layernorm_fwd_fp8(const float* x, const float* gamma, cons
 extern "C" int vitssl_layernorm_bwd(const void* dy_bf16, const float* x, const float* mean, const float* rstd,
                                     const float* gamma, const float* g_res, float* g_out, void* gm_bf16, float* dgamma,
                                     float* dbeta, float* gm_colsum, vitssl_dropout_t drop, int64_t rows, int cols,
-                                    void* stream) {
+                                    float* workspace, int64_t workspace_floats, void* stream) {
   VS_CHECK_ARG(dy_bf16 && x && mean && rstd && gamma && g_out && dgamma && dbeta, "layernorm_bwd: null pointer");
   VS_CHECK_ARG(rows > 0 && cols > 0 && cols % 4 == 0 && cols <= 2048, "layernorm_bwd: cols=%d must be a multiple of 4 and <= 2048", cols);
   VS_CHECK_ARG(!gm_colsum || gm_bf16, "layernorm_bwd: gm_colsum without gm_bf16");
   return launch_ln_bwd<true>(dy_bf16, x, mean, rstd, gamma, g_res, g_out, gm_bf16, dgamma, dbeta, gm_colsum, drop, rows,
-                             cols, (hipStream_t)stream);
+                             cols, workspace, workspace_floats, (hipStream_t)stream);
 }
 
 extern "C" int vitssl_layernorm_bwd_fp8(const void* dy_bf16, const float* x, const float* mean, const float* rstd,
                                         const float* gamma, const float* g_res, float* g_out, void* gm_bf16, void* gm_fp8,
                                         const float* qscale, float* qamax, float* dgamma, float* dbeta, float* gm_colsum,
-                                        vitssl_dropout_t drop, int64_t rows, int cols, void* stream) {
+                                        vitssl_dropout_t drop, int64_t rows, int cols, float* workspace, int64_t workspace_floats, void* stream) {
   VS_CHECK_ARG(dy_bf16 && x && mean && rstd && gamma && g_out && dgamma && dbeta && gm_fp8, "layernorm_bwd_fp8: null pointer");   // gm_bf16 may be NULL
   VS_CHECK_ARG(rows > 0 && cols > 0 && cols % 4 == 0 && cols <= 2048, "layernorm_bwd_fp8: cols=%d must be a multiple of 4 and <= 2048", cols);
   return launch_ln_bwd<true, true>(dy_bf16, x, mean, rstd, gamma, g_res, g_out, gm_bf16, dgamma, dbeta, gm_colsum, drop, rows,
-                                   cols, (hipStream_t)stream, gm_fp8, qscale, qamax);
+                                   cols, workspace, workspace_floats, (hipStream_t)stream, gm_fp8, qscale, qamax);
 }
 
 extern "C" int vitssl_grad_mask_cast_fp8(const float* g, void* gm_bf16, void* gm_fp8, const float* qscale, float* qamax,
-                                         float* gm_colsum, vitssl_dropout_t drop, int64_t rows, int cols, void* stream) {
+                                         float* gm_colsum, vitssl_dropout_t drop, int64_t rows, int cols, float* workspace, int64_t workspace_floats, void* stream) {
   VS_CHECK_ARG(g && gm_fp8, "grad_mask_cast_fp8: null pointer");   // gm_bf16 may be NULL
   VS_CHECK_ARG(rows > 0 && cols > 0 && cols % 4 == 0 && cols <= 2048, "grad_mask_cast_fp8: cols=%d must be a multiple of 4 and <= 2048", cols);
   return launch_ln_bwd<false, true>(nullptr, nullptr, nullptr, nullptr, nullptr, g, nullptr, gm_bf16, nullptr, nullptr,
-                                    gm_colsum, drop, rows, cols, (hipStream_t)stream, gm_fp8, qscale, qamax);
+                                    gm_colsum, drop, rows, cols, workspace, workspace_floats, (hipStream_t)stream, gm_fp8, qscale, qamax);
 }
 
 extern "C" int vitssl_grad_mask_cast(const float* g, void* gm_bf16, float* gm_colsum, vitssl_dropout_t drop,
-                                     int64_t rows, int cols, void* stream) {
+                                     int64_t rows, int cols, float* workspace, int64_t workspace_floats, void* stream) {
   VS_CHECK_ARG(g && gm_bf16, "grad_mask_cast: null pointer");
   VS_CHECK_ARG(rows > 0 && cols > 0 && cols % 4 == 0 && cols <= 2048, "grad_mask_cast: cols=%d must be a multiple of 4 and <= 2048", cols);
   return launch_ln_bwd<false>(nullptr, nullptr, nullptr, nullptr, nullptr, g, nullptr, gm_bf16, nullptr, nullptr,
-                              gm_colsum, drop, rows, cols, (hipStream_t)stream);
+                              gm_colsum, drop, rows, cols, workspace, workspace_floats, (hipStream_t)stream);
 }

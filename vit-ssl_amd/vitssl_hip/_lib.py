@@ -37,7 +37,8 @@ class Fp8TnJob(C.Structure):
 class Gemm(C.Structure):
     _fields_ = [("A", C.c_void_p), ("B", C.c_void_p), ("M", C.c_int64), ("N", C.c_int), ("K", C.c_int),
                 ("epilogue", C.c_int), ("bias", C.c_void_p), ("aux", C.c_void_p), ("out0", C.c_void_p),
-                ("out1", C.c_void_p), ("colsum", C.c_void_p), ("drop", Dropout), ("embed", Embed)]
+                ("out1", C.c_void_p), ("colsum", C.c_void_p), ("drop", Dropout), ("embed", Embed),
+                ("workspace", C.c_void_p), ("workspace_floats", C.c_int64)]
 
 
 class Fp8Gemm(C.Structure):
@@ -47,15 +48,15 @@ class Fp8Gemm(C.Structure):
 
 EPI_BF16, EPI_F32, EPI_GELU, EPI_RESID, EPI_DGELU, EPI_EMBED = range(6)
 
-ABI_VERSION = 2          # vitssl_version(): 2 = vitssl_dino_loss takes the size of its scratch buffer
+ABI_VERSION = 3          # vitssl_version(): 2 = vitssl_dino_loss takes the size of its scratch buffer; 3 = the deterministic sums take a workspace
 _vp, _i, _i64, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
 
 # name -> argtypes (restype is always int except the two noted)
 PROTOTYPES = {
     "vitssl_dropout_mask": [_vp, _i64, _i64, Dropout, _vp],
     "vitssl_layernorm_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _f, _vp],
-    "vitssl_layernorm_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, Dropout, _i64, _i, _vp],
-    "vitssl_grad_mask_cast": [_vp, _vp, _vp, Dropout, _i64, _i, _vp],
+    "vitssl_layernorm_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, Dropout, _i64, _i, _vp, _i64, _vp],
+    "vitssl_grad_mask_cast": [_vp, _vp, _vp, Dropout, _i64, _i, _vp, _i64, _vp],
     "vitssl_gemm_bf16_nt": [C.POINTER(Gemm), _vp],
     "vitssl_gemm_bf16_tn": [_vp, _vp, _vp, _i64, _i, _i, _vp, _i64, _vp],
     "vitssl_gemm_bf16_tn_batch": [C.POINTER(TnJob), _i, _i64, _vp, _i64, _vp],
@@ -65,8 +66,9 @@ PROTOTYPES = {
     "vitssl_quantize_fp8": [_vp, _vp, _i64, _vp],
     "vitssl_attn_bwd_fp8": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "vitssl_quantize_fp8_scaled": [_vp, _vp, _i64, _vp, _vp, _vp],
-    "vitssl_layernorm_bwd_fp8": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, Dropout, _i64, _i, _vp],
-    "vitssl_grad_mask_cast_fp8": [_vp, _vp, _vp, _vp, _vp, _vp, Dropout, _i64, _i, _vp],
+    "vitssl_layernorm_bwd_fp8": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, Dropout, _i64, _i, _vp, _i64,
+                                 _vp],
+    "vitssl_grad_mask_cast_fp8": [_vp, _vp, _vp, _vp, _vp, _vp, Dropout, _i64, _i, _vp, _i64, _vp],
     "vitssl_attn_fwd_fp8": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "vitssl_layernorm_fwd_fp8": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _f, _vp],
     "vitssl_fp8_quantize_weights": [_vp, _vp, _i, _i, _vp, _vp, _vp],
@@ -79,9 +81,9 @@ PROTOTYPES = {
     "vitssl_gather_cls_f32": [_vp, _vp, _i, _i, _i, _vp],
     "vitssl_scatter_cls_f32": [_vp, _vp, _i, _i, _i, _vp],
     "vitssl_embed_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i64, _vp],
-    "vitssl_l1_loss": [_vp, _vp, _vp, _vp, _f, _i64, _vp],
+    "vitssl_l1_loss": [_vp, _vp, _vp, _vp, _f, _i64, _vp, _i64, _vp],
     "vitssl_cross_entropy": [_vp, _vp, _vp, _vp, _f, _i, _i, _vp],
-    "vitssl_colsum_bf16": [_vp, _vp, _i64, _i, _vp],
+    "vitssl_colsum_bf16": [_vp, _vp, _i64, _i, _vp, _i64, _vp],
     "vitssl_cast_bf16": [_vp, _vp, _i64, _vp],
     "vitssl_cast_transpose_bf16": [_vp, _vp, _vp, _i, _i, _vp],
     "vitssl_cast_transpose_batch": [_vp, _vp, _i, _i, _vp],
@@ -144,6 +146,8 @@ def lib():
     l.vitssl_gemm_fp8_tn_workspace_floats.argtypes = [C.c_int64, C.c_int, C.c_int]
     l.vitssl_dino_loss_workspace_floats.restype = C.c_int64
     l.vitssl_dino_loss_workspace_floats.argtypes = [C.c_int, C.c_int, C.c_int]
+    l.vitssl_sum_workspace_floats.restype = C.c_int64
+    l.vitssl_sum_workspace_floats.argtypes = [C.c_int64, C.c_int]
     l.vitssl_embed_bwd_workspace_floats.restype = C.c_int64
     l.vitssl_embed_bwd_workspace_floats.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
     for getter in ("vitssl_get_reserved_cus", "vitssl_debug_last_nt_grid", "vitssl_debug_last_attn_fwd_grid"):

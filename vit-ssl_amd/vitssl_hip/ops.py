@@ -139,14 +139,15 @@ def layernorm_bwd_fp8(dy, x, mean, rstd, gamma, g_res, g_out, gm, gm8, scale, am
          _chk(rstd, F32, "rstd", (rows,)), _chk(gamma, F32, "gamma", (cols,)), _opt(g_res, F32, "g_res", (rows, cols)),
          _chk(g_out, F32, "g_out", (rows, cols)), _opt(gm, BF16, "gm", (rows, cols)), _chk(gm8, FP8, "gm8", (rows, cols)),
          _scalar(scale, "scale"), _scalar(amax, "amax"), _chk(dgamma, F32, "dgamma", (cols,)), _chk(dbeta, F32, "dbeta", (cols,)),
-         _opt(gm_colsum, F32, "gm_colsum", (cols,)), drop, rows, cols, _stream())
+         _opt(gm_colsum, F32, "gm_colsum", (cols,)), drop, rows, cols, *_sum_ws(x.device, rows, cols), _stream())
     _prof_end(ev, "ln_bwd", 0.0, rows * (cols * (2 + 4 + (4 if g_res is not None else 0) + 4 + (3 if gm is not None else 1)) + 8))
 
 
 def grad_mask_cast_fp8(g, gm, gm8, scale, amax, gm_colsum=None, drop=NO_DROP):
     rows, cols = g.shape
     call("vitssl_grad_mask_cast_fp8", _chk(g, F32, "g"), _opt(gm, BF16, "gm", (rows, cols)), _chk(gm8, FP8, "gm8", (rows, cols)),
-         _scalar(scale, "scale"), _scalar(amax, "amax"), _opt(gm_colsum, F32, "gm_colsum", (cols,)), drop, rows, cols, _stream())
+         _scalar(scale, "scale"), _scalar(amax, "amax"), _opt(gm_colsum, F32, "gm_colsum", (cols,)), drop, rows, cols,
+         *_sum_ws(g.device, rows, cols), _stream())
 
 
 def layernorm_bwd(dy, x, mean, rstd, gamma, g_res, g_out, gm, dgamma, dbeta, gm_colsum=None, drop=NO_DROP):
@@ -155,7 +156,8 @@ def layernorm_bwd(dy, x, mean, rstd, gamma, g_res, g_out, gm, dgamma, dbeta, gm_
     call("vitssl_layernorm_bwd", _chk(dy, BF16, "dy", (rows, cols)), _chk(x, F32, "x"), _chk(mean, F32, "mean", (rows,)),
          _chk(rstd, F32, "rstd", (rows,)), _chk(gamma, F32, "gamma", (cols,)), _opt(g_res, F32, "g_res", (rows, cols)),
          _chk(g_out, F32, "g_out", (rows, cols)), _opt(gm, BF16, "gm", (rows, cols)), _chk(dgamma, F32, "dgamma", (cols,)),
-         _chk(dbeta, F32, "dbeta", (cols,)), _opt(gm_colsum, F32, "gm_colsum", (cols,)), drop, rows, cols, _stream())
+         _chk(dbeta, F32, "dbeta", (cols,)), _opt(gm_colsum, F32, "gm_colsum", (cols,)), drop, rows, cols, *_sum_ws(x.device, rows, cols),
+         _stream())
     # dy bf16 + x fp32 (+ residual gradient fp32) in, gradient fp32 (+ masked bf16 operand) out
     _prof_end(ev, "ln_bwd", 0.0, rows * (cols * (2 + 4 + (4 if g_res is not None else 0) + 4 + (2 if gm is not None else 0)) + 8))
 
@@ -163,7 +165,7 @@ def layernorm_bwd(dy, x, mean, rstd, gamma, g_res, g_out, gm, dgamma, dbeta, gm_
 def grad_mask_cast(g, gm, gm_colsum=None, drop=NO_DROP):
     rows, cols = g.shape
     call("vitssl_grad_mask_cast", _chk(g, F32, "g"), _chk(gm, BF16, "gm", (rows, cols)),
-         _opt(gm_colsum, F32, "gm_colsum", (cols,)), drop, rows, cols, _stream())
+         _opt(gm_colsum, F32, "gm_colsum", (cols,)), drop, rows, cols, *_sum_ws(g.device, rows, cols), _stream())
 
 
 _OUT0_DTYPE = {L.EPI_BF16: BF16, L.EPI_F32: F32, L.EPI_GELU: BF16, L.EPI_RESID: F32, L.EPI_DGELU: BF16, L.EPI_EMBED: F32}
@@ -202,6 +204,8 @@ def gemm_nt(A, B, out0, epilogue, bias=None, aux=None, out1=None, colsum=None, d
         g.aux = _chk(aux, BF16, "aux(u)", (M, N))
     g.out1 = _opt(out1, BF16, "out1", (M, N))
     g.colsum = _opt(colsum, F32, "colsum", (N,))
+    if colsum is not None:
+        g.workspace, g.workspace_floats = _sum_ws(colsum.device, M, N)
     g.drop = drop
     ev = _prof_begin()
     call("vitssl_gemm_bf16_nt", C.byref(g), _stream())
@@ -235,6 +239,8 @@ def gemm_fp8_nt(A8, B8, out0, epilogue, alpha=None, bias=None, aux=None, out1=No
         g.aux = _chk(aux, BF16, "aux(g')", (M, N))
     g.out1 = _opt(out1, BF16, "out1", (M, N))
     g.colsum = _opt(colsum, F32, "colsum", (N,))
+    if colsum is not None:
+        g.workspace, g.workspace_floats = _sum_ws(colsum.device, M, N)
     g.drop = drop
     q = Fp8Gemm()
     q.alpha = _scalar(alpha, "alpha")
@@ -262,6 +268,13 @@ def _tn_workspace(device, floats):
         ws = torch.empty(max(floats, 1 << 20), dtype=F32, device=device)
         _TN_WS[key] = ws
     return ws
+
+
+def _sum_ws(device, rows, cols):
+    """(pointer, floats) of scratch for the library's fixed-order sums of a [rows, cols] matrix (include/vitssl_hip.h,
+    vitssl_sum_workspace_floats); the TN slab workspace is reused: launches on one stream are ordered."""
+    ws = _tn_workspace(device, int(L.lib().vitssl_sum_workspace_floats(rows, cols)))
+    return C.c_void_p(ws.data_ptr()), ws.numel()
 
 
 def gemm_tn(A, B, Cacc, atomic=False):
@@ -398,7 +411,7 @@ def embed_bwd(dtok, mask, dproj, dpos, dmask_token, dbias, dcls, B, tokens, tok_
 def l1_loss(pred, target, loss_sum, dpred=None, gscale=0.0):
     n = pred.numel()
     call("vitssl_l1_loss", _chk(pred, F32, "pred"), _chk(target, F32, "target", pred.shape), _chk(loss_sum, F32, "loss_sum", (1,)),
-         _opt(dpred, BF16, "dpred", pred.shape), float(gscale), n, _stream())
+         _opt(dpred, BF16, "dpred", pred.shape), float(gscale), n, *_sum_ws(pred.device, n, 1), _stream())
 
 
 def cross_entropy(logits, labels, loss_sum, dlogits=None, gscale=0.0):
@@ -409,7 +422,7 @@ def cross_entropy(logits, labels, loss_sum, dlogits=None, gscale=0.0):
 
 def colsum_bf16(x, out):
     rows, cols = x.shape
-    call("vitssl_colsum_bf16", _chk(x, BF16, "x"), _chk(out, F32, "out", (cols,)), rows, cols, _stream())
+    call("vitssl_colsum_bf16", _chk(x, BF16, "x"), _chk(out, F32, "out", (cols,)), rows, cols, *_sum_ws(x.device, rows, cols), _stream())
 
 
 def cast_bf16(src, dst):
