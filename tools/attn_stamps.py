@@ -61,7 +61,7 @@ def main():
         assert fn() == 0, lib.vitssl_last_error()
         torch.cuda.synchronize()
         assert lib.vitssl_debug_attn_stamps(None) == 0
-        if name == "fwd" and N > 128 and os.environ.get("VITSSL_ATTN_FWD_PERSIST", "2") != "0":
+        if name == "fwd" and N > 128:
             # persistent forward: per workgroup, time of wave 0 per segment summed over its items
             seg = stamps.cpu().numpy().reshape(-1, 8)[:256, :6].astype(np.float64)
             seg = seg[seg[:, 5] > 0]

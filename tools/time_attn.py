@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Median time of the attention forward / backward launches at one geometry (developer tool; compare builds or
-VITSSL_ATTN_* knobs by running it in alternation).   B H N as arguments, default 256 12 196."""
+VITSSL_ATTN_STAGGER_* settings by running it in alternation).   B H N as arguments, default 256 12 196."""
 import os
 import sys
 
@@ -41,5 +41,4 @@ def timeit(fn, rounds=15, iters=4):
 f = timeit(lambda: ops.attn_fwd(qkv, out, lse, B, N, H, 64))
 b = timeit(lambda: ops.attn_bwd(qkv, out, dout, lse, dqkv, delta, B, N, H, 64))
 fl = 4.0 * B * H * N * N * 64
-print(f"B{B} H{H} N{N}: fwd {f:7.1f} us {fl / f / 1e6:6.1f} TF/s | bwd {b:7.1f} us {2.5 * fl / b / 1e6:6.1f} TF/s   "
-      f"[{os.environ.get('VITSSL_ATTN_FWD_TRIM', '-')}]", flush=True)
+print(f"B{B} H{H} N{N}: fwd {f:7.1f} us {fl / f / 1e6:6.1f} TF/s | bwd {b:7.1f} us {2.5 * fl / b / 1e6:6.1f} TF/s", flush=True)

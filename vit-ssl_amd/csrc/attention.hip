@@ -23,8 +23,8 @@
 // Backward = ONE launch (attn_bwd_fused_kernel): wave w owns keys 32w .. 32w+31 (dK / dV accumulators),
 // sweeps the queries, drops every dS tile into an LDS exchange image from which the waves contract dQ;
 // delta = rowsum(dO*O) is computed in its prologue.  P is recomputed from the saved log-sum-exp; nothing
-// of size N^2 ever reaches HBM.  The older two-launch form (attn_bwd_dq_kernel + attn_bwd_dkv_kernel)
-// stays behind VITSSL_ATTN_BWD=split for A/B timing.
+// of size N^2 ever reaches HBM.  Longer sequences run variants of it: persistent for 129-224 tokens, with a
+// pipelined prologue for 225-256 (launch_bwd).
 #include <stdlib.h>
 #include "common.h"
 
@@ -40,37 +40,7 @@ __device__ unsigned long long* g_attn_stamps = nullptr;   // [workgroup][4] x 10
   } while (0)
 #endif
 
-// 1: the fused backward's 8-wave form runs waves 4-7 one barrier behind waves 0-3 (two barriers per query step);
-// 0 (default): one barrier per step, all waves in phase.  Measured (B = 256, H = 12, N = 196, alternating runs): staggered
-// 276 us, in phase 242 us -- the second barrier per step costs more than the MFMA / VALU overlap between SIMD partners
-// returns; kept as an A/B build.  (Moving dV / dK behind the step's barrier, which both forms share, was worth 253 -> 242 us:
-// the dS columns are published before the 16 MFMAs + 32 transposed reads instead of after them.)
-// 1: the pipelined backward keeps its K^T fragments for the dQ contraction in registers for the whole item (223 -> 218 us at B256 H12 N196; 248 VGPRs)
-#ifndef ATTN_BWD_KT_REGS
-#define ATTN_BWD_KT_REGS 1
-#endif
-#ifndef ATTN_BWD_STAGGER
-#define ATTN_BWD_STAGGER 0
-#endif
-// diagnostic builds only (tools/build_variant.sh): persistent forward without 1 = the arithmetic, 2 = the tile prefetch
-#ifndef ATTN_FWD_ABLATE
-#define ATTN_FWD_ABLATE 0
-#endif
-
 namespace {
-
-template <int V>
-struct IC2 {
-  static constexpr int value = V;
-};
-// f(IC2<0>{}), f(IC2<1>{}), ... f(IC2<N-1>{}): a loop whose index is a compile-time constant (asm immediates)
-template <int N, int I = 0, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < N) {
-    f(IC2<I>{});
-    static_for<N, I + 1>(f);
-  }
-}
 
 constexpr int DH = 64;
 constexpr int ROWB = DH * 2;  // bytes per tile row
@@ -118,7 +88,7 @@ __device__ __forceinline__ int dma_tile(char* lds, const bf16_t* g, long long st
     const int c = lane & 7;
     const int sc = c ^ (((row >> 1) & 3) << 1);
     const unsigned voff = (unsigned)((long long)row * stride * 2 + sc * 16);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, LDS_PTR(lds + i * 1024), 16, voff, 0, 0, 0);
+    dma16_to_lds(rs, lds + i * 1024, voff);
     ++n;
   }
   return n;
@@ -236,7 +206,8 @@ __device__ __forceinline__ void softmax_tile(f32x4 (&s)[NKT], float& m_out, floa
   sum_out = sum;
 }
 
-// grid = B*H, NW waves per workgroup: 4 (two workgroups per CU) for long sequences, 2 when
+// Sequences of up to 128 tokens (longer ones run the persistent forward below).
+// grid = B*H, NW waves per workgroup: 4 (two workgroups per CU), 2 when
 // NS <= 2 (a 37-token DINO local crop has two query pairs: two of four waves would idle and
 // more, smaller workgroups share a CU).  NS = number of 32-key steps (Np = 32*NS >= N).
 // Each wave processes PAIRS of 16-query tiles so that every K / V fragment read from LDS
@@ -385,16 +356,15 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd_kernel(const bf16_t* __re
 // (7.7 us per item against 5.8 us of compute).  Here nqp <= 8 query pairs are one pass of the 8 waves and no wave ever
 // waits for a tile except in the first item.
 //
-// The transposed V reads are inline asm: for the ds_read_tr builtin (no memory operand) hipcc assumes a dependency on
-// every LDS-DMA in flight and would drain vmcnt(0) -- the next item's prefetch -- in front of each read (same finding as
-// csrc/gemm_tn.hip).  The item loop is unrolled by two so that every tile address is a compile-time offset.
+// The transposed V reads are inline asm (ds_read_tr16): the ds_read_tr builtin would drain vmcnt(0) -- the next item's
+// prefetch -- in front of each read.  The item loop is unrolled by two so that every tile address is a compile-time offset.
 // the eight transposed reads of contraction step ST (rows 32 ST .. + 31) of a V tile: four column slices x (rows, rows + 16)
 template <int ST>
 __device__ __forceinline__ void tr_read_v4(s16x4 (&lo)[4], s16x4 (&hi)[4], const unsigned (&va)[4]) {
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt) {
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(lo[dt]) : "v"(va[dt]), "n"(4096 * ST));
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(hi[dt]) : "v"(va[dt]), "n"(4096 * ST + 2048));
+    ds_read_tr16<4096 * ST>(lo[dt], va[dt]);
+    ds_read_tr16<4096 * ST + 2048>(hi[dt], va[dt]);
   }
 }
 
@@ -502,11 +472,11 @@ __global__ __launch_bounds__(1024 / QT, QT == 1 ? 4 : 2) void attn_fwd_pers_kern
       qf[t][0] = qn[t][0];
       qf[t][1] = qn[t][1];
     }
-    if (has_next && ATTN_FWD_ABLATE != 2) {
+    if (has_next) {
       issue_tiles(next, Kn, Kn + TILE);
       load_q(next, qn);
     }
-    if (active && ATTN_FWD_ABLATE != 1) {
+    if (active) {
       f32x4 sc[QT][NKT];
 #pragma unroll
       for (int kt = 0; kt < NKT; ++kt) {
@@ -618,8 +588,8 @@ __global__ __launch_bounds__(1024 / QT, QT == 1 ? 4 : 2) void attn_fwd_pers_kern
     return has_next;
   };
   for (;;) {
-    if (!one_item(IC2<0>{})) break;
-    if (!one_item(IC2<1>{})) break;
+    if (!one_item(IC<0>{})) break;
+    if (!one_item(IC<1>{})) break;
   }
 #ifdef VITSSL_ATTN_STAMPS
   if (g_attn_stamps && threadIdx.x == 0)
@@ -637,8 +607,9 @@ __global__ __launch_bounds__(1024 / QT, QT == 1 ? 4 : 2) void attn_fwd_pers_kern
 // contract over ALL keys from that image -- S and dP are computed once instead of twice,
 // Q / K / V / dO are read from HBM once, there are no atomics and no N^2 traffic.
 // delta = rowsum(dO * O) is computed in the prologue.
-// NW = waves per workgroup: 8 for long sequences; 4 when NS <= 4 (every key owner still gets
-// a wave, each wave then takes two dQ tiles per step) so that two workgroups share a CU --
+// Sequences of up to 128 tokens (longer ones run the persistent and pipelined forms below).
+// NW = waves per workgroup: 4, or 2 when NS <= 2 (every key owner gets a wave, each wave then
+// takes 8 / NW dQ tiles per step), so that two workgroups share a CU --
 // DINO's 96x96 local crops are 37 tokens, and an 8-wave workgroup with six idle waves per
 // (batch, head) was launch-bound (5.8 us per workgroup, as long as a 197-token one).
 // (launch bound: two waves per SIMD.  Without it hipcc spread the 2- and 4-wave forms over 258-284 registers (VGPRs + AGPRs), which
@@ -781,16 +752,9 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_bwd_fused_kernel(const bf16_t
   // qs and their exp / dS arithmetic, so the matrix pipe has work while the VALU runs the softmax recompute.
   //
   // A step is {scores + dQ(qs-1) + exp / dS / exchange writes} X {dV / dK}: the barrier X publishes the dS columns BEFORE the
-  // dV / dK products (round 3; they need nothing from other waves).
-  // ATTN_BWD_STAGGER = 1 (experiment, slower: see the macro): a second barrier Y per step, and waves 4-7 (the second wave of
-  // every SIMD) run ONE barrier behind waves 0-3, so that the VALU-heavy first half of one wave runs beside the MFMA /
-  // LDS-heavy second half of its SIMD partner.
-  // Events e0, e1, ...: waves 0-3 pass X(qs) = e(2qs), Y(qs) = e(2qs+1); waves 4-7 pass an extra barrier e0 first, then
-  // X(qs) = e(2qs+1), Y(qs) = e(2qs+2).  dS(qs) of every wave is published by e(2qs+1); dQ(qs-1) is read after e(2qs-1)
-  // (waves 0-3) / e(2qs) (waves 4-7): every writer is past its X(qs-1).  Buffer (qs+1)&1 is rewritten after e(2qs+1)
-  // / e(2qs+2): its last readers (dQ(qs-1)) finished before e(2qs) / e(2qs+1).  Waves 0-3 add one barrier after the loop.
-  const bool lag = ATTN_BWD_STAGGER && NW == 8 && wave >= 4;     // wave-uniform
-  if (lag) __syncthreads();
+  // dV / dK products (round 3; they need nothing from other waves): 253 -> 242 us at B = 256, H = 12, N = 196.
+  // (A second barrier per step with waves 4-7 one barrier behind waves 0-3, so that the VALU-heavy first half of one wave runs
+  // beside the MFMA / LDS-heavy second half of its SIMD partner, was measured slower, 276 against 242 us, and is gone.)
 #pragma unroll 1
   for (int qs = 0; qs < NS; ++qs) {
     char* sx = Sx + (qs & 1) * 32 * SROW;
@@ -845,9 +809,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_bwd_fused_kernel(const bf16_t
         }
       }
     }
-    if (ATTN_BWD_STAGGER && NW == 8) __syncthreads();   // Y
   }
-  if (ATTN_BWD_STAGGER && NW == 8 && !lag) __syncthreads();     // waves 0-3: the event waves 4-7 pass as their last Y
   dq_tile(Sx + ((NS - 1) & 1) * 32 * SROW, NS - 1);
   ATTN_STAMP(2);
   if (has_keys) {
@@ -896,13 +858,13 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_bwd_fused_kernel(const bf16_t
 }
 
 
-// ------------------------------------------------------------------ backward, fused, pipelined prologue (N > 128)
+// ------------------------------------------------------------------ backward, fused, pipelined prologue (224 < N <= 256)
 // attn_bwd_fused_kernel with the operand loads spread over the query sweep (round 3).  Stamps of the fused kernel (B = 256,
 // H = 12, N = 196): prologue 4.9 us of a 19.6 us workgroup -- all four tiles (Q, dO, K, O: 112 KB) land before the first MFMA,
 // although step qs of the sweep touches only rows 32 qs .. 32 qs + 31 of Q / dO (and, through delta, of O).  Here the
 // prologue waits for K, V and the first TWO 32-row slices; slice qs + 2 is requested by LDS-DMA at the top of step qs and is
 // covered by the wait + barrier that ends the step; delta = rowsum(dO * O) of slice qs + 1 is computed during step qs by the
-// last wave (which owns no keys at N <= 224) from a three-slot ring of O slices.
+// last wave from a three-slot ring of O slices.
 // What that needs: nothing in the sweep may make hipcc drain the DMA queue -- the transposed reads are inline asm (for the
 // ds_read_tr builtin hipcc waits vmcnt(0) while an LDS-DMA is in flight), the step's barrier is a raw s_barrier behind a
 // BUILTIN s_waitcnt (vmcnt(0) of this wave's own, by then one step old, requests + lgkmcnt(0)), never __syncthreads().
@@ -910,11 +872,7 @@ __device__ __forceinline__ void dma_rows8(__amdgpu_buffer_rsrc_t rs, char* lds_r
   const int rl = lane >> 3, c = lane & 7;
   const int sc = c ^ ((((lrow0 + rl) >> 1) & 3) << 1);      // the tile's swizzle, by the row's position in its tile / ring slot
   const unsigned voff = (unsigned)((long long)(grow0 + rl) * stride * 2 + sc * 16);
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, LDS_PTR(lds_rows), 16, voff, 0, 0, 0);
-}
-template <int IMM>
-__device__ __forceinline__ void ds_tr16(s16x4& dst, unsigned addr) {
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(IMM));
+  dma16_to_lds(rs, lds_rows, voff);
 }
 __device__ __forceinline__ bf16x8 join_tr(const s16x4& lo, const s16x4& hi) {
   typedef __attribute__((ext_vector_type(8))) short s16x8;
@@ -1048,26 +1006,17 @@ __global__ __launch_bounds__(512) void attn_bwd_pipe_kernel(const bf16_t* __rest
                          (unsigned)(tile_off(4 * g + tq, 2 * dt_w + (tpp >> 1)) - tile_off(4 * g + tq, (tpp >> 1)));
 
   // dQ^T[d][q] = sum_key K[key][d] dS[q][key] for this wave's tile of step qs, from exchange image sx
-#if ATTN_BWD_KT_REGS
   // this wave's K^T fragments (16 head dimensions x all keys) are the same in every step: read once, 4 NS registers
+  // (re-reading them in every step instead: 223 against 218 us at B = 256, H = 12, N = 196)
   s16x4 klo[NS], khi[NS];
   auto load_kt = [&]() {
     static_for<NS>([&](auto st_c) {
       constexpr int st = decltype(st_c)::value;
-      ds_tr16<4096 * st>(klo[st], kaddr);
-      ds_tr16<4096 * st + 2048>(khi[st], kaddr);
+      ds_read_tr16<4096 * st>(klo[st], kaddr);
+      ds_read_tr16<4096 * st + 2048>(khi[st], kaddr);
     });
   };
-#endif
   auto dq_tile = [&](const char* sx, int qs) {
-#if !ATTN_BWD_KT_REGS
-    s16x4 klo[NS], khi[NS];
-    static_for<NS>([&](auto st_c) {
-      constexpr int st = decltype(st_c)::value;
-      ds_tr16<4096 * st>(klo[st], kaddr);
-      ds_tr16<4096 * st + 2048>(khi[st], kaddr);
-    });
-#endif
     const char* rowp = sx + (16 * qt_w + li) * SROW + 8 * g;
     u32x2 dlo[NS], dhi[NS];
 #pragma unroll
@@ -1096,9 +1045,7 @@ __global__ __launch_bounds__(512) void attn_bwd_pipe_kernel(const bf16_t* __rest
     }
   };
 
-#if ATTN_BWD_KT_REGS
   load_kt();                                       // (the K tile landed with the prologue's wait; the step's lgkmcnt(0) covers the reads)
-#endif
 #pragma unroll 1
   for (int qs = 0; qs < NS; ++qs) {
     char* sx = Sx + (qs & 1) * 32 * SROW;
@@ -1147,24 +1094,20 @@ __global__ __launch_bounds__(512) void attn_bwd_pipe_kernel(const bf16_t* __rest
     if (qs == 0 || dq_stores == 0) __builtin_amdgcn_s_waitcnt(0x0070);      // vmcnt(0) lgkmcnt(0)
     else if (dq_stores == 1) __builtin_amdgcn_s_waitcnt(0x0071);           // vmcnt(1)
     else __builtin_amdgcn_s_waitcnt(0x0072);                               // vmcnt(2)
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("" ::: "memory");
+    raw_barrier();
     if (has_keys) {
       // dV^T += dO^T P, dK^T += Q^T dS: the transposed fragments of the step's 32 rows serve both key tiles
       s16x4 qlo[4], qhi[4], dlo[4], dhi[4];
       const unsigned soff = (unsigned)qs * 4096u;
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) {
-        ds_tr16<TILE>(dlo[dt], vrel[dt] + soff);
-        ds_tr16<TILE + 2048>(dhi[dt], vrel[dt] + soff);
+        ds_read_tr16<TILE>(dlo[dt], vrel[dt] + soff);
+        ds_read_tr16<TILE + 2048>(dhi[dt], vrel[dt] + soff);
       }
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) {
-        ds_tr16<0>(qlo[dt], vrel[dt] + soff);
-        ds_tr16<2048>(qhi[dt], vrel[dt] + soff);
+        ds_read_tr16<0>(qlo[dt], vrel[dt] + soff);
+        ds_read_tr16<2048>(qhi[dt], vrel[dt] + soff);
       }
       bf16x8 pf[2], sf[2];
 #pragma unroll
@@ -1253,7 +1196,7 @@ __global__ __launch_bounds__(512) void attn_bwd_pipe_kernel(const bf16_t* __rest
 // attn_bwd_pipe_kernel inside an item loop (one workgroup per CU, items b, b + G, ...), with the next item's operands requested
 // while the current one is swept, so that the 3.2 us prologue of the pipelined kernel (K tile, V fragments, two slices, lse: nothing
 // else runs on the CU meanwhile, 12 times per CU at B = 256, H = 12) shrinks to fragment reads from LDS.  What moves where:
-//   * K': the K tile is dead once its fragments sit in registers (kf, and the K^T fragments of the dQ products: ATTN_BWD_KT_REGS), so
+//   * K': the K tile is dead once its fragments sit in registers (kf, and the K^T fragments of the dQ products), so
 //     K' lands in it during the sweep; V' lands in a tile of its own (the pipelined kernel reads V with ordinary loads: +28 KiB of LDS,
 //     which is why N > 224 stays on that kernel).  Both are requested right BEHIND the dQ stores of step 1, NS instructions per wave,
 //     and that step's wait leaves them in flight next to the stores (counted vmcnt); step 2's wait covers them.
@@ -1420,18 +1363,14 @@ __global__ __launch_bounds__(512) void attn_bwd_pers_kernel(const bf16_t* __rest
     s16x4 klo[NS], khi[NS];
     static_for<NS>([&](auto st_c) {
       constexpr int st = decltype(st_c)::value;
-      ds_tr16<4096 * st>(klo[st], kaddr);
-      ds_tr16<4096 * st + 2048>(khi[st], kaddr);
+      ds_read_tr16<4096 * st>(klo[st], kaddr);
+      ds_read_tr16<4096 * st + 2048>(khi[st], kaddr);
     });
     if (delta_wave) delta_slice(0);
     // lgkmcnt(0): the K / V tiles are free behind the barrier.  A raw s_barrier: __syncthreads() would also wait for the previous
     // item's last stores (vmcnt(0)), which step 0's own wait absorbs half a step later.
     __builtin_amdgcn_s_waitcnt(0xC07F);
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("" ::: "memory");
+    raw_barrier();
 
     auto dq_tile = [&](const char* sx, int qs) {
       const char* rowp = sx + (16 * qt_w + li) * SROW + 8 * g;
@@ -1547,24 +1486,20 @@ __global__ __launch_bounds__(512) void attn_bwd_pers_kernel(const bf16_t* __rest
         case 9: __builtin_amdgcn_s_waitcnt(0x0079); break;
         default: __builtin_amdgcn_s_waitcnt(0x0070); break;
       }
-      asm volatile("" ::: "memory");
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_sched_barrier(0);
-      asm volatile("" ::: "memory");
+      raw_barrier();
       if (has_keys) {
         // dV^T += dO^T P, dK^T += Q^T dS: the transposed fragments of the step's 32 rows serve both key tiles
         s16x4 qlo[4], qhi[4], dlo[4], dhi[4];
         const unsigned soff = (unsigned)qs * 4096u;
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) {
-          ds_tr16<TILE>(dlo[dt], vrel[dt] + soff);
-          ds_tr16<TILE + 2048>(dhi[dt], vrel[dt] + soff);
+          ds_read_tr16<TILE>(dlo[dt], vrel[dt] + soff);
+          ds_read_tr16<TILE + 2048>(dhi[dt], vrel[dt] + soff);
         }
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) {
-          ds_tr16<0>(qlo[dt], vrel[dt] + soff);
-          ds_tr16<2048>(qhi[dt], vrel[dt] + soff);
+          ds_read_tr16<0>(qlo[dt], vrel[dt] + soff);
+          ds_read_tr16<2048>(qhi[dt], vrel[dt] + soff);
         }
         bf16x8 pf[2], sf[2];
 #pragma unroll
@@ -1663,112 +1598,80 @@ int attn_stagger_ticks(int which) {
   return which == 0 ? fwd.get("VITSSL_ATTN_STAGGER_FWD", 0) : bwd.get("VITSSL_ATTN_STAGGER_BWD", 1400);
 }
 
-template <typename K>
-int ensure_lds(K kernel, int bytes, VsOnce* done, const char* who) {
-  if (done->load(std::memory_order_relaxed) || bytes <= 48 * 1024) return VITSSL_OK;
-  hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (e != hipSuccess) {
-    vitssl_set_error("%s: cannot raise dynamic LDS: %s", who, hipGetErrorString(e));
-    return VITSSL_ERR_LAUNCH;
-  }
-  done->store(true, std::memory_order_relaxed);
-  return VITSSL_OK;
-}
+// Every attention kernel that needs more than the default 48 KiB of dynamic LDS has its limit raised to this, once
+constexpr int ATTN_LDS_LIMIT = 160 * 1024;
 
-// 1 (default): sequences of more than 128 tokens run the persistent forward (8 waves x two query tiles, next item's K / V prefetched);
-// 0: the two-workgroups-per-CU kernel that shorter sequences always use (VITSSL_ATTN_FWD_PERSIST; exercised by tests/test_gpu_knobs.py)
-bool attn_fwd_persist() {
-  static VsEnvInt knob;
-  return knob.get("VITSSL_ATTN_FWD_PERSIST", 1) != 0;
-}
-
+// Sequences of up to 128 tokens: two workgroups per CU, one per (batch, head).  Longer ones: the persistent forward (8 waves x two
+// query tiles, the next item's K / V prefetched).
 template <int NS>
 int launch_fwd(const bf16_t* qkv, bf16_t* out, float* lse, float* probs, int B, int N, int H, hipStream_t s,
                unsigned char* out8 = nullptr) {
   if constexpr (NS >= 5) {
-    if (attn_fwd_persist()) {
-      static VsOnce done_p{false};
-      const int lds_p = 4 * NS * 32 * ROWB + 8 * 2048;   // two (K, V) tile pairs + a 2 KiB output window per wave
-      const int nitems = B * H;
-      const int cus = attn_cu_count();
-      const int grid = nitems < cus ? nitems : cus;
-      if (int rc = ensure_lds(attn_fwd_pers_kernel<NS, 2>, lds_p, &done_p, "attn_fwd_pers")) return rc;
-      g_last_attn_fwd_grid.store(grid, std::memory_order_relaxed);
-      hipLaunchKernelGGL((attn_fwd_pers_kernel<NS, 2>), dim3(grid), dim3(512), lds_p, s, qkv, out, lse, probs, N, H, nitems, out8);
-      VS_CHECK_LAUNCH("attn_fwd_pers");
-      return VITSSL_OK;
-    }
+    static VsOnce done_p{false};
+    const int lds_p = 4 * NS * 32 * ROWB + 8 * 2048;   // two (K, V) tile pairs + a 2 KiB output window per wave
+    const int nitems = B * H;
+    const int cus = attn_cu_count();
+    const int grid = nitems < cus ? nitems : cus;
+    if (int rc = ensure_lds(attn_fwd_pers_kernel<NS, 2>, ATTN_LDS_LIMIT, done_p, "attn_fwd_pers")) return rc;
+    g_last_attn_fwd_grid.store(grid, std::memory_order_relaxed);
+    hipLaunchKernelGGL((attn_fwd_pers_kernel<NS, 2>), dim3(grid), dim3(512), lds_p, s, qkv, out, lse, probs, N, H, nitems, out8);
+    VS_CHECK_LAUNCH("attn_fwd_pers");
+  } else {
+    constexpr int lds = 2 * NS * 32 * ROWB;
+    static_assert(lds <= 48 * 1024, "within the default dynamic-LDS limit");
+    constexpr int NW = NS <= 2 ? 2 : 4;
+    const int per_cu = lds > 80 * 1024 ? 1 : (lds > 53 * 1024 ? 2 : 3);
+    const int cus = attn_cu_count();
+    g_last_attn_fwd_grid.store(B * H, std::memory_order_relaxed);
+    hipLaunchKernelGGL((attn_fwd_kernel<NS, NW>), dim3(B * H), dim3(64 * NW), lds, s, qkv, out, lse, probs, N, H,
+                       cus * per_cu, B * H > 2 * cus * per_cu ? attn_stagger_ticks(0) : 0, out8);
+    VS_CHECK_LAUNCH("attn_fwd");
   }
-  static VsOnce done{false};
-  const int lds = 2 * NS * 32 * ROWB;
-  constexpr int NW = NS <= 2 ? 2 : 4;
-  if (int rc = ensure_lds(attn_fwd_kernel<NS, NW>, lds, &done, "attn_fwd")) return rc;
-  const int per_cu = lds > 80 * 1024 ? 1 : (lds > 53 * 1024 ? 2 : 3);
-  const int cus = attn_cu_count();
-  g_last_attn_fwd_grid.store(B * H, std::memory_order_relaxed);
-  hipLaunchKernelGGL((attn_fwd_kernel<NS, NW>), dim3(B * H), dim3(64 * NW), lds, s, qkv, out, lse, probs, N, H,
-                     cus * per_cu, B * H > 2 * cus * per_cu ? attn_stagger_ticks(0) : 0, out8);
-  VS_CHECK_LAUNCH("attn_fwd");
   return VITSSL_OK;
 }
 
-// 1 (default): sequences of more than 128 tokens run the fused backward with the pipelined prologue; 0: attn_bwd_fused_kernel, which
-// shorter sequences always use (VITSSL_ATTN_BWD_PIPE; exercised by tests/test_gpu_knobs.py)
-bool attn_bwd_pipe() {
-  static VsEnvInt knob;
-  return knob.get("VITSSL_ATTN_BWD_PIPE", 1) != 0;
-}
-
-// 1 (default): sequences of 129-224 tokens run the persistent backward (next item's operands prefetched); 0: one workgroup per
-// (batch, head) with the pipelined prologue (VITSSL_ATTN_BWD_PERSIST; exercised by tests/test_gpu_knobs.py)
-bool attn_bwd_persist() {
-  static VsEnvInt knob;
-  return knob.get("VITSSL_ATTN_BWD_PERSIST", 1) != 0;
-}
-
+// Sequences of up to 128 tokens: the fused backward, one workgroup per (batch, head).  129-224 tokens: the persistent backward (the
+// next item's operands prefetched).  225-256 tokens: the fused backward with the pipelined prologue.
 template <int NS>
 int launch_bwd(const bf16_t* qkv, const bf16_t* out, const bf16_t* dout, const float* lse, bf16_t* dqkv, int B,
                int N, int H, hipStream_t s, unsigned char* dq8 = nullptr, const float* qscale = nullptr, float* qamax = nullptr) {
   const int cus = attn_cu_count();
   if constexpr (NS >= 5 && NS <= 7) {
-    if (attn_bwd_pipe() && attn_bwd_persist()) {
-      static VsOnce done_ps{false}, done_ps8{false};
-      constexpr int LDS_PS = 4 * NS * 32 * ROWB + 2 * 32 * (NS * 64 + 16) + 3 * NS * 32 * 4 + 3 * 32 * ROWB;
-      static_assert(LDS_PS <= 160 * 1024, "the persistent backward needs four operand tiles in LDS");
-      const int nitems = B * H;
-      const int grid = nitems < cus ? nitems : cus;
-      if (dq8) {
-        if (int rc = ensure_lds(attn_bwd_pers_kernel<NS, true>, LDS_PS, &done_ps8, "attn_bwd_pers")) return rc;
-        hipLaunchKernelGGL((attn_bwd_pers_kernel<NS, true>), dim3(grid), dim3(512), LDS_PS, s, qkv, out, dout, lse, dqkv, N, H, nitems, dq8,
-                           qscale, qamax);
-      } else {
-        if (int rc = ensure_lds(attn_bwd_pers_kernel<NS, false>, LDS_PS, &done_ps, "attn_bwd_pers")) return rc;
-        hipLaunchKernelGGL((attn_bwd_pers_kernel<NS, false>), dim3(grid), dim3(512), LDS_PS, s, qkv, out, dout, lse, dqkv, N, H, nitems, dq8,
-                           qscale, qamax);
-      }
-      VS_CHECK_LAUNCH("attn_bwd_pers");
-      return VITSSL_OK;
+    static VsOnce done_ps{false}, done_ps8{false};
+    constexpr int LDS_PS = 4 * NS * 32 * ROWB + 2 * 32 * (NS * 64 + 16) + 3 * NS * 32 * 4 + 3 * 32 * ROWB;
+    static_assert(LDS_PS <= 160 * 1024, "the persistent backward needs four operand tiles in LDS");
+    const int nitems = B * H;
+    const int grid = nitems < cus ? nitems : cus;
+    if (dq8) {
+      if (int rc = ensure_lds(attn_bwd_pers_kernel<NS, true>, ATTN_LDS_LIMIT, done_ps8, "attn_bwd_pers")) return rc;
+      hipLaunchKernelGGL((attn_bwd_pers_kernel<NS, true>), dim3(grid), dim3(512), LDS_PS, s, qkv, out, dout, lse, dqkv, N, H, nitems, dq8,
+                         qscale, qamax);
+    } else {
+      if (int rc = ensure_lds(attn_bwd_pers_kernel<NS, false>, ATTN_LDS_LIMIT, done_ps, "attn_bwd_pers")) return rc;
+      hipLaunchKernelGGL((attn_bwd_pers_kernel<NS, false>), dim3(grid), dim3(512), LDS_PS, s, qkv, out, dout, lse, dqkv, N, H, nitems, dq8,
+                         qscale, qamax);
     }
-  }
-  if constexpr (NS >= 5) {
-    if (attn_bwd_pipe()) {
-      static VsOnce done_p{false};
-      const int lds_p = 3 * NS * 32 * ROWB + 2 * 32 * (NS * 64 + 16) + 2 * NS * 32 * 4 + 3 * 32 * ROWB;
-      if (int rc = ensure_lds(attn_bwd_pipe_kernel<NS>, lds_p, &done_p, "attn_bwd_pipe")) return rc;
-      hipLaunchKernelGGL((attn_bwd_pipe_kernel<NS>), dim3(B * H), dim3(512), lds_p, s, qkv, out, dout, lse, dqkv, N, H,
-                         cus, B * H > 2 * cus ? attn_stagger_ticks(1) : 0, dq8, qscale, qamax);
-      VS_CHECK_LAUNCH("attn_bwd_pipe");
-      return VITSSL_OK;
+    VS_CHECK_LAUNCH("attn_bwd_pers");
+  } else if constexpr (NS == 8) {
+    static VsOnce done_p{false};
+    const int lds_p = 3 * NS * 32 * ROWB + 2 * 32 * (NS * 64 + 16) + 2 * NS * 32 * 4 + 3 * 32 * ROWB;
+    if (int rc = ensure_lds(attn_bwd_pipe_kernel<NS>, ATTN_LDS_LIMIT, done_p, "attn_bwd_pipe")) return rc;
+    hipLaunchKernelGGL((attn_bwd_pipe_kernel<NS>), dim3(B * H), dim3(512), lds_p, s, qkv, out, dout, lse, dqkv, N, H,
+                       cus, B * H > 2 * cus ? attn_stagger_ticks(1) : 0, dq8, qscale, qamax);
+    VS_CHECK_LAUNCH("attn_bwd_pipe");
+  } else {
+    static_assert(NS <= 4, "the fused backward serves up to 128 tokens");
+    constexpr int NW = NS <= 2 ? 2 : 4;
+    constexpr int lds_f = 3 * NS * 32 * ROWB + 2 * 32 * (NS * 64 + 16) + 2 * NS * 32 * 4;
+    if constexpr (lds_f > 48 * 1024) {
+      static VsOnce done_f{false};
+      if (int rc = ensure_lds(attn_bwd_fused_kernel<NS, NW>, ATTN_LDS_LIMIT, done_f, "attn_bwd_fused")) return rc;
     }
+    const int per_cu = lds_f > 80 * 1024 ? 1 : 2;
+    hipLaunchKernelGGL((attn_bwd_fused_kernel<NS, NW>), dim3(B * H), dim3(64 * NW), lds_f, s, qkv, out, dout, lse, dqkv, N, H,
+                       cus * per_cu, B * H > 2 * cus * per_cu ? attn_stagger_ticks(1) : 0, dq8, qscale, qamax);
+    VS_CHECK_LAUNCH("attn_bwd_fused");
   }
-  static VsOnce done_f{false};
-  constexpr int NW = NS <= 2 ? 2 : (NS <= 4 ? 4 : 8);
-  const int lds_f = 3 * NS * 32 * ROWB + 2 * 32 * (NS * 64 + 16) + 2 * NS * 32 * 4;
-  if (int rc = ensure_lds(attn_bwd_fused_kernel<NS, NW>, lds_f, &done_f, "attn_bwd_fused")) return rc;
-  const int per_cu = lds_f > 80 * 1024 ? 1 : 2;
-  hipLaunchKernelGGL((attn_bwd_fused_kernel<NS, NW>), dim3(B * H), dim3(64 * NW), lds_f, s, qkv, out, dout, lse, dqkv, N, H,
-                     cus * per_cu, B * H > 2 * cus * per_cu ? attn_stagger_ticks(1) : 0, dq8, qscale, qamax);
-  VS_CHECK_LAUNCH("attn_bwd_fused");
   return VITSSL_OK;
 }
 

@@ -7,6 +7,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <atomic>
+#include <type_traits>
 #include "../../include/vitssl_hip.h"
 
 // ---------------------------------------------------------------- error plumbing
@@ -87,12 +88,83 @@ typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) short s16x4;
+typedef __attribute__((ext_vector_type(2))) int i32x2;
 typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 typedef __attribute__((ext_vector_type(8))) int i32x8;
 typedef unsigned short bf16_t;  // raw storage
 
 #define LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
+
+// ---------------------------------------------------------------- gfx950 primitives of the GEMM and attention kernels
+// (target builtins with immediate operands are kept out of the kernels' lambdas: on the host pass a lambda body is checked
+// eagerly and the kernel would silently lose its stub.  The wrappers below are plain functions for that reason.)
+
+// compile-time index: f(IC<0>{}), f(IC<1>{}), ... f(IC<N-1>{}) is a loop whose index can feed asm immediates
+template <int V>
+using IC = std::integral_constant<int, V>;
+template <int N, int I = 0, typename F>
+__device__ __forceinline__ void static_for(F&& f) {
+  if constexpr (I < N) {
+    f(IC<I>{});
+    static_for<N, I + 1>(f);
+  }
+}
+
+// s_waitcnt vmcnt(N): at most N of this wave's vector-memory operations (loads, stores, LDS-DMA) still in flight
+template <int N>
+__device__ __forceinline__ void wait_vmcnt() {
+  static_assert(N >= 0 && N <= 63, "vmcnt is a 6-bit counter");
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+
+// LDS-DMA of 16 bytes per lane (buffer_load_dwordx4 ... lds): the wave's 64 chunks land as 1 KiB at lds_wave_base
+__device__ __forceinline__ void dma16_to_lds(__amdgpu_buffer_rsrc_t rsrc, char* lds_wave_base, unsigned voffset) {
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, LDS_PTR(lds_wave_base), 16, voffset, 0, 0, 0);
+}
+
+// Transposed LDS reads with an immediate offset.  Inline asm on purpose: for the ds_read_tr builtins (no memory operand) hipcc
+// assumes a dependency on every LDS-DMA in flight and drains vmcnt(0) in front of each read.
+template <int IMM>
+__device__ __forceinline__ void ds_read_tr16(s16x4& dst, unsigned addr) {
+  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(IMM));
+}
+template <int IMM>
+__device__ __forceinline__ void ds_read_tr8(i32x2& dst, unsigned addr) {
+  asm volatile("ds_read_b64_tr_b8 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(IMM));
+}
+
+// Raw s_barrier between two parts of a hand-scheduled loop.  It carries no fence: the empty asm statements keep the optimiser
+// from moving LDS accesses across it, the sched_barriers keep the machine scheduler from moving MFMAs.
+__device__ __forceinline__ void raw_barrier() {
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_sched_barrier(0);
+  asm volatile("" ::: "memory");
+}
+
+// XCD-contiguous remap of workgroup index bid < n: workgroups are dealt round-robin over the 8 XCDs (bid, bid + 8, ... share one
+// XCD's L2); this bijection of [0, n) hands every XCD one contiguous run of indices, so neighbouring work shares an L2.
+// (bid is blockIdx.x itself or an int copy of it; the type only picks a logical or an arithmetic shift.)
+template <typename Index>
+__device__ __forceinline__ int xcd_remap(Index bid, int n) {
+  const int xcd = bid & 7, q = n >> 3, r = n & 7;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+}
+
+// Raise a kernel's limit of dynamic LDS to `bytes`, once per process (`done`).  Launches above the 48 KiB default need it.
+template <typename K>
+int ensure_lds(K kernel, int bytes, VsOnce& done, const char* who) {
+  if (done.load(std::memory_order_relaxed)) return VITSSL_OK;
+  hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e != hipSuccess) {
+    vitssl_set_error("%s: cannot raise dynamic LDS to %d: %s", who, bytes, hipGetErrorString(e));
+    return VITSSL_ERR_LAUNCH;
+  }
+  done.store(true, std::memory_order_relaxed);
+  return VITSSL_OK;
+}
 
 // ---------------------------------------------------------------- bf16 <-> f32
 __device__ __forceinline__ float bf2f(bf16_t h) { return __uint_as_float(((unsigned)h) << 16); }

@@ -31,95 +31,10 @@
 // and quarter-step DMA schedules, start-up stagger, L2 warm-up loads, global_load_lds,
 // peeling the under-filled last round into a SMALL-tile launch.
 #include <stdlib.h>
-#include <type_traits>
 #include <atomic>
 #include "common.h"
 
-// cache policy of the epilogue stores (buffer aux bits: 1 = sc0, 2 = nt, 16 = sc1); developer experiments only
-#ifndef NT_STORE_AUX
-#define NT_STORE_AUX 0
-#endif
-// residual-stream stores (fp32, read next by a different kernel) are issued non-temporal: interleaved A/B
-// on MI355X, out-projection shape M = 50176, N = K = 768: 116 -> 97 us; neutral at K = 3072
-#ifndef NT_RESID_AUX
-#define NT_RESID_AUX 2
-#endif
-// bf16 images (activations / gradients consumed by the NEXT kernel): 16 = sc1, write-through without keeping
-// the line in this XCD's L2, so the 30-60 MB of output per tile round do not evict the weight panels the
-// following rounds re-use (FETCH_SIZE of the FC1 GELU launch 362 -> 297 MB at group 4, 223 MB at group 6)
-#ifndef NT_BF16_AUX
-#define NT_BF16_AUX 0
-#endif
-// g' = keep*scale*gelu'(u), the second image of the FC1 epilogue, is read again only in backward: its stores
-// are non-temporal (2) so that `a`, which FC2 reads next, keeps its lines (in-step A/B: -0.25 ms per ViT-B step; sc1 = 16: slower)
-#ifndef NT_GPRIME_AUX
-#define NT_GPRIME_AUX 2
-#endif
-// 1 (default): the GELU epilogue of the ping-pong kernel reads gelu / gelu' from an LDS table; 0: arithmetic only (A/B builds)
-#ifndef NT_GELU_LUT
-#define NT_GELU_LUT 1
-#endif
-// rows (16-row MFMA tiles) whose residual / g' operands are requested together in the RESID / DGELU epilogues
-#ifndef NT_RG_RESID
-#define NT_RG_RESID 1
-#endif
-#ifndef NT_RG_DGELU
-#define NT_RG_DGELU 2
-#endif
-// ... with the operand prefetch (two groups alive at once)
-#ifndef NT_RG_RESID_PF
-#define NT_RG_RESID_PF 1
-#endif
-#ifndef NT_RG_DGELU_PF
-#define NT_RG_DGELU_PF 2
-#endif
-// 1: the RESID / DGELU epilogues of the ping-pong kernel request the operand lines of the next row group before they store the
-// current one (see nt_epilogue)
-#ifndef NT_EPI_PREFETCH
-#define NT_EPI_PREFETCH 1
-#endif
-// 1 (default): the ping-pong kernel's epilogue hands every 16-row tile of an output image through a private 2 KiB LDS window
-// of the wave, so that a store instruction's 64 lanes cover 8 rows x 128 CONTIGUOUS bytes with adjacent lanes on adjacent
-// addresses.  tools/probes/store_patterns.hip: a CU stores 55 GB/s in the accumulator layout (adjacent lanes = adjacent ROWS,
-// 16 bytes each: every lane is its own request) and 183-190 GB/s once four or more adjacent lanes are contiguous.
-#ifndef NT_LDS_T
-#define NT_LDS_T 1
-#endif
-// start-up stagger window of the ping-pong kernel in tile times (VITSSL_NT_STAGGER overrides)
-// 1: the K-tile position of the ping-pong loop's operand DMA lives in the buffer descriptor instead of the lanes' offsets
-#ifndef NT_DESC_WINDOW
-#define NT_DESC_WINDOW 1
-#endif
-// 1: s_setprio 1 around the MFMA clusters of the ping-pong loop.  Round 2 measured it neutral; with the leaner loops of round 3 it
-// costs 0.5-1.5 % on 15 of 16 shape x epilogue pairs (interleaved A/B, profiles/r03_tls_ab.txt): 8 more scalar instructions per
-// K-tile in loops whose LOAD parts are bound by issue slots (see gemm_tn.hip).  Default off.
-#ifndef NT_SETPRIO
-#define NT_SETPRIO 0
-#endif
-// epilogues whose launches stagger (bit = VITSSL_EPI_* value).  Spreading the workgroups in time costs L2 sharing (the workgroups
-// of a raster group are no longer at the same k): FETCH_SIZE per launch with / without stagger (tools/fetch_ab.sh): plain bf16,
-// 224-row tiles 415 / 282 MB, residual 547 / 412, dGELU 692 / 645, GELU 347 / 344.  Whole step (same box, alternating, ms): all
-// 33.12, residual + dGELU 33.13, dGELU only 33.26, none 33.42 -> only the two epilogues that are bound by their own traffic stagger.
-#ifndef NT_STAGGER_EPIS_DEFAULT
-#define NT_STAGGER_EPIS_DEFAULT 0x18
-#endif
-#ifndef NT_STAGGER_DEFAULT
-#define NT_STAGGER_DEFAULT 1.0f
-#endif
-// diagnostic builds only (tools/build_variant.sh): 1 = epilogue arithmetic and loads but NO stores,
-// 2 = stores but no GELU / dropout arithmetic and no residual / g' loads
-#ifndef NT_ABLATE
-#define NT_ABLATE 0
-#endif
-// diagnostic builds only: ping-pong K loop without 1 = DMA, 2 = fragment reads, 3 = MFMA
-#ifndef NT_LOOP_ABLATE
-#define NT_LOOP_ABLATE 0
-#endif
-
 namespace {
-
-template <int V>
-using IC = std::integral_constant<int, V>;
 
 template <int BK_, int WM_, int WN_, int MI_ = 8>
 struct NtCfg {
@@ -200,13 +115,13 @@ __device__ __forceinline__ void stage_tile(__amdgpu_buffer_rsrc_t rsrc, char* ld
     const int c = lane % LPR;                   // 16-B chunk position in the LDS row
     const int sc = c ^ nt_swz<BK_>(r);          // chunk fetched from global
     const unsigned voff = (unsigned)(((row0 + r) * (long long)K + k0) * 2 + sc * 16);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, LDS_PTR(lds_tile + i * 1024), 16, voff, 0, 0, 0);
+    dma16_to_lds(rsrc, lds_tile + i * 1024, voff);
   }
 }
 
-// s_waitcnt vmcnt(N) with a compile-time N
+// s_waitcnt vmcnt(N rounded down to 16, 8 or 0): waits at least as long as the exact count (common.h, wait_vmcnt)
 template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
+__device__ __forceinline__ void wait_vmcnt_round_down() {
   if constexpr (N >= 16) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
   else if constexpr (N >= 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
   else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -277,7 +192,7 @@ __device__ __forceinline__ void nt_epilogue(const NtParams& p, f32x4 (&acc)[4][C
   // TLS: xs = this wave's private 2 KiB of LDS (ping-pong kernel: its own B1 staging slots of the buffer that is not being
   // refilled, see the kernel) and N is a multiple of 8; otherwise the stores leave in the accumulator layout
   // GLUT_OFF >= 0: LDS byte offset of the GELU table minus GLUT_LO8 (the ds_read's immediate)
-  constexpr bool GLUT = EPI == VITSSL_EPI_GELU && GLUT_OFF >= 0 && NT_ABLATE == 0;
+  constexpr bool GLUT = EPI == VITSSL_EPI_GELU && GLUT_OFF >= 0;
   // fp8 operands: the table's entries are (bf16 s gelu'(u)) | (e4m3(s gelu(u) qs) << 16) -- the e4m3 byte is quantised from
   // the fp32 value when the table is built, exactly as the arithmetic path does per element -- and serve launches that
   // write the g' image and the e4m3 image only (no bf16 `a`, no amax: what engine.EncoderStack asks for); launch-uniform
@@ -327,7 +242,10 @@ __device__ __forceinline__ void nt_epilogue(const NtParams& p, f32x4 (&acc)[4][C
     auto hi = __builtin_amdgcn_permlane16_swap(w0[1], w1[1], false, false);
     return u32x4{lo[0], hi[0], lo[1], hi[1]};
   };
-  // ---- line-shaped stores through the wave's LDS window (NT_LDS_T).  A 16-row tile of an image is 16 rows x 128 bytes
+  // ---- line-shaped stores through the wave's LDS window (TLS), so that a store instruction's 64 lanes cover 8 rows x 128
+  // CONTIGUOUS bytes with adjacent lanes on adjacent addresses.  tools/probes/store_patterns.hip: a CU stores 55 GB/s in the
+  // accumulator layout (adjacent lanes = adjacent ROWS, 16 bytes each: every lane is its own request) and 183-190 GB/s once four
+  // or more adjacent lanes are contiguous.  A 16-row tile of an image is 16 rows x 128 bytes
   // (64 bf16 columns, or the 32 fp32 columns of a pair).  It is written in the accumulator layout (lane (m, c) = row m, 8- or
   // 16-byte chunk), with the chunk position XORed by the row so the writes spread over the banks, and read back as lane
   // (rho, kappa) = row rho (+8 for the second read), 16-byte chunk kappa: 8 lanes = one 128-byte line.
@@ -350,14 +268,9 @@ __device__ __forceinline__ void nt_epilogue(const NtParams& p, f32x4 (&acc)[4][C
     const unsigned b = n < p.N ? (trow * un + (unsigned)n) * 4u : OOB;
     return b + (unsigned)(16 * i + 8 * half) * (un * 4u);
   };
-  // one row tile of a bf16 image: w[jp][h]
-  constexpr int BF16_AUX = NT_STORE_AUX != 0 ? NT_STORE_AUX : NT_BF16_AUX;
+  // one row tile of a bf16 image: w[jp][h]; AUXV = cache policy of the stores (buffer aux bits: 1 = sc0, 2 = nt, 16 = sc1)
   auto store_bf16_row = [&](__amdgpu_buffer_rsrc_t rs, int i, const u32x2 (&w)[2][2], auto aux_c) {
     constexpr int AUXV = decltype(aux_c)::value;
-    if (NT_ABLATE == 1) {
-      asm volatile("" ::"v"(w[0][0]), "v"(w[0][1]), "v"(w[1][0]), "v"(w[1][1]));
-      return;
-    }
     if (tls) {
 #pragma unroll
       for (int jp = 0; jp < 2; ++jp)
@@ -379,13 +292,10 @@ __device__ __forceinline__ void nt_epilogue(const NtParams& p, f32x4 (&acc)[4][C
       }
     }
   };
-  // one pair (32 columns) of a row tile of an fp32 image
-  constexpr int F32_AUX = NT_STORE_AUX != 0 ? NT_STORE_AUX : (EPI == VITSSL_EPI_RESID ? NT_RESID_AUX : 0);
+  // one pair (32 columns) of a row tile of an fp32 image.  Residual-stream stores (read next by a different kernel) are
+  // non-temporal (aux 2): interleaved A/B on MI355X, out-projection shape M = 50176, N = K = 768: 116 -> 97 us; neutral at K = 3072
+  constexpr int F32_AUX = EPI == VITSSL_EPI_RESID ? 2 : 0;
   auto store_f32_pair = [&](__amdgpu_buffer_rsrc_t rs, int i, int jp, const f32x4& v0, const f32x4& v1, const int (&nnp)[2]) {
-    if (NT_ABLATE == 1) {
-      asm volatile("" ::"v"(v0), "v"(v1));
-      return;
-    }
     if (tls) {
       *(f32x4*)(xs + tw32) = v0;
       *(f32x4*)(xs + (tw32 ^ 64u)) = v1;
@@ -444,15 +354,15 @@ __device__ __forceinline__ void nt_epilogue(const NtParams& p, f32x4 (&acc)[4][C
   // Rows per group: the group's loads are one memory round trip.  The 224-row tiles (MI = 7: every N = 768 launch of ViT-B,
   // both residual epilogues among them) take ONE row per group.  Round 3 measured uneven groups (4 + 3) against that,
   // interleaved: N = K = 768 residual 104 -> 109 us, K = 3072 residual 251 -> 247 us, dGELU unchanged -- the phase is
-  // bound by bytes, not by round trips (as round 1 found for MI = 8); NT_RG_RESID / NT_RG_DGELU keep the experiment.
-  // Operand prefetch (NT_EPI_PREFETCH, line-shaped form only): the residual / g' lines of group g+1 are requested BEFORE group g
+  // bound by bytes, not by round trips (as round 1 found for MI = 8).
+  // Operand prefetch (line-shaped form only): the residual / g' lines of group g+1 are requested BEFORE group g
   // is computed and stored.  The vector-memory counter retires in issue order, so in the plain order (loads of g+1 behind the
   // stores of g) the wait for a group's operands also waited for the previous group's stores to be acknowledged by the L2 --
   // one load round trip plus one store round trip per group, 7 times per tile for the 224-row residual epilogue.
-  constexpr bool PREF = NT_EPI_PREFETCH != 0 && TLS && (EPI == VITSSL_EPI_RESID || EPI == VITSSL_EPI_DGELU);
+  constexpr bool PREF = TLS && (EPI == VITSSL_EPI_RESID || EPI == VITSSL_EPI_DGELU);
   // (with the prefetch two groups of operands are alive at once: 1 row per group for the residual lines, 2 for g')
-  constexpr int RG = EPI == VITSSL_EPI_RESID ? (PREF ? NT_RG_RESID_PF : (MI % 2 == 0 ? 2 : NT_RG_RESID))
-                     : EPI == VITSSL_EPI_DGELU ? (PREF ? NT_RG_DGELU_PF : (MI % 4 == 0 ? 4 : NT_RG_DGELU))
+  constexpr int RG = EPI == VITSSL_EPI_RESID ? (PREF ? 1 : (MI % 2 == 0 ? 2 : 1))
+                     : EPI == VITSSL_EPI_DGELU ? (PREF ? 2 : (MI % 4 == 0 ? 4 : 2))
                                                : 4;
   constexpr int NB = PREF ? 2 : 1;
   f32x4 res[NB][RG][2][2];   // RESID: residual stream (line layout until used)
@@ -465,9 +375,7 @@ __device__ __forceinline__ void nt_epilogue(const NtParams& p, f32x4 (&acc)[4][C
 #pragma unroll
         for (int jp = 0; jp < 2; ++jp) {
           if (ii >= cnt) continue;
-          if (NT_ABLATE == 2) {
-            res[b][ii][jp][0] = res[b][ii][jp][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-          } else if (tls) {
+          if (tls) {
             // whole lines (8 rows x 128 bytes per instruction); turned into the accumulator layout through the LDS window at use
             res[b][ii][jp][0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsAux, off_line32(ig + ii, jp, 0), 0, 0));
             res[b][ii][jp][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsAux, off_line32(ig + ii, jp, 1), 0, 0));
@@ -579,7 +487,7 @@ __device__ __forceinline__ void nt_epilogue(const NtParams& p, f32x4 (&acc)[4][C
           // keep masks of each group's two bf16 pairs (0xffff per kept element), ANDed onto the packed outputs
           unsigned km[2][2] = {{0xffffffffu, 0xffffffffu}, {0xffffffffu, 0xffffffffu}};
           u32x2 dw[2] = {u32x2{0u, 0u}, u32x2{0u, 0u}};
-          const bool dropping = p.drop_on && NT_ABLATE != 2;
+          const bool dropping = p.drop_on;
           if (dropping) {
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
@@ -608,14 +516,7 @@ __device__ __forceinline__ void nt_epilogue(const NtParams& p, f32x4 (&acc)[4][C
             }
             float y[4], d[4];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              if (NT_ABLATE == 2) {
-                y[r] = v[h][r];
-                d[r] = v[h][r] * 0.5f;
-                continue;
-              }
-              gelu_both_scaled(round_bf(v[h][r]), gelu_hs, gelu_cs, y[r], d[r]);
-            }
+            for (int r = 0; r < 4; ++r) gelu_both_scaled(round_bf(v[h][r]), gelu_hs, gelu_cs, y[r], d[r]);
             out_b[jp][h] = u32x2{pack_bf2(y[0], y[1]) & km[h][0], pack_bf2(y[2], y[3]) & km[h][1]};
             out_a[jp][h] = u32x2{pack_bf2(d[0], d[1]) & km[h][0], pack_bf2(d[2], d[3]) & km[h][1]};
             if constexpr (Q8) {
@@ -656,7 +557,7 @@ __device__ __forceinline__ void nt_epilogue(const NtParams& p, f32x4 (&acc)[4][C
         } else if constexpr (EPI == VITSSL_EPI_F32) {
           store_f32_pair(rsOut0, i, jp, v[0], v[1], nn[jp]);
         } else if constexpr (EPI == VITSSL_EPI_RESID) {
-          if (tls && NT_ABLATE != 2) {            // the pair's residual lines -> accumulator layout (inverse of store_f32_pair's path)
+          if (tls) {                              // the pair's residual lines -> accumulator layout (inverse of store_f32_pair's path)
             *(f32x4*)(xs + tr32a) = res[gb][ii][jp][0];
             *(f32x4*)(xs + tr32a + 1024) = res[gb][ii][jp][1];
             res[gb][ii][jp][0] = *(const f32x4*)(xs + tw32);
@@ -664,7 +565,7 @@ __device__ __forceinline__ void nt_epilogue(const NtParams& p, f32x4 (&acc)[4][C
           }
 #pragma unroll
           for (int h = 0; h < 2; ++h) {
-            if (p.drop_on && NT_ABLATE != 2) {
+            if (p.drop_on) {
               bool keep[4];
               drop_keep4(p.dk, drop_words_a0(p.dk, a0row + (unsigned)i * a0rowstep + a0col[jp][h]), keep);
 #pragma unroll
@@ -698,11 +599,12 @@ __device__ __forceinline__ void nt_epilogue(const NtParams& p, f32x4 (&acc)[4][C
       // the row's 128 bytes of every bf16 image leave in back-to-back instructions
       if constexpr (EPI == VITSSL_EPI_BF16 || EPI == VITSSL_EPI_GELU || EPI == VITSSL_EPI_DGELU) {
         // fp8 path: the bf16 image of a dGELU output is optional once its e4m3 image is written (launch-uniform)
-        if (!(Q8 && EPI == VITSSL_EPI_DGELU) || p.out0)
-          store_bf16_row(rsOut0, i, out_a, IC<(EPI == VITSSL_EPI_GELU && NT_STORE_AUX == 0) ? NT_GPRIME_AUX : BF16_AUX>{});
+        // g' (out0 of the GELU epilogue) is read again only in backward: its stores are non-temporal (aux 2) so that `a`, which
+        // FC2 reads next, keeps its lines (in-step A/B: -0.25 ms per ViT-B step; sc1 = 16 was slower)
+        if (!(Q8 && EPI == VITSSL_EPI_DGELU) || p.out0) store_bf16_row(rsOut0, i, out_a, IC<EPI == VITSSL_EPI_GELU ? 2 : 0>{});
       }
       if constexpr (EPI == VITSSL_EPI_GELU) {
-        if (!Q8 || p.out1) store_bf16_row(rsOut1, i, out_b, IC<BF16_AUX>{});   // same for the GELU output
+        if (!Q8 || p.out1) store_bf16_row(rsOut1, i, out_b, IC<0>{});   // same for the GELU output
       }
       if constexpr (Q8EPI) {
         if (q8) {
@@ -722,17 +624,17 @@ __device__ __forceinline__ void nt_epilogue(const NtParams& p, f32x4 (&acc)[4][C
               const u32x4 s8 = *(const u32x4*)(xs + rho4 * 64 + ((kap4 ^ ((rho4 >> 1) & 3)) << 4));
               const int n8 = n0 + wn * 64 + 16 * kap4;
               const unsigned o8 = n8 < p.N ? ((unsigned)(wm * CFG::WROWS + 16 * i + rho4) * un + (unsigned)n8) : OOB;
-              __builtin_amdgcn_raw_buffer_store_b128(s8, rsOut2, o8, 0, BF16_AUX);
+              __builtin_amdgcn_raw_buffer_store_b128(s8, rsOut2, o8, 0, 0);
             } else {
               const int n = n0 + wn * 64 + 16 * g4;
-              __builtin_amdgcn_raw_buffer_store_b128(u32x4{e[0], e[1], f[0], f[1]}, rsOut2, off_elem(i, n, 1u), 0, BF16_AUX);
+              __builtin_amdgcn_raw_buffer_store_b128(u32x4{e[0], e[1], f[0], f[1]}, rsOut2, off_elem(i, n, 1u), 0, 0);
             }
           } else {
 #pragma unroll
             for (int jp = 0; jp < 2; ++jp)
 #pragma unroll
               for (int h = 0; h < 2; ++h)
-                __builtin_amdgcn_raw_buffer_store_b32(out_q[jp][h], rsOut2, off_elem(i, nn[jp][h], 1u), 0, BF16_AUX);
+                __builtin_amdgcn_raw_buffer_store_b32(out_q[jp][h], rsOut2, off_elem(i, nn[jp][h], 1u), 0, 0);
           }
         }
       }
@@ -808,8 +710,7 @@ __global__ __launch_bounds__(CFG::THREADS, CFG::MIN_WAVES_PER_SIMD) void gemm_nt
     const int base = r * G;
     const int cnt = min(G, ntiles - base);
     if (bid >= cnt) return false;
-    const int xcd = bid & 7, q = cnt >> 3, rr = cnt & 7;
-    const int wgid = base + (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (bid >> 3);
+    const int wgid = base + xcd_remap(bid, cnt);
     const int full = p.tiles_m * p.group_n;
     const int cg = wgid / full;
     const int rem = wgid - cg * full;
@@ -930,7 +831,7 @@ __global__ __launch_bounds__(CFG::THREADS, CFG::MIN_WAVES_PER_SIMD) void gemm_nt
     // flight" implies that DMA has landed, without waiting for the stores themselves.
     constexpr int TAIL = (EPI == VITSSL_EPI_GELU || EPI == VITSSL_EPI_F32) ? 16
                          : ((EPI == VITSSL_EPI_EMBED || EPI == EPI_F32_SPLITK) ? 0 : 8);   // stores of the last row group
-    wait_vmcnt<TAIL>();
+    wait_vmcnt_round_down<TAIL>();
     m0 = m0n;
     n0 = n0n;
   }
@@ -972,7 +873,6 @@ constexpr int nt_epi_vmem_ops() {
   // row tile), DGELU = g' loads + the bf16 image (2 + 2).  fp8 operands: the bf16 `a` image (GELU) / the bf16 dGELU image are
   // optional at launch time, so only g' stores (GELU: 2) or g' loads (DGELU: 2) plus the one e4m3 store are certain: 3 per row tile
   // (round-3 advisor finding: 4 was counted).
-  if (NT_ABLATE != 0) return 0;
   return EPI == VITSSL_EPI_BF16 ? 2 * MI
          : (EPI == VITSSL_EPI_GELU || EPI == VITSSL_EPI_DGELU) ? (F8 ? 3 * MI : 4 * MI)
          : EPI == VITSSL_EPI_F32 ? 4 * MI
@@ -980,26 +880,10 @@ constexpr int nt_epi_vmem_ops() {
          : 0;
 }
 
-template <int N>
-__device__ __forceinline__ void wait_vmcnt_exact() {
-  static_assert(N >= 0 && N <= 63, "vmcnt is a 6-bit counter");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 // two 16-byte fragments of one tile row -> the 32-byte operand of the K = 128 fp8 MFMA
 __device__ __forceinline__ i32x8 join_frags(const bf16x8& lo, const bf16x8& hi) {
   const u32x4 a = __builtin_bit_cast(u32x4, lo), b = __builtin_bit_cast(u32x4, hi);
   return i32x8{(int)a[0], (int)a[1], (int)a[2], (int)a[3], (int)b[0], (int)b[1], (int)b[2], (int)b[3]};
-}
-
-// (target builtins with immediate operands are kept out of the kernel's lambdas: on the host pass a
-// lambda body is checked eagerly and the kernel would silently lose its stub)
-// cache policy of the operand DMA (buffer aux bits: 1 = sc0, 2 = nt, 16 = sc1); developer experiments only
-#ifndef NT_DMA_AUX
-#define NT_DMA_AUX 0
-#endif
-__device__ __forceinline__ void dma16_to_lds(__amdgpu_buffer_rsrc_t rsrc, char* lds_wave_base, unsigned voffset) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, LDS_PTR(lds_wave_base), 16, voffset, 0, 0, NT_DMA_AUX);
 }
 
 template <int EPI, typename CFG, bool F8 = false>
@@ -1012,7 +896,7 @@ __global__ __launch_bounds__(CFG::THREADS, 2) void gemm_nt_pp_kernel(NtParams p)
   constexpr int DUMMY = 2 * BUF;                       // 1 KiB sink for the slots a short A1 unit does not need
   constexpr unsigned OOBV = 0x80000000u;
   // EPI_GELU (bf16 operands): the 18 KiB GELU table sits behind the sink (see "GELU by table" above nt_epilogue)
-  constexpr bool USE_GLUT = EPI == VITSSL_EPI_GELU && NT_ABLATE == 0 && NT_GELU_LUT;
+  constexpr bool USE_GLUT = EPI == VITSSL_EPI_GELU;
   constexpr int GLUT_BASE = 2 * BUF + 1024;
   constexpr int GLUT_IMM = USE_GLUT ? GLUT_BASE - (int)GLUT_LO8 : -1;
   static_assert(!USE_GLUT || (GLUT_IMM >= 0 && GLUT_IMM < 65536), "the table's offset must fit the ds_read immediate");
@@ -1028,8 +912,7 @@ __global__ __launch_bounds__(CFG::THREADS, 2) void gemm_nt_pp_kernel(NtParams p)
     const int base = r * G;
     const int cnt = min(G, ntiles - base);
     if (bid >= cnt) return false;
-    const int xcd = bid & 7, q = cnt >> 3, rr = cnt & 7;
-    const int wgid = base + (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (bid >> 3);
+    const int wgid = base + xcd_remap(bid, cnt);
     const int full = p.tiles_m * p.group_n;
     const int cg = wgid / full;
     const int rem = wgid - cg * full;
@@ -1067,8 +950,6 @@ __global__ __launch_bounds__(CFG::THREADS, 2) void gemm_nt_pp_kernel(NtParams p)
   constexpr unsigned ESZ = F8 ? 1u : 2u;
   const unsigned long long a_bytes = (unsigned long long)p.M * p.K * ESZ;
   const unsigned long long b_bytes = (unsigned long long)p.N * p.K * ESZ;
-  __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, (int)a_bytes, 0x00020000);
-  __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc((void*)p.B, 0, (int)b_bytes, 0x00020000);
   const int nk = F8 ? p.K / 128 : p.K / 64;
   const unsigned rowb = (unsigned)p.K * ESZ;           // bytes per operand row
 
@@ -1134,29 +1015,25 @@ __global__ __launch_bounds__(CFG::THREADS, 2) void gemm_nt_pp_kernel(NtParams p)
   // DMA of one unit: 2 wave-instructions.  bufsel = LDS buffer (0/1) of the unit's K-tile.
   auto stage_a = [&](const Cur& c, int bufsel, auto h_c) {
     constexpr int h = decltype(h_c)::value;
-    if (NT_LOOP_ABLATE == 1 && bufsel >= 0) return;
     // The K-tile's position goes into the DESCRIPTOR (scalar arithmetic: window = operand bytes from (tile row 0, k0) on; an ended
     // stream gets an empty window -> zero fill, no traffic), not into the lanes' offsets: the LOAD parts of this loop share their SIMD
     // with the partner wave's MFMA cluster and vector-ALU instructions there cost issue slots (csrc/gemm_tn.hip).
-    __amdgpu_buffer_rsrc_t rs = NT_DESC_WINDOW ? __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)p.A + c.a), 0,
-                                                                                    c.a == OOBV ? 0 : (int)(a_bytes - c.a), 0x00020000)
-                                               : rsA;
+    __amdgpu_buffer_rsrc_t rs =
+        __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)p.A + c.a), 0, c.a == OOBV ? 0 : (int)(a_bytes - c.a), 0x00020000);
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
       const bool live = ldsA[h][e] != DUMMY;
       // (an ended stream has c.a = OOBV: out of range for every live slot -> zero fill)
-      dma16_to_lds(rs, smem + (live ? bufsel * BUF : 0) + ldsA[h][e], NT_DESC_WINDOW ? voffA[h][e] : voffA[h][e] + c.a);
+      dma16_to_lds(rs, smem + (live ? bufsel * BUF : 0) + ldsA[h][e], voffA[h][e]);
     }
   };
   auto stage_b = [&](const Cur& c, int bufsel, auto h_c) {
     constexpr int h = decltype(h_c)::value;
-    if (NT_LOOP_ABLATE == 1 && bufsel >= 0) return;
-    __amdgpu_buffer_rsrc_t rs = NT_DESC_WINDOW ? __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)p.B + c.b), 0,
-                                                                                    c.b == OOBV ? 0 : (int)(b_bytes - c.b), 0x00020000)
-                                               : rsB;
+    __amdgpu_buffer_rsrc_t rs =
+        __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)p.B + c.b), 0, c.b == OOBV ? 0 : (int)(b_bytes - c.b), 0x00020000);
 #pragma unroll
     for (int e = 0; e < 2; ++e)
-      dma16_to_lds(rs, smem + bufsel * BUF + ldsB[h][e], NT_DESC_WINDOW ? voffB[h][e] : voffB[h][e] + c.b);
+      dma16_to_lds(rs, smem + bufsel * BUF + ldsB[h][e], voffB[h][e]);
   };
 
   // ---- fragment addressing (as in gemm_nt_kernel)
@@ -1175,7 +1052,6 @@ __global__ __launch_bounds__(CFG::THREADS, 2) void gemm_nt_pp_kernel(NtParams p)
   auto read_a = [&](const char* buf, auto mh_c) {
     constexpr int mh = decltype(mh_c)::value;
     constexpr int cnt = mh == 0 ? 4 : MH1;
-    if (NT_LOOP_ABLATE == 2 && buf != nullptr) return;
 #pragma unroll
     for (int ii = 0; ii < cnt; ++ii) {
       fa[0][ii] = *(const bf16x8*)(buf + offA0 + (4 * mh + ii) * 2048);
@@ -1184,22 +1060,17 @@ __global__ __launch_bounds__(CFG::THREADS, 2) void gemm_nt_pp_kernel(NtParams p)
   };
   auto read_b = [&](const char* buf, auto nh_c) {
     constexpr int nh = decltype(nh_c)::value;
-    if (NT_LOOP_ABLATE == 2 && buf != nullptr) return;
 #pragma unroll
     for (int jj = 0; jj < 2; ++jj) {
       fb[nh][0][jj] = *(const bf16x8*)(buf + offB0 + (2 * nh + jj) * 2048);
       fb[nh][1][jj] = *(const bf16x8*)(buf + offB1 + (2 * nh + jj) * 2048);
     }
   };
+  // (s_setprio 1 around these clusters was neutral in round 2 and cost 0.5-1.5 % with the leaner loops of round 3: 8 more scalar
+  // instructions per K-tile in LOAD parts that are bound by issue slots; profiles/r03_tls_ab.txt)
   auto mma_quad = [&](auto mh_c, auto nh_c) {
     constexpr int mh = decltype(mh_c)::value, nh = decltype(nh_c)::value;
     constexpr int cnt = mh == 0 ? 4 : MH1;
-    if (NT_LOOP_ABLATE == 3) {
-      asm volatile("" ::"v"(fa[0][0]), "v"(fa[1][0]), "v"(fa[0][1]), "v"(fa[1][1]), "v"(fa[0][2]), "v"(fa[1][2]), "v"(fa[0][3]), "v"(fa[1][3]),
-                   "v"(fb[nh][0][0]), "v"(fb[nh][1][0]), "v"(fb[nh][0][1]), "v"(fb[nh][1][1]));
-      return;
-    }
-    if (NT_SETPRIO) __builtin_amdgcn_s_setprio(1);
     if constexpr (F8) {
 #pragma unroll
       for (int jj = 0; jj < 2; ++jj) {
@@ -1219,18 +1090,7 @@ __global__ __launch_bounds__(CFG::THREADS, 2) void gemm_nt_pp_kernel(NtParams p)
             acc[2 * nh + jj][4 * mh + ii] =
                 __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[nh][kk][jj], fa[kk][ii], acc[2 * nh + jj][4 * mh + ii], 0, 0, 0);
     }
-    if (NT_SETPRIO) __builtin_amdgcn_s_setprio(0);
   };
-  auto section = [&]() {                               // end of a LOAD or COMPUTE part
-    // the raw s_barrier carries no fence: the empty asm statements keep the optimiser from moving
-    // fragment loads across it, sched_barrier keeps the machine scheduler from moving MFMAs
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("" ::: "memory");
-  };
-
   // One K-tile = 4 phases.  NW = counted wait of p0 / p1 / p3 (8, or 8 + S right after an epilogue).
   auto ktile = [&](int buf, const Cur& c1, const Cur& c2, bool last_of_round, auto nw_c) {
     constexpr int NW = decltype(nw_c)::value;
@@ -1239,31 +1099,31 @@ __global__ __launch_bounds__(CFG::THREADS, 2) void gemm_nt_pp_kernel(NtParams p)
     read_b(cur, IC<0>{});
     read_a(cur, IC<0>{});
     stage_b(c1, buf ^ 1, IC<1>{});
-    wait_vmcnt_exact<NW>();
-    section();
+    wait_vmcnt<NW>();
+    raw_barrier();
     mma_quad(IC<0>{}, IC<0>{});
-    section();
+    raw_barrier();
     // p1: quadrant (m0, n1)
     read_b(cur, IC<1>{});
     stage_a(c1, buf ^ 1, IC<1>{});
-    wait_vmcnt_exact<NW>();
-    section();
+    wait_vmcnt<NW>();
+    raw_barrier();
     mma_quad(IC<0>{}, IC<1>{});
-    section();
+    raw_barrier();
     // p2: quadrant (m1, n1)
     read_a(cur, IC<1>{});
     stage_b(c2, buf, IC<0>{});
-    section();
+    raw_barrier();
     mma_quad(IC<1>{}, IC<1>{});
-    section();
+    raw_barrier();
     // p3: quadrant (m1, n0)
     stage_a(c2, buf, IC<0>{});
-    wait_vmcnt_exact<NW>();
-    section();
+    wait_vmcnt<NW>();
+    raw_barrier();
     mma_quad(IC<1>{}, IC<0>{});
     // waves 4-7 leave the stagger at the end of an output tile (they re-enter it with the
     // barrier at the top of the next one): both wave groups then run their epilogues together
-    if (!(last_of_round && wm == 1)) section();
+    if (!(last_of_round && wm == 1)) raw_barrier();
   };
 
   // ---- prologue: K-tiles 0 and (B0, A0 of) 1 of the stream
@@ -1297,14 +1157,12 @@ __global__ __launch_bounds__(CFG::THREADS, 2) void gemm_nt_pp_kernel(NtParams p)
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   }
-  wait_vmcnt_exact<8>();                               // B0, A0 of K-tile 0 have landed
-  section();
+  wait_vmcnt<8>();                               // B0, A0 of K-tile 0 have landed
+  raw_barrier();
 
   constexpr int S = nt_epi_vmem_ops<EPI, MI, F8>();
-#ifndef NT_PROBE_NW
-#define NT_PROBE_NW 8      // timing probe only: any other value reads staging units that may not have landed
-#endif
-  constexpr int NW_POST = (NT_PROBE_NW + S) > 63 ? 63 : (NT_PROBE_NW + S);
+  constexpr int NW = 8;                                // "all but the 4 newest units have landed"
+  constexpr int NW_POST = (NW + S) > 63 ? 63 : (NW + S);
   int buf = 0;
 #ifdef VITSSL_NT_STAMPS
   auto stamp = [&](int round, int which) {
@@ -1319,7 +1177,7 @@ __global__ __launch_bounds__(CFG::THREADS, 2) void gemm_nt_pp_kernel(NtParams p)
 #endif
   for (int round = 0;; ++round) {
     stamp(round, 0);
-    if (wm == 1) section();                            // waves 4-7 run one barrier behind waves 0-3
+    if (wm == 1) raw_barrier();                        // waves 4-7 run one barrier behind waves 0-3
 #pragma unroll
     for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -1327,7 +1185,7 @@ __global__ __launch_bounds__(CFG::THREADS, 2) void gemm_nt_pp_kernel(NtParams p)
     for (int t = 0; t < nk; ++t) {
       const bool last = t + 1 == nk;
       if (t == 0 && round > 0) ktile(buf, c1, c2, last, IC<NW_POST>{});
-      else ktile(buf, c1, c2, last, IC<NT_PROBE_NW>{});
+      else ktile(buf, c1, c2, last, IC<NW>{});
       c1 = c2;
       c2 = cur_next(c2);
       buf ^= 1;
@@ -1345,7 +1203,7 @@ __global__ __launch_bounds__(CFG::THREADS, 2) void gemm_nt_pp_kernel(NtParams p)
     // the wave's LDS window for line-shaped stores: its own two B1 staging slots (2 KiB, contiguous) of the buffer whose B1 / A1
     // units are not in flight -- K-tile (last) read them two barriers ago, and this wave itself re-issues them in p0 of the
     // next K-tile, after its epilogue in program order; no other wave ever writes there
-    nt_epilogue<EPI, CFG, F8, GLUT_IMM, NT_LDS_T != 0>(p, acc, m0, n0, wm, wn, lane, smem, smem + (buf ^ 1) * BUF + ldsB[1][0]);
+    nt_epilogue<EPI, CFG, F8, GLUT_IMM, true>(p, acc, m0, n0, wm, wn, lane, smem, smem + (buf ^ 1) * BUF + ldsB[1][0]);
     stamp(round, 2);
 #ifdef VITSSL_NT_STAMPS
     if (p.stamps) {                                    // diagnostic: when have this wave's stores been acknowledged?
@@ -1362,40 +1220,31 @@ __global__ __launch_bounds__(CFG::THREADS, 2) void gemm_nt_pp_kernel(NtParams p)
 int cu_count() { return vitssl_persistent_cus(); }
 void nt_note_grid(int grid);   // remembers the workgroup count of the last ping-pong launch (vitssl_debug_last_nt_grid)
 
-// 1 (default): 8-wave BK = 64 tiles run the ping-pong kernel; 0: the two-phase loop (VITSSL_NT_PP, developer knob)
-int nt_pp_enabled() {
-  static VsEnvInt knob;
-  return knob.get("VITSSL_NT_PP", 1);
-}
-
 template <int EPI, typename CFG, bool F8 = false>
 int launch_pp(NtParams p, hipStream_t s) {
-  constexpr int LDS = 2 * CFG::BUF_BYTES + 1024 + ((EPI == VITSSL_EPI_GELU && NT_ABLATE == 0 && NT_GELU_LUT) ? GLUT_BYTES : 0);
+  constexpr int LDS = 2 * CFG::BUF_BYTES + 1024 + (EPI == VITSSL_EPI_GELU ? GLUT_BYTES : 0);
   static VsOnce attr_done{false};
-  if (!attr_done.load(std::memory_order_relaxed)) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_nt_pp_kernel<EPI, CFG, F8>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    if (e != hipSuccess) {
-      vitssl_set_error("gemm_nt: cannot raise dynamic LDS to %d: %s", LDS, hipGetErrorString(e));
-      return VITSSL_ERR_LAUNCH;
-    }
-    attr_done.store(true, std::memory_order_relaxed);
-  }
+  if (int rc = ensure_lds(gemm_nt_pp_kernel<EPI, CFG, F8>, LDS, attr_done, "gemm_nt")) return rc;
   const long long ntiles = (long long)p.tiles_m * p.tiles_n;
   const long long slots = cu_count();
   const long long grid = ntiles < slots ? ntiles : slots;
-  // tile-time estimate for the start-up stagger (us): K loop ~1.45 us per 256-row K-tile + an uncontended epilogue
+  // tile-time estimate for the start-up stagger (us): K loop ~1.45 us per 256-row K-tile + an uncontended epilogue.
+  // Round 2 measured the stagger time-neutral: in the accumulator layout a CU's stores were bound inside the CU (55 GB/s) whether or
+  // not the other CUs stored at the same moment.  With line-shaped epilogue accesses a CU alone stores 180+ GB/s but only ~55 when
+  // all 256 burst together, so spreading the epilogues pays: interleaved A/B, M = 50176: dGELU 281 -> 262 us (N = 3072, K = 768),
+  // residual 241 -> 231 (K = 3072), plain stores -1.5..-3 %, never slower; whole step 34.29 -> 34.05 ms.
   // VITSSL_NT_STAGGER (developer knob): scale of the window, 0 = off
+  constexpr float STAGGER_SCALE = 1.0f;
   static VsEnvMilli stagger_knob;
-  {
-    // Round 2 measured this time-neutral: in the accumulator layout a CU's stores were bound inside the CU (55 GB/s) whether or not
-    // the other CUs stored at the same moment.  With line-shaped epilogue accesses (NT_LDS_T) a CU alone stores 180+ GB/s but only
-    // ~55 when all 256 burst together, so spreading the epilogues now pays: interleaved A/B, M = 50176: dGELU 281 -> 262 us
-    // (N = 3072, K = 768), residual 241 -> 231 (K = 3072), plain stores -1.5..-3 %, never slower; whole step 34.29 -> 34.05 ms.
-  }
-  const float stagger_scale = stagger_knob.get("VITSSL_NT_STAGGER", NT_STAGGER_DEFAULT);
-  // which epilogues stagger (bit = VITSSL_EPI_* value; VITSSL_NT_STAGGER_EPIS overrides): see NT_STAGGER_EPIS_DEFAULT
+  const float stagger_scale = stagger_knob.get("VITSSL_NT_STAGGER", STAGGER_SCALE);
+  // Which epilogues stagger (bit = VITSSL_EPI_* value; VITSSL_NT_STAGGER_EPIS overrides).  Spreading the workgroups in time costs L2
+  // sharing (the workgroups of a raster group are no longer at the same k): FETCH_SIZE per launch with / without stagger
+  // (tools/fetch_ab.sh): plain bf16, 224-row tiles 415 / 282 MB, residual 547 / 412, dGELU 692 / 645, GELU 347 / 344.  Whole step
+  // (same box, alternating, ms): all 33.12, residual + dGELU 33.13, dGELU only 33.26, none 33.42 -> only the two epilogues that are
+  // bound by their own traffic stagger.
+  constexpr int STAGGER_EPIS = (1 << VITSSL_EPI_RESID) | (1 << VITSSL_EPI_DGELU);
   static VsEnvInt stagger_mask_knob;
-  const int stagger_mask = stagger_mask_knob.get("VITSSL_NT_STAGGER_EPIS", NT_STAGGER_EPIS_DEFAULT);
+  const int stagger_mask = stagger_mask_knob.get("VITSSL_NT_STAGGER_EPIS", STAGGER_EPIS);
   const float epi_us = EPI == VITSSL_EPI_BF16 ? 2.f : EPI == VITSSL_EPI_GELU ? 7.f : EPI == VITSSL_EPI_DGELU ? 5.f
                        : EPI == VITSSL_EPI_RESID ? 8.f : 4.f;
   const float tile_us = (float)(p.K * p.esz / 128) * 1.45f * (float)CFG::MI / 8.f + epi_us;
@@ -1408,15 +1257,9 @@ int launch_pp(NtParams p, hipStream_t s) {
 
 template <int EPI, typename CFG>
 int launch_cfg_parts(NtParams p, hipStream_t s) {
-  static VsOnce attr_done{false};
-  if (!attr_done.load(std::memory_order_relaxed) && CFG::LDS_BYTES > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_nt_kernel<EPI, CFG>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       CFG::LDS_BYTES);
-    if (e != hipSuccess) {
-      vitssl_set_error("gemm_nt: cannot raise dynamic LDS to %d: %s", CFG::LDS_BYTES, hipGetErrorString(e));
-      return VITSSL_ERR_LAUNCH;
-    }
-    attr_done.store(true, std::memory_order_relaxed);
+  if constexpr (CFG::LDS_BYTES > 48 * 1024) {
+    static VsOnce attr_done{false};
+    if (int rc = ensure_lds(gemm_nt_kernel<EPI, CFG>, CFG::LDS_BYTES, attr_done, "gemm_nt")) return rc;
   }
   p.tiles_m = (int)ceil_div64(p.M, CFG::BM);
   p.tiles_n = (int)ceil_div64(p.N, CFG::BN);
@@ -1446,7 +1289,7 @@ int launch_cfg_parts(NtParams p, hipStream_t s) {
     }
   }
   if constexpr (CFG::WAVES == 8 && CFG::BK == 64 && EPI != EPI_F32_SPLITK) {
-    if (nt_pp_enabled() && p.k_chunk == 0 && (p.N & 7) == 0) return launch_pp<EPI, CFG>(p, s);   // (its line-shaped stores move 8 columns per lane)
+    if (p.k_chunk == 0 && (p.N & 7) == 0) return launch_pp<EPI, CFG>(p, s);   // (its line-shaped stores move 8 columns per lane)
   }
   // Persistent workgroups.  Measured on MI355X (bench.py, same box, alternating runs): with
   // K = 768 / 3072 (ViT-B) the NT family takes 23.12 ms per step either way and the whole step

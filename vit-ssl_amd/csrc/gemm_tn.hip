@@ -16,7 +16,6 @@
 // rate; they remain as the fallback when no workspace is given).  Rows past M are
 // zero-filled by the buffer descriptor's bounds check, so ragged M needs no tail code.
 #include <stdlib.h>
-#include <type_traits>
 #include "common.h"
 
 #ifdef VITSSL_TN_STAMPS
@@ -48,125 +47,6 @@ struct TnParams {
 
 __device__ __forceinline__ int tn_f(int row) { return (row & 3) | (((row >> 3) & 1) << 2); }
 
-// stage rows [mrow0, mrow0+64) x cols [col0, col0+256) of X[M, ld] into lds_tile
-__device__ __forceinline__ void tn_stage(__amdgpu_buffer_rsrc_t rsrc, char* lds_tile, long long mrow0, int col0,
-                                         int ld, int wave, int lane) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int i = wave * 4 + j;                  // instruction slot: rows 2i, 2i+1
-    const int row = i * 2 + (lane >> 5);
-    const int ch16 = lane & 31;                  // 16-B chunk position in the LDS row
-    const int sc32 = (ch16 >> 1) ^ tn_f(row);    // 32-B chunk fetched from global
-    const int sch16 = (sc32 << 1) | (ch16 & 1);
-    const unsigned voff = (unsigned)(((mrow0 + row) * (long long)ld + col0) * 2 + sch16 * 16);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, LDS_PTR(lds_tile + i * 1024), 16, voff, 0, 0, 0);
-  }
-}
-
-// transposed fragment: 8 consecutive m (rows ks*32 + 8g + 0..7) of column c0 + (lane&15)
-__device__ __forceinline__ bf16x8 tn_frag(const char* tile, int ks, int c0, int lane) {
-  const int g = lane >> 4, q = (lane >> 2) & 3, pp = lane & 3;
-  const int c32 = c0 >> 4;
-  const int r0 = ks * 32 + 8 * g + q;
-  const int r1 = r0 + 4;
-  const char* a0 = tile + r0 * 512 + ((c32 ^ tn_f(r0)) << 5) + 8 * pp;
-  const char* a1 = tile + r1 * 512 + ((c32 ^ tn_f(r1)) << 5) + 8 * pp;
-  s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)a0);
-  s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)a1);
-  typedef __attribute__((ext_vector_type(8))) short s16x8;
-  s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8, v);
-}
-
-__global__ __launch_bounds__(TN_THREADS) void gemm_tn_kernel(TnParams p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int w1 = wave >> 2, w2 = wave & 3;
-
-  // block -> (split, tile1, tile2); splits of one tile are spread over XCDs (they share
-  // nothing), tiles sharing an operand panel are adjacent.
-  // XCD-aware bijective remap (blocks b, b+8, .. share an XCD): the tiles of one split,
-  // which share the split's dY / X row slabs, become neighbours on one XCD's L2.
-  const int ntiles = p.tiles1 * p.tiles2;
-  const int nwg = ntiles * p.splits;
-  const int xcd = blockIdx.x & 7, qq = nwg >> 3, rr = nwg & 7;
-  const int bid = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (blockIdx.x >> 3);
-  const int split = bid / ntiles;
-  const int tile = bid - split * ntiles;
-  const int t1 = tile / p.tiles2, t2 = tile - t1 * p.tiles2;
-  const int c1 = t1 * TN_T, c2 = t2 * TN_T;
-
-  const long long total_chunks = (p.M + TN_KM - 1) / TN_KM;
-  const long long ch_begin = (long long)split * p.chunks_per_split;
-  long long ch_end = ch_begin + p.chunks_per_split;
-  if (ch_end > total_chunks) ch_end = total_chunks;
-  const int nk = ch_begin < ch_end ? (int)(ch_end - ch_begin) : 0;   // empty split: writes a zero slab
-
-  __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, (int)((unsigned long long)p.M * p.N1 * 2ull), 0x00020000);
-  __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc((void*)p.B, 0, (int)((unsigned long long)p.M * p.N2 * 2ull), 0x00020000);
-
-  f32x4 acc[8][4];
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  if (nk > 0) {
-    tn_stage(rsA, smem, ch_begin * TN_KM, c1, p.N1, wave, lane);
-    tn_stage(rsB, smem + TN_TILE_BYTES, ch_begin * TN_KM, c2, p.N2, wave, lane);
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-
-  for (int t = 0; t < nk; ++t) {
-    const char* bufA = smem + (t & 1) * 2 * TN_TILE_BYTES;
-    const char* bufB = bufA + TN_TILE_BYTES;
-    if (t + 1 < nk) {
-      char* nA = smem + ((t + 1) & 1) * 2 * TN_TILE_BYTES;
-      tn_stage(rsA, nA, (ch_begin + t + 1) * TN_KM, c1, p.N1, wave, lane);
-      tn_stage(rsB, nA + TN_TILE_BYTES, (ch_begin + t + 1) * TN_KM, c2, p.N2, wave, lane);
-    }
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      bf16x8 fa[8], fb[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) fb[j] = tn_frag(bufB, ks, w2 * 64 + j * 16, lane);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) fa[i] = tn_frag(bufA, ks, w1 * 128 + i * 16, lane);
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[j], fa[i], acc[i][j], 0, 0, 0);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-  }
-
-  // D[n2 = 4*(lane>>4)+r][n1 = lane&15]: 4 consecutive n2 of one C row per lane
-  float* dst = p.slabs ? p.slabs + (long long)split * p.N1 * p.N2 : p.C;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int n1 = c1 + w1 * 128 + i * 16 + (lane & 15);
-    if (n1 >= p.N1) continue;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int n2 = c2 + w2 * 64 + j * 16 + 4 * (lane >> 4);
-      if (n2 >= p.N2) continue;
-      float* q = dst + (long long)n1 * p.N2 + n2;
-      if (p.slabs) {
-        *(f32x4*)q = acc[i][j];
-      } else if (p.direct) {
-        *(f32x4*)q = *(const f32x4*)q + acc[i][j];
-      } else {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) unsafeAtomicAdd(q + r, acc[i][j][r]);
-      }
-    }
-  }
-}
-
 // ====================================================================================
 // Ping-pong main loop for the weight-gradient GEMM (same scheme as gemm_nt_pp_kernel, see there).
 // A K-tile (64 contraction rows) is multiplied in 4 phases of 16 MFMAs: (ks, n1-half) =
@@ -177,43 +57,9 @@ __global__ __launch_bounds__(TN_THREADS) void gemm_tn_kernel(TnParams p) {
 // (a half is refilled two phases after its last fragment read: Bk0 is read in p0, Ak0 in p0-p1, Bk1 in
 // p2, Ak1 in p2-p3; the wait covering a half sits in the phase before its first read).
 typedef __attribute__((ext_vector_type(8))) short tn_s16x8;
-// diagnostic builds only (tools/build_variant.sh), bit mask: 1 = no DMA inside the K loop, 2 = no fragment reads, 4 = no MFMA
-#ifndef TN_ABLATE
-#define TN_ABLATE 0
-#endif
-// (A K-tile is two phases of 32 MFMAs per wave; round 2's four phases of 16 -- twice the barriers -- were 2-4 % slower and are gone.)
-// 1 = s_setprio 1 around the MFMA clusters, 2 = raised priority for the LOAD parts; 0 (default): none -- interleaved A/B on the four
-// ViT-B weight-gradient shapes: 0 is 1.0-1.9 % faster than 1, 2 is 0.6-1.3 % faster than 1 (round 2's loop gained 10 % from 1)
-#ifndef TN_SETPRIO
-#define TN_SETPRIO 0
-#endif
-// 1: the operand DMA of a partial tile skips the columns past the matrix (A/B builds: 0)
-#ifndef TN_MASK_COLS
-#define TN_MASK_COLS 1
-#endif
-
-
-template <int N>
-__device__ __forceinline__ void tn_wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-__device__ __forceinline__ void tn_dma16(__amdgpu_buffer_rsrc_t rsrc, char* lds_wave_base, unsigned voffset) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, LDS_PTR(lds_wave_base), 16, voffset, 0, 0, 0);
-}
-
-template <int IMM>
-__device__ __forceinline__ void tn_ds_tr(s16x4& dst, unsigned addr) {
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(IMM));
-}
-
-__device__ __forceinline__ void tn_section() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("" ::: "memory");
-}
+// (A K-tile is two phases of 32 MFMAs per wave; round 2's four phases of 16 -- twice the barriers -- were 2-4 % slower and are gone.
+// s_setprio around the MFMA clusters or the LOAD parts was 0.6-1.9 % slower on the four ViT-B weight-gradient shapes and is not
+// used, although round 2's loop gained 10 % from it.)
 
 // Tried in round 3 and dropped (git history: "single-stream" kernel): all 8 waves in step, every wave reading the NEXT phase's
 // fragments into a second register set in the shadow of its own MFMAs (inline-asm MFMAs interleaved 1:1 with the 24 reads + DMA,
@@ -261,7 +107,7 @@ __device__ __forceinline__ void tn_pp_unit(const TnUnit& p, char* smem) {
       // columns past the operand's width get the out-of-range offset (zero fill, no traffic): without it a partial tile
       // (ViT-S: 384 = 256 + 128) staged the first columns of the NEXT row in their place -- finite junk that the stores
       // skip, but 16 KiB per K-tile the CU took in for nothing
-      const bool okA = !TN_MASK_COLS || c1 + sch16 * 8 < p.N1, okB = !TN_MASK_COLS || c2 + sch16 * 8 < p.N2;
+      const bool okA = c1 + sch16 * 8 < p.N1, okB = c2 + sch16 * 8 < p.N2;
       voffA[h][e] = okA ? (unsigned)((row * (long long)p.N1 + c1) * 2 + sch16 * 16) : 0x80000000u;
       voffB[h][e] = okB ? (unsigned)((row * (long long)p.N2 + c2) * 2 + sch16 * 16) : 0x80000000u;
       ldsA[h][e] = r0 * 512;
@@ -278,17 +124,15 @@ __device__ __forceinline__ void tn_pp_unit(const TnUnit& p, char* smem) {
   };
   auto stage_a = [&](int t, int bufsel, auto h_c) {
     constexpr int h = decltype(h_c)::value;
-    if ((TN_ABLATE & 1) && t >= 2) return;
     __amdgpu_buffer_rsrc_t rs = window(p.A, p.N1, t);
 #pragma unroll
-    for (int e = 0; e < 2; ++e) tn_dma16(rs, smem + bufsel * TN_TILE_BYTES + ldsA[h][e], voffA[h][e]);
+    for (int e = 0; e < 2; ++e) dma16_to_lds(rs, smem + bufsel * TN_TILE_BYTES + ldsA[h][e], voffA[h][e]);
   };
   auto stage_b = [&](int t, int bufsel, auto h_c) {
     constexpr int h = decltype(h_c)::value;
-    if ((TN_ABLATE & 1) && t >= 2) return;
     __amdgpu_buffer_rsrc_t rs = window(p.B, p.N2, t);
 #pragma unroll
-    for (int e = 0; e < 2; ++e) tn_dma16(rs, smem + bufsel * TN_TILE_BYTES + ldsB[h][e], voffB[h][e]);
+    for (int e = 0; e < 2; ++e) dma16_to_lds(rs, smem + bufsel * TN_TILE_BYTES + ldsB[h][e], voffB[h][e]);
   };
 
   f32x4 acc[8][4];
@@ -315,8 +159,6 @@ __device__ __forceinline__ void tn_pp_unit(const TnUnit& p, char* smem) {
   }
   s16x4 tb[4][2];                                      // raw halves (rows r0.., rows r0 + 4..) of the fragments being read
   bf16x8 fb[4];
-  using I0 = std::integral_constant<int, 0>;
-  using I1 = std::integral_constant<int, 1>;
 
 #ifdef VITSSL_TN_STAMPS
   // diagnostic build (tools/tn_stamps.py): time (10 ns ticks) wave 0 / wave 4 spend in each part of a phase, summed over the K loop:
@@ -341,16 +183,15 @@ __device__ __forceinline__ void tn_pp_unit(const TnUnit& p, char* smem) {
   // the 24 transposed reads of one phase: buffer and contraction half are compile-time (immediate offsets), no address arithmetic
   auto read_frags = [&](auto buf_c, auto ks_c) {
     constexpr int IMM = decltype(buf_c)::value * TN_TILE_BYTES + decltype(ks_c)::value * 16384;
-    if (TN_ABLATE & 2) return;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      tn_ds_tr<IMM>(tb[j][0], fragB[j]);
-      tn_ds_tr<IMM + 2048>(tb[j][1], fragB[j]);
+      ds_read_tr16<IMM>(tb[j][0], fragB[j]);
+      ds_read_tr16<IMM + 2048>(tb[j][1], fragB[j]);
     }
 #pragma unroll
     for (int ii = 0; ii < 8; ++ii) {
-      tn_ds_tr<IMM>(ta2[ii][0], fragA[ii]);
-      tn_ds_tr<IMM + 2048>(ta2[ii][1], fragA[ii]);
+      ds_read_tr16<IMM>(ta2[ii][0], fragA[ii]);
+      ds_read_tr16<IMM + 2048>(ta2[ii][1], fragA[ii]);
     }
   };
   auto landed8 = [&]() {
@@ -368,56 +209,48 @@ __device__ __forceinline__ void tn_pp_unit(const TnUnit& p, char* smem) {
     }
   };
   auto mma32 = [&]() {
-    if (TN_ABLATE & 4) {
-      asm volatile("" ::"v"(fa2[0]), "v"(fa2[1]), "v"(fa2[2]), "v"(fa2[3]), "v"(fa2[4]), "v"(fa2[5]), "v"(fa2[6]), "v"(fa2[7]), "v"(fb[0]), "v"(fb[1]),
-                   "v"(fb[2]), "v"(fb[3]));
-      return;
-    }
-    if (TN_SETPRIO == 1) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int ii = 0; ii < 8; ++ii)
 #pragma unroll
       for (int j = 0; j < 4; ++j) acc[ii][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[j], fa2[ii], acc[ii][j], 0, 0, 0);
-    if (TN_SETPRIO == 1) __builtin_amdgcn_s_setprio(0);
   };
   // one phase = contraction half ks (32 rows) of K-tile t in buffer b: all 32 MFMAs of the wave; the ks half of K-tile t + 1 goes
   // into the other buffer
   auto phase = [&](auto buf_c, auto ks_c, int t, bool skip_section) {
     constexpr int bsel = decltype(buf_c)::value;
-    if (TN_SETPRIO == 2) __builtin_amdgcn_s_setprio(2);
     read_frags(buf_c, ks_c);
     stage_b(t + 1, bsel ^ 1, ks_c);
     stage_a(t + 1, bsel ^ 1, ks_c);
     TSTAMP(0);
-    tn_wait_vmcnt<4>();
+    wait_vmcnt<4>();
     TSTAMP(1);
-    tn_section();
+    raw_barrier();
     TSTAMP(2);
     landed8();
     TSTAMP(3);
     mma32();
     TSTAMP(4);
-    if (!skip_section) tn_section();
+    if (!skip_section) raw_barrier();
     TSTAMP(5);
   };
   if (nk > 0) {
-    stage_b(0, 0, I0{});
-    stage_a(0, 0, I0{});
-    stage_b(0, 0, I1{});
-    stage_a(0, 0, I1{});
-    tn_wait_vmcnt<4>();                                // the ks-0 halves of K-tile 0 have landed
-    tn_section();
-    if (w1 == 1) tn_section();                         // waves 4-7 run one barrier behind waves 0-3
+    stage_b(0, 0, IC<0>{});
+    stage_a(0, 0, IC<0>{});
+    stage_b(0, 0, IC<1>{});
+    stage_a(0, 0, IC<1>{});
+    wait_vmcnt<4>();                                // the ks-0 halves of K-tile 0 have landed
+    raw_barrier();
+    if (w1 == 1) raw_barrier();                         // waves 4-7 run one barrier behind waves 0-3
 #ifdef VITSSL_TN_STAMPS
     tprev = __builtin_amdgcn_s_memrealtime();
     const unsigned long long tclk0 = __builtin_amdgcn_s_memtime();     // shader clocks over the same loop: slot 7
 #endif
     for (int t = 0; t < nk; t += 2) {
-      phase(I0{}, I0{}, t, false);
-      phase(I0{}, I1{}, t, t + 1 == nk && w1 == 1);    // (waves 4-7 leave the stagger at the end)
+      phase(IC<0>{}, IC<0>{}, t, false);
+      phase(IC<0>{}, IC<1>{}, t, t + 1 == nk && w1 == 1);    // (waves 4-7 leave the stagger at the end)
       if (t + 1 >= nk) break;
-      phase(I1{}, I0{}, t + 1, false);
-      phase(I1{}, I1{}, t + 1, t + 2 == nk && w1 == 1);
+      phase(IC<1>{}, IC<0>{}, t + 1, false);
+      phase(IC<1>{}, IC<1>{}, t + 1, t + 2 == nk && w1 == 1);
     }
 #ifdef VITSSL_TN_STAMPS
     if (g_tn_stamps && p.stamp_wg >= 0 && lane == 0 && (wave & 3) == 0) {
@@ -460,10 +293,9 @@ __device__ __forceinline__ void tn_pp_unit(const TnUnit& p, char* smem) {
 
 __global__ __launch_bounds__(TN_THREADS, 2) void gemm_tn_pp_kernel(TnParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
+  // block -> (split, tile): the tiles of one split, which share the split's rows of both operands, are neighbours on one XCD
   const int ntiles = p.tiles1 * p.tiles2;
-  const int nwg = ntiles * p.splits;
-  const int xcd = blockIdx.x & 7, qq = nwg >> 3, rr = nwg & 7;
-  const int bid = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (blockIdx.x >> 3);
+  const int bid = xcd_remap(blockIdx.x, ntiles * p.splits);
   const int split = bid / ntiles;
   const int tile = bid - split * ntiles;
   const int t1 = tile / p.tiles2, t2 = tile - t1 * p.tiles2;
@@ -559,8 +391,7 @@ __device__ __forceinline__ void tn_batch_unit(const TnBatchParams& p, int un, in
 __global__ __launch_bounds__(TN_THREADS, 2) void gemm_tn_batch_kernel(TnBatchParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int G = gridDim.x;
-  const int xcd = blockIdx.x & 7, qq = G >> 3, rr = G & 7;
-  const int bid = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (blockIdx.x >> 3);
+  const int bid = xcd_remap(blockIdx.x, G);
   const TnBatchWalk w = tn_batch_walk(p, bid, G);
   for (int un = w.first; un < w.end; un += w.step) {
     TnUnit u;
@@ -575,7 +406,7 @@ __global__ __launch_bounds__(TN_THREADS, 2) void gemm_tn_batch_kernel(TnBatchPar
     u.mode = p.slots ? 3 : 1;
     u.stamp_wg = -1;
     tn_pp_unit(u, smem);
-    tn_section();                                      // every wave is done with the LDS before the next unit's first DMA
+    raw_barrier();                                      // every wave is done with the LDS before the next unit's first DMA
   }
 }
 
@@ -620,9 +451,8 @@ __global__ __launch_bounds__(256) void tn_batch_reduce_kernel(TnBatchParams p) {
 // takes rows 32 g + 8 q + 0..7 in read q: the same k order for both operands, which is all a contraction needs.
 // The 16-byte chunk index is XORed with f(row) = (row & 7) | ((row >> 5) & 1) << 3 on the DMA source side and on the
 // reads: the two lane groups of a half-wave then touch 16 rows x 16 B in 16 distinct chunk positions (conflict-free).
-// Plain double buffering, all 8 waves in step: one K = 128 MFMA step consumes the whole tile, so the half-tile units of
-// the ping-pong schedule (refilled two phases after their last read) do not exist here; the next tile's DMA is in
-// flight under the current tile's 48 reads and 32 MFMAs per wave.
+// (Round 3's form of the loop, plain double buffering with all 8 waves in step, was 19-21 % slower than the ping-pong loop
+// below and is gone; DESIGN.md section 10a keeps the numbers.)
 struct Tn8Params {
   const unsigned char* A;
   const unsigned char* B;
@@ -637,14 +467,8 @@ struct Tn8Params {
   const float* alpha2;
 };
 constexpr int TN8_KM = 128;
-typedef __attribute__((ext_vector_type(2))) int tn_i32x2;
 
 __device__ __forceinline__ int tn8_f(int row) { return (row & 7) | (((row >> 5) & 1) << 3); }
-
-template <int IMM>
-__device__ __forceinline__ void tn8_ds_tr(tn_i32x2& dst, unsigned addr) {
-  asm volatile("ds_read_b64_tr_b8 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(IMM));
-}
 
 // One unit of work of the e4m3 weight-gradient loop (as TnUnit; K-tiles of TN8_KM rows)
 struct Tn8Unit {
@@ -660,136 +484,6 @@ struct Tn8Unit {
   const float* alpha;
   const float* alpha2;
 };
-
-__device__ __forceinline__ void tn8_unit(const Tn8Unit& p, char* smem) {
-  constexpr int BUF = 2 * TN_TILE_BYTES;               // one K-tile: A tile then B tile
-  constexpr unsigned OOBV = 0x80000000u;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int w1 = wave >> 2, w2 = wave & 3;
-
-  const int c1 = p.c1, c2 = p.c2;
-  const long long ch_begin = p.ch_begin;
-  const int nk = p.nk;
-
-  __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, (int)((unsigned long long)p.M * p.N1), 0x00020000);
-  __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc((void*)p.B, 0, (int)((unsigned long long)p.M * p.N2), 0x00020000);
-
-  // staging: instruction slot e of this wave covers tile rows 16 wave + 4 e + (lane >> 4), one 16-byte chunk per lane
-  unsigned voffA[4], voffB[4];
-  int ldsoff[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const int r0 = 16 * wave + 4 * e;
-    const int row = r0 + (lane >> 4);
-    const int sch = (lane & 15) ^ tn8_f(row);
-    const bool ok1 = c1 + sch * 16 < p.N1, ok2 = c2 + sch * 16 < p.N2;     // columns past the matrix: zero fill
-    voffA[e] = ok1 ? (unsigned)(row * (long long)p.N1 + c1 + sch * 16) : OOBV;
-    voffB[e] = ok2 ? (unsigned)(row * (long long)p.N2 + c2 + sch * 16) : OOBV;
-    ldsoff[e] = r0 * 256;
-  }
-  const unsigned stepA = (unsigned)TN8_KM * (unsigned)p.N1, stepB = (unsigned)TN8_KM * (unsigned)p.N2;
-  auto stage = [&](int t, int bufsel) {
-    const unsigned ba = (unsigned)(ch_begin + t) * stepA, bb = (unsigned)(ch_begin + t) * stepB;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      tn_dma16(rsA, smem + bufsel * BUF + ldsoff[e], voffA[e] == OOBV ? OOBV : voffA[e] + ba);
-      tn_dma16(rsB, smem + bufsel * BUF + TN_TILE_BYTES + ldsoff[e], voffB[e] == OOBV ? OOBV : voffB[e] + bb);
-    }
-  };
-
-  f32x4 acc[8][4];
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  // per-lane byte address of read 0 (rows 32 g + (i >> 1)) of every 16-column tile; read q adds 8 rows = 2048 bytes
-  // (f(row + 8 q) = f(row) for q < 4: bits 3 and 4 of the row do not enter f)
-  const unsigned lds0 = (unsigned)(unsigned long long)LDS_PTR(smem);
-  unsigned fragA[8], fragB[4];
-  {
-    const int g = lane >> 4, i16 = lane & 15;
-    const int r0 = 32 * g + (i16 >> 1);
-    const int fx = tn8_f(r0);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) fragA[i] = lds0 + r0 * 256 + (((w1 * 8 + i) ^ fx) << 4) + 8 * (i16 & 1);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) fragB[j] = lds0 + TN_TILE_BYTES + r0 * 256 + (((w2 * 4 + j) ^ fx) << 4) + 8 * (i16 & 1);
-  }
-
-  if (nk > 0) stage(0, 0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-
-  for (int t = 0; t < nk; ++t) {
-    const unsigned cur = (unsigned)((t & 1) * BUF);
-    if (t + 1 < nk) stage(t + 1, (t + 1) & 1);
-    tn_i32x2 rb[4][4], ra[8][4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      tn8_ds_tr<0>(rb[j][0], fragB[j] + cur);
-      tn8_ds_tr<2048>(rb[j][1], fragB[j] + cur);
-      tn8_ds_tr<4096>(rb[j][2], fragB[j] + cur);
-      tn8_ds_tr<6144>(rb[j][3], fragB[j] + cur);
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      tn8_ds_tr<0>(ra[i][0], fragA[i] + cur);
-      tn8_ds_tr<2048>(ra[i][1], fragA[i] + cur);
-      tn8_ds_tr<4096>(ra[i][2], fragA[i] + cur);
-      tn8_ds_tr<6144>(ra[i][3], fragA[i] + cur);
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    i32x8 fb[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      fb[j] = i32x8{rb[j][0][0], rb[j][0][1], rb[j][1][0], rb[j][1][1], rb[j][2][0], rb[j][2][1], rb[j][3][0], rb[j][3][1]};
-    if (TN_SETPRIO == 1) __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const i32x8 fa = {ra[i][0][0], ra[i][0][1], ra[i][1][0], ra[i][1][1], ra[i][2][0], ra[i][2][1], ra[i][3][0], ra[i][3][1]};
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fb[j], fa, acc[i][j], 0, 0, 0, 0, 0, 0);
-    }
-    if (TN_SETPRIO == 1) __builtin_amdgcn_s_setprio(0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-  }
-
-  const float al = (p.alpha ? *p.alpha : 1.0f) * (p.alpha2 ? *p.alpha2 : 1.0f);
-  if (p.mode == 3) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        *(f32x4*)(p.dst + (w1 * 128 + i * 16 + (lane & 15)) * TN_T + w2 * 64 + j * 16 + 4 * (lane >> 4)) = acc[i][j] * al;
-    return;
-  }
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int n1 = c1 + w1 * 128 + i * 16 + (lane & 15);
-    if (n1 >= p.N1) continue;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int n2 = c2 + w2 * 64 + j * 16 + 4 * (lane >> 4);
-      if (n2 >= p.N2) continue;
-      float* q = p.dst + (long long)n1 * p.N2 + n2;
-      const f32x4 v = acc[i][j] * al;
-      if (p.mode == 0) {
-        *(f32x4*)q = v;
-      } else if (p.mode == 1) {
-        *(f32x4*)q = *(const f32x4*)q + v;
-      } else {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) unsafeAtomicAdd(q + r, v[r]);
-      }
-    }
-  }
-}
-
 
 // ---- ping-pong form of the e4m3 weight-gradient loop (round 4) ----------------------------------------------------------------
 // Same roles as tn_pp_unit: waves 4-7 (the n1 half w1 = 1 of the tile) run one barrier behind waves 0-3, so on every SIMD one wave is
@@ -830,7 +524,7 @@ __device__ __forceinline__ void tn8_pp_unit(const Tn8Unit& p, char* smem) {
     return __builtin_amdgcn_make_buffer_rsrc((void*)(base + row0 * ncols), 0, (int)(rows * ncols), 0x00020000);
   };
   // staging slots: 8 DMA instructions per wave and K-tile.  Group 0: the B tile, slot e = rows 32 w2 + 4 e (+ lane >> 4), chunk
-  // lane & 15 (as tn8_unit).  Group 1: slots 0-3 = A_1, slots 4-7 = A_0, rows 32 w2 + 8 (e & 3) (+ lane >> 3), position lane & 7.
+  // lane & 15.  Group 1: slots 0-3 = A_1, slots 4-7 = A_0, rows 32 w2 + 8 (e & 3) (+ lane >> 3), position lane & 7.
   unsigned voff[8];
   int ldsoff[8];
 #pragma unroll
@@ -854,17 +548,14 @@ __device__ __forceinline__ void tn8_pp_unit(const Tn8Unit& p, char* smem) {
   auto issue_b = [&](int t, int bufsel) {               // group 0
     __amdgpu_buffer_rsrc_t rs = window(p.B, p.N2, t);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) tn_dma16(rs, smem + ldsoff[e] + bufsel * BT, voff[e]);
+    for (int e = 0; e < 8; ++e) dma16_to_lds(rs, smem + ldsoff[e] + bufsel * BT, voff[e]);
   };
   auto issue_a = [&](int t, int bufsel, auto first_c) {  // group 1: slots first .. first + 3
     constexpr int first = decltype(first_c)::value;
     __amdgpu_buffer_rsrc_t rs = window(p.A, p.N1, t);
 #pragma unroll
-    for (int e = first; e < first + 4; ++e) tn_dma16(rs, smem + ldsoff[e] + bufsel * AG, voff[e]);
+    for (int e = first; e < first + 4; ++e) dma16_to_lds(rs, smem + ldsoff[e] + bufsel * AG, voff[e]);
   };
-  using I0 = std::integral_constant<int, 0>;
-  using I1 = std::integral_constant<int, 1>;
-  using I4 = std::integral_constant<int, 4>;
 
   f32x4 acc[8][4];
 #pragma unroll
@@ -883,22 +574,22 @@ __device__ __forceinline__ void tn8_pp_unit(const Tn8Unit& p, char* smem) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) fragB[j] = lds0 + B_BASE + r0 * 256 + (((w2 * 4 + j) ^ tn8_f(r0)) << 4) + 8 * (i16 & 1);
   }
-  tn_i32x2 rb[4][4], ra[8][4];
+  i32x2 rb[4][4], ra[8][4];
   auto read_frags = [&](auto buf_c) {
     constexpr int IA = decltype(buf_c)::value * AG, IB = decltype(buf_c)::value * BT;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      tn8_ds_tr<IB>(rb[j][0], fragB[j]);
-      tn8_ds_tr<IB + 2048>(rb[j][1], fragB[j]);
-      tn8_ds_tr<IB + 4096>(rb[j][2], fragB[j]);
-      tn8_ds_tr<IB + 6144>(rb[j][3], fragB[j]);
+      ds_read_tr8<IB>(rb[j][0], fragB[j]);
+      ds_read_tr8<IB + 2048>(rb[j][1], fragB[j]);
+      ds_read_tr8<IB + 4096>(rb[j][2], fragB[j]);
+      ds_read_tr8<IB + 6144>(rb[j][3], fragB[j]);
     }
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-      tn8_ds_tr<IA>(ra[i][0], fragA[i]);
-      tn8_ds_tr<IA + 1024>(ra[i][1], fragA[i]);
-      tn8_ds_tr<IA + 2048>(ra[i][2], fragA[i]);
-      tn8_ds_tr<IA + 3072>(ra[i][3], fragA[i]);
+      ds_read_tr8<IA>(ra[i][0], fragA[i]);
+      ds_read_tr8<IA + 1024>(ra[i][1], fragA[i]);
+      ds_read_tr8<IA + 2048>(ra[i][2], fragA[i]);
+      ds_read_tr8<IA + 3072>(ra[i][3], fragA[i]);
     }
   };
   auto mma = [&]() {
@@ -920,33 +611,33 @@ __device__ __forceinline__ void tn8_pp_unit(const Tn8Unit& p, char* smem) {
     if (w1 == 0) {
       issue_b(t + 1, bsel ^ 1);
     } else {
-      issue_a(t + 1, bsel ^ 1, I0{});                   // A_1(t+1)
-      issue_a(t + 2, bsel, I4{});                       // A_0(t+2)
-      tn_wait_vmcnt<8>();                               // everything older than those two: A_0(t+1) among it
+      issue_a(t + 1, bsel ^ 1, IC<0>{});                   // A_1(t+1)
+      issue_a(t + 2, bsel, IC<4>{});                       // A_0(t+2)
+      wait_vmcnt<8>();                               // everything older than those two: A_0(t+1) among it
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the reads are DONE before the barrier: the partner group refills behind it
-    tn_section();
+    raw_barrier();
     mma();
-    if (w1 == 0) tn_wait_vmcnt<0>();                    // B(t+1)
-    else tn_wait_vmcnt<4>();                            // A_1(t+1)
-    if (!skip_section) tn_section();
+    if (w1 == 0) wait_vmcnt<0>();                    // B(t+1)
+    else wait_vmcnt<4>();                            // A_1(t+1)
+    if (!skip_section) raw_barrier();
   };
 
   if (nk > 0) {
     if (w1 == 0) {
       issue_b(0, 0);
     } else {
-      issue_a(0, 0, I0{});
-      issue_a(0, 0, I4{});
-      issue_a(1, 1, I4{});
+      issue_a(0, 0, IC<0>{});
+      issue_a(0, 0, IC<4>{});
+      issue_a(1, 1, IC<4>{});
     }
-    tn_wait_vmcnt<0>();
-    tn_section();
-    if (w1 == 1) tn_section();                         // waves 4-7 run one barrier behind waves 0-3
+    wait_vmcnt<0>();
+    raw_barrier();
+    if (w1 == 1) raw_barrier();                         // waves 4-7 run one barrier behind waves 0-3
     for (int t = 0; t < nk; t += 2) {
-      ktile(I0{}, t, t + 1 == nk && w1 == 1);          // (waves 4-7 leave the stagger at the end)
+      ktile(IC<0>{}, t, t + 1 == nk && w1 == 1);          // (waves 4-7 leave the stagger at the end)
       if (t + 1 >= nk) break;
-      ktile(I1{}, t + 1, t + 2 == nk && w1 == 1);
+      ktile(IC<1>{}, t + 1, t + 2 == nk && w1 == 1);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // trailing zero-fill DMA retired before the LDS is released
   }
@@ -982,13 +673,11 @@ __device__ __forceinline__ void tn8_pp_unit(const Tn8Unit& p, char* smem) {
   }
 }
 
-template <bool PP>
 __global__ __launch_bounds__(TN_THREADS, 2) void gemm_tn_fp8_kernel(Tn8Params p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
+  // block -> (split, tile): the tiles of one split, which share the split's rows of both operands, are neighbours on one XCD
   const int ntiles = p.tiles1 * p.tiles2;
-  const int nwg = ntiles * p.splits;
-  const int xcd = blockIdx.x & 7, qq = nwg >> 3, rr = nwg & 7;
-  const int bid = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (blockIdx.x >> 3);
+  const int bid = xcd_remap(blockIdx.x, ntiles * p.splits);
   const int split = bid / ntiles;
   const int tile = bid - split * ntiles;
   const int t1 = tile / p.tiles2, t2 = tile - t1 * p.tiles2;
@@ -1010,8 +699,7 @@ __global__ __launch_bounds__(TN_THREADS, 2) void gemm_tn_fp8_kernel(Tn8Params p)
   u.mode = p.slabs ? 0 : (p.direct ? 1 : 2);
   u.alpha = p.alpha;
   u.alpha2 = p.alpha2;
-  if constexpr (PP) tn8_pp_unit(u, smem);
-  else tn8_unit(u, smem);
+  tn8_pp_unit(u, smem);
 }
 
 // several e4m3 weight gradients over the same rows in one launch (vitssl_gemm_fp8_tn_batch; see gemm_tn_batch_kernel)
@@ -1021,13 +709,11 @@ struct Tn8BatchParams {
   const float* alpha2[TN_MAX_JOBS];
 };
 
-template <bool PP>
 __global__ __launch_bounds__(TN_THREADS, 2) void gemm_tn_fp8_batch_kernel(Tn8BatchParams pp) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const TnBatchParams& p = pp.b;
   const int G = gridDim.x;
-  const int xcd = blockIdx.x & 7, qq = G >> 3, rr = G & 7;
-  const int bid = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (blockIdx.x >> 3);
+  const int bid = xcd_remap(blockIdx.x, G);
   const TnBatchWalk w = tn_batch_walk(p, bid, G);
   for (int un = w.first; un < w.end; un += w.step) {
     Tn8Unit u;
@@ -1042,8 +728,7 @@ __global__ __launch_bounds__(TN_THREADS, 2) void gemm_tn_fp8_batch_kernel(Tn8Bat
     u.mode = p.slots ? 3 : 1;
     u.alpha = pp.alpha[j];
     u.alpha2 = pp.alpha2[j];
-    if constexpr (PP) tn8_pp_unit(u, smem);
-    else tn8_unit(u, smem);
+    tn8_pp_unit(u, smem);
     __syncthreads();                                   // every wave is done with the LDS before the next unit's first DMA
   }
 }
@@ -1055,6 +740,16 @@ __global__ void tn_reduce_kernel(float* __restrict__ C, const float* __restrict_
     for (int s = 0; s < splits; ++s) a += *(const f32x4*)(slabs + s * stride + 4 * i);
     *(f32x4*)(C + 4 * i) = a;
   }
+}
+
+// the reduce pass of a single-launch weight gradient: C += the sum of its `splits` slabs
+int tn_reduce_slabs(float* C, const float* slabs, int N1, int N2, int splits, hipStream_t s, const char* who) {
+  const long long n4 = (long long)N1 * N2 / 4;
+  long long grid = (n4 + 255) / 256;
+  if (grid > 2048) grid = 2048;
+  hipLaunchKernelGGL(tn_reduce_kernel, dim3((unsigned)grid), dim3(256), 0, s, C, slabs, n4, (long long)N1 * N2, splits);
+  VS_CHECK_LAUNCH(who);
+  return VITSSL_OK;
 }
 
 void tn_plan(long long M, int N1, int N2, int* tiles1, int* tiles2, int* splits, int* chunks_per_split, int km = TN_KM) {
@@ -1102,32 +797,11 @@ extern "C" int vitssl_gemm_bf16_tn(const void* A, const void* B, float* C, int64
   p.direct = p.splits == 1;
   if (p.direct) p.slabs = nullptr;
   static VsOnce attr_done{false};
-  static VsEnvInt pp_env;                              // VITSSL_TN_PP=0: the two-phase loop (developer knob; tests/test_gpu_knobs.py)
-  const int use_pp = pp_env.get("VITSSL_TN_PP", 1);
-  if (!attr_done.load(std::memory_order_relaxed)) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_tn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute((const void*)gemm_tn_pp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES);
-    if (e != hipSuccess) {
-      vitssl_set_error("gemm_tn: cannot raise dynamic LDS: %s", hipGetErrorString(e));
-      return VITSSL_ERR_LAUNCH;
-    }
-    attr_done.store(true, std::memory_order_relaxed);
-  }
+  if (int rc = ensure_lds(gemm_tn_pp_kernel, TN_LDS_BYTES, attr_done, "gemm_tn")) return rc;
   hipStream_t s = (hipStream_t)stream;
-  if (use_pp)
-    hipLaunchKernelGGL(gemm_tn_pp_kernel, dim3(p.tiles1 * p.tiles2 * p.splits), dim3(TN_THREADS), TN_LDS_BYTES, s, p);
-  else
-    hipLaunchKernelGGL(gemm_tn_kernel, dim3(p.tiles1 * p.tiles2 * p.splits), dim3(TN_THREADS), TN_LDS_BYTES, s, p);
+  hipLaunchKernelGGL(gemm_tn_pp_kernel, dim3(p.tiles1 * p.tiles2 * p.splits), dim3(TN_THREADS), TN_LDS_BYTES, s, p);
   VS_CHECK_LAUNCH("gemm_tn");
-  if (p.slabs) {
-    const long long n4 = (long long)N1 * N2 / 4;
-    long long grid = (n4 + 255) / 256;
-    if (grid > 2048) grid = 2048;
-    hipLaunchKernelGGL(tn_reduce_kernel, dim3((unsigned)grid), dim3(256), 0, s, C, p.slabs, n4, (long long)N1 * N2, p.splits);
-    VS_CHECK_LAUNCH("gemm_tn_reduce");
-  }
-  return VITSSL_OK;
+  return p.slabs ? tn_reduce_slabs(C, p.slabs, N1, N2, p.splits, s, "gemm_tn_reduce") : VITSSL_OK;
 }
 
 // ---- batch of weight gradients over the same M rows
@@ -1245,14 +919,7 @@ extern "C" int vitssl_gemm_bf16_tn_batch(const vitssl_tn_job_t* jobs, int njobs,
                "changes with vitssl_set_reserved_cus: query again after changing the reserve)", need, cus);
   p.slots = need ? workspace : nullptr;
   static VsOnce attr_done{false};
-  if (!attr_done.load(std::memory_order_relaxed)) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_tn_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES);
-    if (e != hipSuccess) {
-      vitssl_set_error("gemm_tn_batch: cannot raise dynamic LDS: %s", hipGetErrorString(e));
-      return VITSSL_ERR_LAUNCH;
-    }
-    attr_done.store(true, std::memory_order_relaxed);
-  }
+  if (int rc = ensure_lds(gemm_tn_batch_kernel, TN_LDS_BYTES, attr_done, "gemm_tn_batch")) return rc;
   hipStream_t s = (hipStream_t)stream;
   const long long units = (long long)T * p.splits;
   const unsigned grid = (unsigned)((units < cus && p.rem_chunks == 0) ? units : cus);      // (with a remainder range every CU has work)
@@ -1263,13 +930,6 @@ extern "C" int vitssl_gemm_bf16_tn_batch(const vitssl_tn_job_t* jobs, int njobs,
     VS_CHECK_LAUNCH("gemm_tn_batch_reduce");
   }
   return VITSSL_OK;
-}
-
-// 1 (default): the e4m3 weight gradients run the ping-pong loop (tn8_pp_unit); 0: all eight waves in step (tn8_unit)
-// (VITSSL_TN8_PP, developer knob; tests/test_gpu_knobs.py)
-static int tn8_pp_enabled() {
-  static VsEnvInt knob;
-  return knob.get("VITSSL_TN8_PP", 1);
 }
 
 extern "C" int64_t vitssl_gemm_fp8_tn_workspace_floats(int64_t M, int N1, int N2) {
@@ -1302,30 +962,11 @@ extern "C" int vitssl_gemm_fp8_tn(const void* A8, const void* B8, float* C, int6
   p.direct = p.splits == 1;
   if (p.direct) p.slabs = nullptr;
   static VsOnce attr_done{false};
-  if (!attr_done.load(std::memory_order_relaxed)) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_tn_fp8_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute((const void*)gemm_tn_fp8_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES);
-    if (e != hipSuccess) {
-      vitssl_set_error("gemm_fp8_tn: cannot raise dynamic LDS: %s", hipGetErrorString(e));
-      return VITSSL_ERR_LAUNCH;
-    }
-    attr_done.store(true, std::memory_order_relaxed);
-  }
+  if (int rc = ensure_lds(gemm_tn_fp8_kernel, TN_LDS_BYTES, attr_done, "gemm_fp8_tn")) return rc;
   hipStream_t s = (hipStream_t)stream;
-  if (tn8_pp_enabled())
-    hipLaunchKernelGGL(gemm_tn_fp8_kernel<true>, dim3(p.tiles1 * p.tiles2 * p.splits), dim3(TN_THREADS), TN_LDS_BYTES, s, p);
-  else
-    hipLaunchKernelGGL(gemm_tn_fp8_kernel<false>, dim3(p.tiles1 * p.tiles2 * p.splits), dim3(TN_THREADS), TN_LDS_BYTES, s, p);
+  hipLaunchKernelGGL(gemm_tn_fp8_kernel, dim3(p.tiles1 * p.tiles2 * p.splits), dim3(TN_THREADS), TN_LDS_BYTES, s, p);
   VS_CHECK_LAUNCH("gemm_fp8_tn");
-  if (p.slabs) {
-    const long long n4 = (long long)N1 * N2 / 4;
-    long long grid = (n4 + 255) / 256;
-    if (grid > 2048) grid = 2048;
-    hipLaunchKernelGGL(tn_reduce_kernel, dim3((unsigned)grid), dim3(256), 0, s, C, p.slabs, n4, (long long)N1 * N2, p.splits);
-    VS_CHECK_LAUNCH("gemm_fp8_tn_reduce");
-  }
-  return VITSSL_OK;
+  return p.slabs ? tn_reduce_slabs(C, p.slabs, N1, N2, p.splits, s, "gemm_fp8_tn_reduce") : VITSSL_OK;
 }
 
 namespace {
@@ -1384,23 +1025,11 @@ extern "C" int vitssl_gemm_fp8_tn_batch(const vitssl_fp8_tn_job_t* jobs, int njo
                "gemm_fp8_tn_batch: workspace of %lld floats needed (vitssl_gemm_fp8_tn_batch_workspace_floats)", need);
   p.slots = need ? workspace : nullptr;
   static VsOnce attr_done{false};
-  if (!attr_done.load(std::memory_order_relaxed)) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_tn_fp8_batch_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute((const void*)gemm_tn_fp8_batch_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES);
-    if (e != hipSuccess) {
-      vitssl_set_error("gemm_fp8_tn_batch: cannot raise dynamic LDS: %s", hipGetErrorString(e));
-      return VITSSL_ERR_LAUNCH;
-    }
-    attr_done.store(true, std::memory_order_relaxed);
-  }
+  if (int rc = ensure_lds(gemm_tn_fp8_batch_kernel, TN_LDS_BYTES, attr_done, "gemm_fp8_tn_batch")) return rc;
   hipStream_t s = (hipStream_t)stream;
   const long long units = (long long)T * p.splits;
   const unsigned grid = (unsigned)((units < cus && p.rem_chunks == 0) ? units : cus);
-  if (tn8_pp_enabled())
-    hipLaunchKernelGGL(gemm_tn_fp8_batch_kernel<true>, dim3(grid), dim3(TN_THREADS), TN_LDS_BYTES, s, pp);
-  else
-    hipLaunchKernelGGL(gemm_tn_fp8_batch_kernel<false>, dim3(grid), dim3(TN_THREADS), TN_LDS_BYTES, s, pp);
+  hipLaunchKernelGGL(gemm_tn_fp8_batch_kernel, dim3(grid), dim3(TN_THREADS), TN_LDS_BYTES, s, pp);
   VS_CHECK_LAUNCH("gemm_fp8_tn_batch");
   if (p.slots) {
     hipLaunchKernelGGL(tn_batch_reduce_kernel, dim3((unsigned)T * 8u), dim3(256), 0, s, p);

@@ -16,29 +16,6 @@ namespace {
 
 constexpr int LN_THREADS = 256;  // 4 waves = 4 rows in flight per block
 
-// 1: the residual-branch gradient of a row is requested together with dy and x (one memory round trip per row
-// instead of two: the second used to start only after the two wave reductions)
-#ifndef LN_HOIST_GRES
-#define LN_HOIST_GRES 1
-#endif
-// 1: backward requests the NEXT row's dy / x / residual gradient before it reduces the current row (the loads fly
-// under the two wave reductions and the stores); costs 7.5 V registers per lane
-#ifndef LN_PREFETCH
-#define LN_PREFETCH 1
-#endif
-#ifndef LN_FWD_PREFETCH
-#define LN_FWD_PREFETCH 1
-#endif
-// 1: forward stores 16 bytes per lane (adjacent lanes trade their v = 0 / v = 1 pieces with a DPP quad
-// swap, so an even lane writes 8 consecutive columns of the first 256, an odd lane of the second 256)
-#ifndef LN_FWD_PAIR
-#define LN_FWD_PAIR 0
-#endif
-// 1: the backward processes rows of 384 columns two per wave (ln_bwd_kernel's PAIR form); 0: one row per wave (A/B builds)
-#ifndef LN_ROW_PAIRS
-#define LN_ROW_PAIRS 1
-#endif
-
 // Q8: also emit the e4m3 image of the output (fp8 operand path, unit scale)
 template <int V, bool Q8 = false>
 __global__ __launch_bounds__(LN_THREADS) void ln_fwd_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
@@ -59,9 +36,9 @@ __global__ __launch_bounds__(LN_THREADS) void ln_fwd_kernel(const float* __restr
   }
   const float inv = 1.0f / (float)cols;
   const long long row_step = (long long)gridDim.x * 4;
-  f32x4 nxt[V];
+  f32x4 nxt[V];                                   // the next row of this wave, requested before the current one is reduced
   auto fetch = [&](long long row) {
-    if (!LN_FWD_PREFETCH || row >= rows) return;
+    if (row >= rows) return;
 #pragma unroll
     for (int v = 0; v < V; ++v) {
       const int c4 = lane + 64 * v;
@@ -70,14 +47,13 @@ __global__ __launch_bounds__(LN_THREADS) void ln_fwd_kernel(const float* __restr
   };
   fetch((long long)blockIdx.x * 4 + wave);
   for (long long row = (long long)blockIdx.x * 4 + wave; row < rows; row += row_step) {
-    const float* xr = x + row * cols;
     f32x4 xv[V];
     float s = 0.f;
 #pragma unroll
     for (int v = 0; v < V; ++v) {
       const int c4 = lane + 64 * v;
       if (c4 < c4n) {
-        xv[v] = LN_FWD_PREFETCH ? nxt[v] : *(const f32x4*)(xr + 4 * c4);
+        xv[v] = nxt[v];
         s += xv[v][0] + xv[v][1] + xv[v][2] + xv[v][3];
       }
     }
@@ -98,25 +74,6 @@ __global__ __launch_bounds__(LN_THREADS) void ln_fwd_kernel(const float* __restr
       rstd[row] = rs;
     }
     bf16_t* yr = y + row * cols;
-    if (LN_FWD_PAIR && !Q8 && V >= 2 && c4n == 64 * V) {
-      u32x2 w[V];
-#pragma unroll
-      for (int v = 0; v < V; ++v) {
-        const f32x4 o = xv[v] * rs * g[v] + b[v];
-        w[v] = u32x2{pack_bf2(o[0], o[1]), pack_bf2(o[2], o[3])};
-      }
-      const bool odd = lane & 1;
-#pragma unroll
-      for (int v = 0; v + 1 < V; v += 2) {
-        const u32x2 t = odd ? w[v] : w[v + 1];                        // what the partner lane needs
-        const u32x2 r = {(unsigned)__builtin_amdgcn_update_dpp(0, (int)t[0], 0xB1, 0xF, 0xF, false),
-                         (unsigned)__builtin_amdgcn_update_dpp(0, (int)t[1], 0xB1, 0xF, 0xF, false)};   // quad_perm [1,0,3,2]
-        const u32x4 q = odd ? u32x4{r[0], r[1], w[v + 1][0], w[v + 1][1]} : u32x4{w[v][0], w[v][1], r[0], r[1]};
-        *(u32x4*)(yr + 256 * (v + (odd ? 1 : 0)) + 4 * (lane - (odd ? 1 : 0))) = q;
-      }
-      if (V & 1) *(u32x2*)(yr + 4 * (lane + 64 * (V - 1))) = w[V - 1];
-      continue;
-    }
 #pragma unroll
     for (int v = 0; v < V; ++v) {
       const int c4 = lane + 64 * v;
@@ -136,7 +93,7 @@ __global__ __launch_bounds__(LN_THREADS) void ln_fwd_kernel(const float* __restr
 // spills, fewer resident waves win (MI355X, interleaved A/B, M = 50176, D = 768: with column sums + dropout
 // 134 us without prefetch, 154 at 3 workgroups (spills), 125 at 2; without column sums 132 -> 118 at 3)
 constexpr int ln_bwd_blocks(int V, bool has_ln, bool has_cs) {
-  if (!(LN_PREFETCH && has_ln)) return (V <= 2 || (V == 3 && !has_cs)) ? 4 : (V <= 4 ? 3 : 1);
+  if (!has_ln) return (V <= 2 || (V == 3 && !has_cs)) ? 4 : (V <= 4 ? 3 : 1);
   return V <= 1 ? 4 : (V == 2 ? (has_cs ? 3 : 4) : (V == 3 ? (has_cs ? 2 : 3) : (V == 4 ? 2 : 1)));
 }
 
@@ -162,7 +119,7 @@ __global__ __launch_bounds__(LN_THREADS, ln_bwd_blocks(V, HAS_LN, HAS_CS)) void 
   const int wave = threadIdx.x >> 6;
   const int c4n = cols >> 2;
   const int c4h = PAIR ? c4n >> 1 : c4n;            // float4 per row
-  static_assert(!PAIR || (HAS_LN && LN_PREFETCH && !Q8), "row pairs are built for the prefetching LayerNorm form, bf16 image");
+  static_assert(!PAIR || (HAS_LN && !Q8), "row pairs are built for the LayerNorm form with a bf16 image");
   f32x4 g[V], acc_dg[V], acc_db[V], acc_cs[V];
   bool hi[V];                                       // PAIR: the slot holds columns of the pair's second row
 #pragma unroll
@@ -182,7 +139,7 @@ __global__ __launch_bounds__(LN_THREADS, ln_bwd_blocks(V, HAS_LN, HAS_CS)) void 
   u32x2 ndy[V];
   float nmu = 0.f, nrs = 0.f, nmuB = 0.f, nrsB = 0.f;
   auto fetch = [&](long long row) {
-    if (!(HAS_LN && LN_PREFETCH) || row >= rows) return;
+    if (!HAS_LN || row >= rows) return;
     if constexpr (PAIR) {
       nmu = mean[2 * row];
       nrs = rstd[2 * row];
@@ -206,7 +163,7 @@ __global__ __launch_bounds__(LN_THREADS, ln_bwd_blocks(V, HAS_LN, HAS_CS)) void 
   fetch((long long)blockIdx.x * 4 + wave);
   for (long long row = (long long)blockIdx.x * 4 + wave; row < rows; row += row_step) {
     f32x4 dx[V];
-    if constexpr (HAS_LN && LN_PREFETCH) {
+    if constexpr (HAS_LN) {
       const float mu = nmu, rs = nrs, muB = nmuB, rsB = nrsB;
       f32x4 xh[V], gr[V];
       u32x2 dyp[V];
@@ -250,40 +207,6 @@ __global__ __launch_bounds__(LN_THREADS, ln_bwd_blocks(V, HAS_LN, HAS_CS)) void 
           const f32x4 d = {bf_lo(dyp[v][0]), bf_hi(dyp[v][0]), bf_lo(dyp[v][1]), bf_hi(dyp[v][1])};
           dx[v] = (d * g[v] - (hi[v] ? m1B : m1) - xh[v] * (hi[v] ? m2B : m2)) * (hi[v] ? rsB : rs);
           if (g_res) dx[v] += gr[v];
-          *(f32x4*)(g_out + row * cols + 4 * c4) = dx[v];
-        }
-      }
-    } else if constexpr (HAS_LN) {
-      const float mu = mean[row], rs = rstd[row];
-      f32x4 xh[V];
-      f32x4 gr[V];
-      u32x2 dyp[V];   // dy kept packed (bf16) between the two passes: fewer live registers
-      float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-      for (int v = 0; v < V; ++v) {
-        const int c4 = lane + 64 * v;
-        if (c4 < c4n) {
-          if (LN_HOIST_GRES && g_res) gr[v] = *(const f32x4*)(g_res + row * cols + 4 * c4);
-          dyp[v] = *(const u32x2*)(dy + row * cols + 4 * c4);
-          const f32x4 d = {bf_lo(dyp[v][0]), bf_hi(dyp[v][0]), bf_lo(dyp[v][1]), bf_hi(dyp[v][1])};
-          xh[v] = (*(const f32x4*)(x + row * cols + 4 * c4) - mu) * rs;
-          const f32x4 dyg = d * g[v];
-          acc_dg[v] += d * xh[v];
-          acc_db[v] += d;
-          s1 += dyg[0] + dyg[1] + dyg[2] + dyg[3];
-          const f32x4 t = dyg * xh[v];
-          s2 += t[0] + t[1] + t[2] + t[3];
-        }
-      }
-      const float m1 = wave_sum(s1) * inv;
-      const float m2 = wave_sum(s2) * inv;
-#pragma unroll
-      for (int v = 0; v < V; ++v) {
-        const int c4 = lane + 64 * v;
-        if (c4 < c4n) {
-          const f32x4 d = {bf_lo(dyp[v][0]), bf_hi(dyp[v][0]), bf_lo(dyp[v][1]), bf_hi(dyp[v][1])};
-          dx[v] = (d * g[v] - m1 - xh[v] * m2) * rs;
-          if (g_res) dx[v] += LN_HOIST_GRES ? gr[v] : *(const f32x4*)(g_res + row * cols + 4 * c4);
           *(f32x4*)(g_out + row * cols + 4 * c4) = dx[v];
         }
       }
@@ -362,16 +285,10 @@ __global__ __launch_bounds__(LN_THREADS, ln_bwd_blocks(V, HAS_LN, HAS_CS)) void 
 // A/B against the former cap of 2048: M = 50176, D = 768: 123 -> 110 us, with column sums 126 -> 111; D = 1024,
 // M = 25088: 89 -> 75; D = 384: 79 -> 58; DINO local crops, M = 18944, D = 768: 65 -> 37).  Forward has no such tail:
 // 4096 blocks give 43.5-43.6 ms per ViT-B step against 43.8 with 2048 (uncapped: 43.7).
-#ifndef LN_BWD_GRID_CAP
-#define LN_BWD_GRID_CAP 0     // 0 = the rule above; a positive value forces the cap (developer A/B builds)
-#endif
+constexpr long long LN_FWD_GRID_CAP = 4096;
 inline int ln_grid(long long rows, bool fwd = false, int cols = 1024) {
   long long g = (rows + 3) / 4;
-#ifndef LN_FWD_GRID_CAP
-#define LN_FWD_GRID_CAP 4096
-#endif
   long long cap = fwd ? LN_FWD_GRID_CAP : (long long)vitssl_persistent_cus() * (cols <= 512 ? 2 : 1);
-  if (!fwd && LN_BWD_GRID_CAP > 0) cap = LN_BWD_GRID_CAP;
   if (g > cap) g = cap;
   if (g < 1) g = 1;
   return (int)g;
@@ -386,7 +303,7 @@ int launch_ln_bwd_parts(const void* dy, const float* x, const float* mean, const
   const int on = dk.thr != 0;
   VS_CHECK_ARG(!on || (unsigned long long)rows * (unsigned long long)cols < (1ull << 34),
                "layernorm_bwd / grad_mask_cast: the dropout stream's group counter is 32 bits (rows * cols < 2^34)");
-  if constexpr (HAS_LN && !Q8 && LN_PREFETCH && LN_ROW_PAIRS) {
+  if constexpr (HAS_LN && !Q8) {
     if (cols == 384 && (rows & 1) == 0) {            // two rows per wave (PAIR)
       const int pgrid = ln_grid(rows / 2, false, 768);
       if (gm_colsum)
@@ -430,7 +347,7 @@ int launch_ln_bwd(const void* dy, const float* x, const float* mean, const float
                   const float* g_res, float* g_out, void* gm, float* dgamma, float* dbeta, float* gm_colsum,
                   vitssl_dropout_t drop, int64_t rows, int cols, float* workspace, int64_t workspace_floats, hipStream_t s,
                   void* gm8 = nullptr, const float* qscale = nullptr, float* qamax = nullptr) {
-  const bool pair = HAS_LN && !Q8 && LN_PREFETCH && LN_ROW_PAIRS && cols == 384 && (rows & 1) == 0;
+  const bool pair = HAS_LN && !Q8 && cols == 384 && (rows & 1) == 0;
   const int grid = pair ? ln_grid(rows / 2, false, 768) : ln_grid(rows, false, cols);
   const long long slab = (long long)grid * cols;
   if (!((HAS_LN && (dgamma || dbeta)) || gm_colsum))
