@@ -451,3 +451,14 @@ def test_bench_dump_outputs_writes_a_fixed_sample_under_the_cap(tmp_path, monkey
     assert b.dtype == np.float32 and b.shape == (1000,) and np.all(np.diff(b) >= 0) and len(np.unique(b)) > 800
     for k in arrays:
         assert np.array_equal(got[k], np.load(tmp_path / "b" / f"{k}.npy")), k
+
+
+def test_fuzz_slice_out_of_time_is_not_a_pass(capsys):
+    """tools/fuzz_ops.run with a case count: a time budget that runs out first (here: before the first case) is a failure,
+    so the deterministic slices of tests/test_gpu_fuzz.py cannot pass on a few of their cases"""
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+    import fuzz_ops
+    assert fuzz_ops.run(seed=1, kinds="ln", budget_s=0.0, max_cases=3) != 0
+    assert "after 0 of 3 cases" in capsys.readouterr().out
+    assert fuzz_ops.run(seed=1, kinds="ln", budget_s=0.0) == 0        # a time-bounded sweep without a count

@@ -246,7 +246,8 @@ def dino_case(_ops, B, gi, li, patch, D, H, F, K, G, Lv):
 
 def run(seed=0, kinds="nt,nt,tn,attn,ln,nt8,tn8,tnb", budget_s=120.0, max_cases=None):
     """Returns 0, or 1 after printing the first failing case.  `max_cases` bounds the sweep by count (a deterministic list of
-    cases for a given seed: tests/test_gpu_fuzz.py), `budget_s` by time."""
+    cases for a given seed: tests/test_gpu_fuzz.py), `budget_s` by time; when `max_cases` is given, running out of time before
+    reaching it returns 2 (a slice that ran few or none of its later cases is not a pass)."""
     rng = random.Random(int(seed))
     budget = float(budget_s)
     t0 = time.time()
@@ -320,9 +321,12 @@ def run(seed=0, kinds="nt,nt,tn,attn,ln,nt8,tn8,tnb", budget_s=120.0, max_cases=
         n += 1
         if n % 10 == 0:
             print(f"{n} cases ok ({time.time() - t0:.0f} s); last: {kind}{args}", flush=True)
-    print(f"all {n} cases ok: " + " ".join(f"{k}{a}" for k, a in cases[-12:]))
+    print(f"all {n} cases ok ({time.time() - t0:.0f} s): " + " ".join(f"{k}{a}" for k, a in cases[-12:]))
     for kind, (err, name, case) in sorted(WORST.items()):
         print(f"  largest gradient distance of the sweep, {kind}: {err:.4f} ({name}, {kind}{case})")
+    if max_cases is not None and n < max_cases:
+        print(f"INCOMPLETE: the time budget of {budget:.0f} s ran out after {n} of {max_cases} cases", flush=True)
+        return 2
     return 0
 
 
