@@ -152,7 +152,7 @@ typedef struct {
 } vitssl_fp8_gemm_t;
 int vitssl_gemm_fp8_nt(const vitssl_gemm_t* g, const vitssl_fp8_gemm_t* q, void* stream);
 
-/* vitssl_attn_fwd that also writes the e4m3 image of `out` (made from the fp32 values before the bf16 store) */
+/* vitssl_attn_fwd that also writes the e4m3 image of `out` (made from the fp32 values before the bf16 store); N <= 256 */
 int vitssl_attn_fwd_fp8(const void* qkv, void* out, void* out_fp8, float* lse, float* probs, int B, int N, int H, int dh,
                         void* stream);
 /* Weight gradient on e4m3 operands: C[N1,N2] (fp32) += alpha * alpha2 * A8[M,N1]^T . B8[M,N2]  (dY scaled image x the
@@ -238,12 +238,17 @@ int vitssl_gemm_fp8_tn_batch(const vitssl_fp8_tn_job_t* jobs, int njobs, int64_t
  * out  bf16 [B, N, H*dh]      (heads merged, ready for final_linear)
  * lse  f32  [B, H, N]         (log-sum-exp of the scaled scores, saved for backward)
  * probs f32 [B, H, N, N] or NULL (return_attn=True path)
- * dh = 64 (every ViT family of BASELINE.json), N <= 256; other geometries return VITSSL_ERR_ARG;
- * scale = 1/sqrt(dh). */
+ * dh = 64 (every ViT family of BASELINE.json), N <= 2048; other geometries return VITSSL_ERR_ARG;
+ * scale = 1/sqrt(dh).
+ * N <= 256: one workgroup per (image, head), keys and values resident in LDS.  257 <= N <= 2048 (patch 8, 384 / 512-pixel
+ * images): streaming kernels, one workgroup per (image, head, 128 queries), online softmax; `probs` is then written by a
+ * second launch from `lse`, so `out` is the same bits with and without it.  Same layouts, same tolerances, deterministic.
+ * The _fp8 entry points above (e4m3 images of out / dqkv) stop at N <= 256: run longer sequences with bf16 operands. */
 int vitssl_attn_fwd(const void* qkv, void* out, float* lse, float* probs, int B, int N, int H, int dh,
                     void* stream);
-/* delta_ws: f32 [B,H,N] scratch for rowsum(dO*O) (used by the two-launch variant only; the default
- * one-launch backward keeps delta in LDS); dqkv bf16 [B,N,3,H,dh] fully overwritten. */
+/* delta_ws: f32 [B,H,N] scratch for rowsum(dO*O): required for N > 256, where the backward is three launches (delta;
+ * dK / dV per key tile; dQ per query tile: no atomics, no other workspace); the one-launch backward of N <= 256 keeps
+ * delta in LDS and ignores it.  dqkv bf16 [B,N,3,H,dh] fully overwritten. */
 int vitssl_attn_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv,
                     float* delta_ws, int B, int N, int H, int dh, void* stream);
 

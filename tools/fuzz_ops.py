@@ -3,7 +3,7 @@
 shapes the parametrised lists do not name -- ragged M / N, every N % 8 / N % 4 residue class the entry points accept,
 token counts 1..256 -- and prints the first failing shape.
 
-    SEED=1 BUDGET_S=150 [KINDS=nt,tn,attn,ln,nt8,tn8,tnb,simmim,vit,dino] [CASES=n] python tools/fuzz_ops.py
+    SEED=1 BUDGET_S=150 [KINDS=nt,tn,attn,attnlong,ln,nt8,tn8,tnb,simmim,vit,dino] [CASES=n] python tools/fuzz_ops.py
 (exit code 1 on the first failure)"""
 import contextlib
 import os
@@ -307,6 +307,9 @@ def run(seed=0, kinds="nt,nt,tn,attn,ln,nt8,tn8,tnb", budget_s=120.0, max_cases=
             fn = dino_case
         elif kind == "attn":
             args = (rng.randint(1, 256),)
+            fn = T.test_attention_fwd_bwd
+        elif kind == "attnlong":                             # the streaming kernels (csrc/attention_long.hip); not in the default kinds
+            args = (rng.randint(257, 1100),)
             fn = T.test_attention_fwd_bwd
         else:                                                # a quarter of the cases on the row-pair backward (384 columns, even row count)
             args = (2 * rng.randint(1, 3000), 384) if rng.random() < 0.25 else (rng.randint(1, 2000), 4 * rng.randint(1, 512))

@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
 """Median time of the attention forward / backward launches at one geometry (developer tool; compare builds or
-VITSSL_ATTN_STAGGER_* settings by running it in alternation).   B H N as arguments, default 256 12 196."""
+VITSSL_ATTN_STAGGER_* settings by running it in alternation), next to the reference formulation on the same tensors:
+softmax(q @ k^T / 8) @ v in bf16 through torch (vit_core/attention.py:20-23 of the reference), forward and forward + backward.
+The two implementations alternate round by round in one process; medians and the min - max spread of the rounds are printed.
+B H N as arguments, default 256 12 196."""
 import os
 import sys
 
@@ -21,24 +24,67 @@ dqkv = torch.empty_like(qkv)
 delta = torch.empty(B, H, N, device=dev)
 
 
-def timeit(fn, rounds=15, iters=4):
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(rounds):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(iters):
+# the reference formulation's operands: the same values as [B, H, N, 64] tensors (contiguous, as its Linear + transpose leave them)
+x5 = qkv.view(B, N, 3, H, 64)
+q_r, k_r, v_r = (x5[:, :, i].transpose(1, 2).contiguous().requires_grad_(True) for i in range(3))
+do_r = dout.view(B, N, H, 64).transpose(1, 2).contiguous()
+
+
+def ref_fwd():
+    with torch.no_grad():
+        return torch.matmul(torch.softmax(torch.matmul(q_r, k_r.transpose(-2, -1)) / 8.0, dim=-1), v_r)
+
+
+def ref_fwd_bwd():
+    o = torch.matmul(torch.softmax(torch.matmul(q_r, k_r.transpose(-2, -1)) / 8.0, dim=-1), v_r)
+    torch.autograd.grad(o, (q_r, k_r, v_r), do_r)
+
+
+def ours_fwd():
+    ops.attn_fwd(qkv, out, lse, B, N, H, 64)
+
+
+def ours_fwd_bwd():
+    ops.attn_fwd(qkv, out, lse, B, N, H, 64)
+    ops.attn_bwd(qkv, out, dout, lse, dqkv, delta, B, N, H, 64)
+
+
+def ours_bwd():
+    ops.attn_bwd(qkv, out, dout, lse, dqkv, delta, B, N, H, 64)
+
+
+def time_alternating(fns, rounds=15, iters=4):
+    """fns: name -> callable; every round times each of them once, in turn.  Returns name -> sorted round times (us per call)."""
+    for fn in fns.values():
+        for _ in range(3):
             fn()
-        e1.record()
-        torch.cuda.synchronize()
-        ts.append(e0.elapsed_time(e1) / iters * 1e3)
-    ts.sort()
-    return ts[len(ts) // 2]
+    torch.cuda.synchronize()
+    ts = {k: [] for k in fns}
+    for _ in range(rounds):
+        for k, fn in fns.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(iters):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ts[k].append(e0.elapsed_time(e1) / iters * 1e3)
+    return {k: sorted(v) for k, v in ts.items()}
 
 
-f = timeit(lambda: ops.attn_fwd(qkv, out, lse, B, N, H, 64))
-b = timeit(lambda: ops.attn_bwd(qkv, out, dout, lse, dqkv, delta, B, N, H, 64))
+def med(v):
+    return v[len(v) // 2]
+
+
+with_ref = "--no-ref" not in sys.argv
+fns = {"fwd": ours_fwd, "bwd": ours_bwd, "fwd+bwd": ours_fwd_bwd}
+if with_ref:
+    fns.update({"ref fwd": ref_fwd, "ref fwd+bwd": ref_fwd_bwd})
+ts = time_alternating(fns)
 fl = 4.0 * B * H * N * N * 64
-print(f"B{B} H{H} N{N}: fwd {f:7.1f} us {fl / f / 1e6:6.1f} TF/s | bwd {b:7.1f} us {2.5 * fl / b / 1e6:6.1f} TF/s", flush=True)
+f, b = med(ts["fwd"]), med(ts["bwd"])
+print(f"B{B} H{H} N{N}: fwd {f:7.1f} us {fl / f / 1e6:6.1f} TF/s | bwd {b:7.1f} us {2.0 * fl / b / 1e6:6.1f} TF/s", flush=True)
+for k, v in ts.items():
+    print(f"  {k:12s} median {med(v):9.1f} us   min {v[0]:9.1f}   max {v[-1]:9.1f}", flush=True)
+if with_ref:
+    print(f"  reference / ours: fwd {med(ts['ref fwd']) / f:5.2f}x   fwd+bwd {med(ts['ref fwd+bwd']) / med(ts['fwd+bwd']):5.2f}x", flush=True)

@@ -49,6 +49,7 @@ class BackboneRuntime:
             raise L.VitsslError(f"patch embedding built for a {self.grid} grid got {gh}x{gw}")
         tokens = gh * gw
         T = tokens + 1
+        self.stack.check_tokens(T)
         dev = x.device
         pos, pos_graph = self.pos_for(gh, gw, need_grad=save)
         # a forward that saves nothing (no_grad / eval) must not touch the buffers a pending

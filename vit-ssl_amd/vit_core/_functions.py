@@ -364,6 +364,7 @@ class _StackFn(Function):
     @staticmethod
     def forward(ctx, runner, x, training, return_attn, need, *params):
         Bn, T, D = x.shape
+        runner.stack.check_tokens(T)
         st = runner.store
         st.refresh_weights()
         seed = R.next_seed() if (training and runner.stack.p > 0) else 0

@@ -103,6 +103,7 @@ class _SimMIMRuntime:
         st, ws = self.store, self.ws
         if x.dim() != 4 or tuple(x.shape[1:]) != (self.C, self.H, self.W):
             raise L.VitsslError(f"SimMIMViT: expected input [B,{self.C},{self.H},{self.W}], got {tuple(x.shape)}")
+        self.stack.check_tokens(self.N)
         x = R.as_f32(x)
         B = x.shape[0]
         M = B * self.N
@@ -251,6 +252,7 @@ class SimMIMViT(nn.Module):
         self.eval()
         R.require_gpu(x, "SimMIMViT")
         rt = self.runtime(x.device)
+        rt.stack.check_tokens(rt.N)
         rt.store.refresh_weights()
         x = R.as_f32(x)
         B = x.shape[0]

@@ -27,6 +27,8 @@ BF16 = torch.bfloat16
 F32 = torch.float32
 FP8 = ops.FP8
 ALIGN = 64  # elements; keeps every parameter 256-byte aligned inside the flat buffer
+MAX_TOKENS = 2048       # attention: streaming kernels for 257-2048 tokens (bf16 operands), csrc/attention_long.hip
+FP8_MAX_TOKENS = 256    # the fp8 attention entry points (e4m3 images of out / dqkv) end where the one-workgroup-per-head kernels do
 
 # Operand type of the FORWARD Linear products inside the encoder blocks: "bf16" (default, the reference's
 # autocast contract) or "fp8" (OCP e4m3, BASELINE.json configs[4]; backward products stay bf16).  Read when an
@@ -433,11 +435,22 @@ class EncoderStack:
             return ops.NO_DROP
         return ops.make_dropout(self.p, seed, self.site_base + 3 * i + which)
 
+    def check_tokens(self, T: int):
+        """Refuse a sequence length the attention kernels of this operand mode do not cover.  Models call it at the top of
+        their forward, before the first kernel of the step; forward() below repeats it for lone blocks."""
+        if self.fp8 and T > FP8_MAX_TOKENS:
+            raise L.VitsslError(f"fp8 linear operands support sequences of up to {FP8_MAX_TOKENS} tokens, got {T}: use bf16 "
+                                f"operands (set_linear_operands('bf16') or VITSSL_LINEAR_OPERANDS=bf16), which cover up to "
+                                f"{MAX_TOKENS} tokens")
+        if T > MAX_TOKENS:
+            raise L.VitsslError(f"sequence length {T} > {MAX_TOKENS} unsupported by the attention kernels")
+
     # forward ----------------------------------------------------------------
     def forward(self, x: torch.Tensor, B: int, T: int, training: bool, seed: int, save: bool, slot: str = "a",
                 return_attn: bool = False):
         """x: fp32 [B*T, D] (left untouched).  Returns (x_out fp32 [B*T, D], probs or None)."""
         st, D, H, F, dh = self.store, self.D, self.H, self.F, self.dh
+        self.check_tokens(T)
         M = B * T
         dev = x.device
         g = self.ws.get
