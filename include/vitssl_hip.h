@@ -298,7 +298,9 @@ int vitssl_colsum_bf16(const void* x_bf16, float* out, int64_t rows, int cols, f
  * formed without float atomics: each workgroup stores its partial in the caller's workspace and one reduce launch adds
  * the partials in a fixed order, so the same inputs give the same bits in every run.  The workspace is the caller's
  * memory; two calls may share one only if they are ordered (one stream).  vitssl_sum_workspace_floats(rows, cols):
- * floats that suffice for any of these calls summing a [rows, cols] matrix over its rows (for the L1 loss: n, 1). */
+ * floats that suffice for any of these calls summing a [rows, cols] matrix over its rows (for the L1 loss: n, 1).  Every one of
+ * these calls refuses a workspace with fewer floats than that (or NULL where a sum is asked for) before it launches anything,
+ * whether or not the launch at hand would have used them all; the error text names the sizing function. */
 int64_t vitssl_sum_workspace_floats(int64_t rows, int cols);
 
 /* ---- parameter plumbing ----------------------------------------------------------- */

@@ -71,7 +71,9 @@ typedef std::atomic<bool> VsOnce;   // "hipFuncSetAttribute already done" flags:
 // in a slot of the caller's workspace and vs_reduce_parts adds the slots to the target in a fixed order, so that the same
 // inputs give the same bits (include/vitssl_hip.h, vitssl_sum_workspace_floats).
 // vs_parts: the workspace if it holds `need` floats, else nullptr with the error set.
-float* vs_parts(float* workspace, int64_t workspace_floats, long long need, const char* who);
+float* vs_parts(float* workspace, int64_t workspace_floats, long long need, const char* who, const char* sizing = "vitssl_sum_workspace_floats");
+// the same for a sum over a [rows, cols] matrix: requires the documented vitssl_sum_workspace_floats(rows, cols), which must cover `need`
+float* vs_sum_parts(float* workspace, int64_t workspace_floats, long long need, long long rows, int cols, const char* who);
 // target[c] += sum over p = 0 .. nparts-1 of parts[p * stride + c], c < n, always summed in the same order; up to three
 // (target, parts) pairs of one shape in one launch (null targets are skipped)
 struct VsSums {

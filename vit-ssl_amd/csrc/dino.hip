@@ -487,7 +487,8 @@ extern "C" int64_t vitssl_dino_loss_workspace_floats(int G, int B, int K) {
 extern "C" int vitssl_dino_loss(const float* teacher, const float* student, const float* center, float* t_ws, int64_t t_ws_floats,
                                 float* loss_sum, void* dstudent_bf16, int G, int V, int B, int K, float teacher_temp,
                                 float student_temp, float gscale, void* stream) {
-  VS_CHECK_ARG(teacher && student && center && t_ws && loss_sum, "dino_loss: null pointer");
+  VS_CHECK_ARG(teacher && student && center && loss_sum, "dino_loss: null pointer");
+  VS_CHECK_ARG(t_ws, "dino_loss: no scratch buffer (vitssl_dino_loss_workspace_floats floats are required)");
   VS_CHECK_ARG(G > 0 && V > 0 && B > 0 && K > 0 && K % 4 == 0, "dino_loss: K=%d must be a positive multiple of 4", K);
   VS_CHECK_ARG(t_ws_floats >= vitssl_dino_loss_workspace_floats(G, B, K), "dino_loss: scratch of %lld floats, %lld needed (vitssl_dino_loss_workspace_floats)",
                (long long)t_ws_floats, (long long)vitssl_dino_loss_workspace_floats(G, B, K));

@@ -395,13 +395,26 @@ __global__ void reduce_parts_kernel(VsSums sums, int nparts, long long n, long l
   if (threadIdx.y == 0 && c < n) target[c] += red[threadIdx.x];
 }
 
-float* vs_parts(float* workspace, int64_t workspace_floats, long long need, const char* who) {
+float* vs_parts(float* workspace, int64_t workspace_floats, long long need, const char* who, const char* sizing) {
   if (!workspace || workspace_floats < need) {
-    vitssl_set_error("%s: workspace of %lld floats, need %lld (vitssl_sum_workspace_floats)", who, (long long)(workspace ? workspace_floats : 0),
-                     need);
+    vitssl_set_error("%s: workspace of %lld floats, need %lld (%s)", who, (long long)(workspace ? workspace_floats : 0), need, sizing);
     return nullptr;
   }
   return workspace;
+}
+
+// The documented contract of every fixed-order sum over a [rows, cols] matrix: the caller's workspace holds at least
+// vitssl_sum_workspace_floats(rows, cols) floats.  That (not the smaller count this launch happens to use) is what is checked, so
+// a caller's under-sized buffer is refused on every shape, and a launch that would need more than the promise is an error here
+// instead of a write behind the caller's buffer.
+float* vs_sum_parts(float* workspace, int64_t workspace_floats, long long need, long long rows, int cols, const char* who) {
+  const long long promised = vitssl_sum_workspace_floats(rows, cols);
+  if (need > promised) {
+    vitssl_set_error("%s: this launch needs %lld floats of workspace, vitssl_sum_workspace_floats(%lld, %d) promises %lld", who, need, rows,
+                     cols, promised);
+    return nullptr;
+  }
+  return vs_parts(workspace, workspace_floats, promised, who);
 }
 
 extern "C" int64_t vitssl_sum_workspace_floats(int64_t rows, int cols) {
@@ -530,7 +543,7 @@ extern "C" int vitssl_embed_bwd(const float* dtok, const uint8_t* mask, void* dp
   const int T_out = tokens + tok_offset;
   const int bs = embed_bwd_splits(B, T_out);
   const int ysplits = EMBED_YSPLITS;
-  if (!vs_parts(workspace, workspace_floats, embed_ws_floats(bs, T_out, D), "embed_bwd")) return VITSSL_ERR_ARG;
+  if (!vs_parts(workspace, workspace_floats, embed_ws_floats(bs, T_out, D), "embed_bwd", "vitssl_embed_bwd_workspace_floats")) return VITSSL_ERR_ARG;
   float* ws = (dmask_token || dbias) ? workspace : nullptr;
   float* parts = workspace + (long long)bs * T_out * 2 * D;
   const bool pos_sums = dpos || (dcls && tok_offset == 1);
@@ -556,7 +569,7 @@ extern "C" int vitssl_l1_loss(const float* pred, const float* target, float* los
                               int64_t n, float* workspace, int64_t workspace_floats, void* stream) {
   VS_CHECK_ARG(pred && target && loss_sum && n > 0 && n % 4 == 0, "l1_loss: n=%lld must be a positive multiple of 4", (long long)n);
   const unsigned grid = stream_grid(n / 4);
-  float* parts = vs_parts(workspace, workspace_floats, grid, "l1_loss");
+  float* parts = vs_sum_parts(workspace, workspace_floats, grid, n, 1, "l1_loss");
   if (!parts) return VITSSL_ERR_ARG;
   hipLaunchKernelGGL(l1_loss_kernel, dim3(grid), dim3(EW_THREADS), 0, (hipStream_t)stream, pred, target, parts,
                      (bf16_t*)dpred_bf16, gscale, (long long)(n / 4));
@@ -578,7 +591,7 @@ extern "C" int vitssl_colsum_bf16(const void* x_bf16, float* out, int64_t rows, 
   VS_CHECK_ARG(x_bf16 && out && rows > 0 && cols > 0 && cols % 4 == 0, "colsum_bf16: bad args");
   int splits = (int)((rows + 127) / 128);
   if (splits > 512) splits = 512;
-  float* parts = vs_parts(workspace, workspace_floats, (long long)splits * cols, "colsum_bf16");
+  float* parts = vs_sum_parts(workspace, workspace_floats, (long long)splits * cols, rows, cols, "colsum_bf16");
   if (!parts) return VITSSL_ERR_ARG;
   hipLaunchKernelGGL(colsum_bf16_kernel, dim3((cols / 4 + EW_THREADS - 1) / EW_THREADS, splits), dim3(EW_THREADS), 0,
                      (hipStream_t)stream, (const bf16_t*)x_bf16, parts, (long long)rows, cols);

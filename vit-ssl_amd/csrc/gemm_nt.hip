@@ -1350,7 +1350,7 @@ int launch_cfg(NtParams p, hipStream_t s) {
   float* colsum = p.colsum;
   if (!colsum) return launch_cfg_parts<EPI, CFG>(p, s);
   const int groups = (int)ceil_div64(p.M, CFG::BM) * (CFG::BM / CFG::WROWS);
-  p.colsum = vs_parts(p.workspace, p.workspace_floats, (long long)groups * p.N, "gemm_nt column sums");
+  p.colsum = vs_sum_parts(p.workspace, p.workspace_floats, (long long)groups * p.N, p.M, p.N, "gemm_nt column sums");
   if (!p.colsum) return VITSSL_ERR_ARG;
   const int rc = launch_cfg_parts<EPI, CFG>(p, s);
   if (rc != VITSSL_OK) return rc;

@@ -790,7 +790,8 @@ extern "C" int vitssl_gemm_bf16_tn(const void* A, const void* B, float* C, int64
   tn_plan(M, N1, N2, &p.tiles1, &p.tiles2, &p.splits, &p.chunks_per_split);
   const long long need = (long long)p.splits * N1 * N2;
   p.slabs = (workspace && workspace_floats >= need) ? workspace : nullptr;
-  VS_CHECK_ARG(!workspace || p.slabs, "gemm_tn: workspace too small (%lld < %lld floats)", (long long)workspace_floats, need);
+  VS_CHECK_ARG(!workspace || p.slabs, "gemm_tn: workspace too small (%lld < %lld floats, vitssl_gemm_tn_workspace_floats)", (long long)workspace_floats,
+               need);
   // One split (more C tiles than CUs: the DINO head's [65536, 768] weight gradient): the slab would be written, read back and
   // added to C by a second kernel -- 3 x 201 MB for nothing, since every tile has a single owner (tn_reduce was 1.6 ms of a
   // DINO step, 114 us per such call).  The owner adds into C itself.
@@ -958,7 +959,8 @@ extern "C" int vitssl_gemm_fp8_tn(const void* A8, const void* B8, float* C, int6
   tn_plan(M, N1, N2, &p.tiles1, &p.tiles2, &p.splits, &p.chunks_per_split, TN8_KM);
   const long long need = (long long)p.splits * N1 * N2;
   p.slabs = (workspace && workspace_floats >= need) ? workspace : nullptr;
-  VS_CHECK_ARG(!workspace || p.slabs, "gemm_fp8_tn: workspace too small (%lld < %lld floats)", (long long)workspace_floats, need);
+  VS_CHECK_ARG(!workspace || p.slabs, "gemm_fp8_tn: workspace too small (%lld < %lld floats, vitssl_gemm_fp8_tn_workspace_floats)",
+               (long long)workspace_floats, need);
   p.direct = p.splits == 1;
   if (p.direct) p.slabs = nullptr;
   static VsOnce attr_done{false};

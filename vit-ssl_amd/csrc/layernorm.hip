@@ -353,7 +353,7 @@ int launch_ln_bwd(const void* dy, const float* x, const float* mean, const float
   if (!((HAS_LN && (dgamma || dbeta)) || gm_colsum))
     return launch_ln_bwd_parts<HAS_LN, Q8>(dy, x, mean, rstd, gamma, g_res, g_out, gm, nullptr, nullptr, nullptr, drop, rows, cols, s, gm8,
                                            qscale, qamax);
-  float* parts = vs_parts(workspace, workspace_floats, 3 * slab, "layernorm_bwd / grad_mask_cast");
+  float* parts = vs_sum_parts(workspace, workspace_floats, 3 * slab, rows, cols, "layernorm_bwd / grad_mask_cast");
   if (!parts) return VITSSL_ERR_ARG;
   float* pg = HAS_LN && dgamma ? parts : nullptr;
   float* pb = HAS_LN && dbeta ? parts + slab : nullptr;
