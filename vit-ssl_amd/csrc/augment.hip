@@ -16,6 +16,7 @@
 //                           2 saturation, 3 hue), gray, hue_shift (uint8 added to H)
 //   fparams f32   [B, 10] = brightness, contrast, saturation, k1d[0..6] (normalised Gaussian)
 #include "common.h"
+#include "resample_taps.h"   // Pillow's fixed-point BILINEAR taps, shared with transforms.hip
 
 // Pillow / NumPy round every product and every sum separately; hipcc's default
 // (-ffp-contract=fast) fuses `a + b * c` into one FMA even through __fmul_rn / __fadd_rn, and a
@@ -25,41 +26,6 @@
 namespace {
 
 constexpr int AUG_IP = 11, AUG_FP = 10;
-constexpr int PRECISION_BITS = 32 - 8 - 2;   // Pillow Resample.c
-
-__device__ __forceinline__ double bilinear_filter(double x) {
-  x = x < 0.0 ? -x : x;
-  return x < 1.0 ? 1.0 - x : 0.0;
-}
-
-// Pillow precompute_coeffs + normalize_coeffs_8bpc for output position xx, evaluated on the
-// fly (BILINEAR, support 1).  Returns the first source index; writes up to `cap` fixed-point
-// taps to k[] and their number to *count.
-__device__ __forceinline__ int resample_taps(int in_size, int out_size, int xx, int* k, int cap, int* count) {
-  const double scale = (double)in_size / (double)out_size;
-  const double filterscale = scale < 1.0 ? 1.0 : scale;
-  const double support = filterscale;
-  const double ss = 1.0 / filterscale;
-  const double center = ((double)xx + 0.5) * scale;
-  int xmin = (int)(center - support + 0.5);
-  if (xmin < 0) xmin = 0;
-  int xmax = (int)(center + support + 0.5);
-  if (xmax > in_size) xmax = in_size;
-  xmax -= xmin;
-  if (xmax > cap) xmax = cap;          // cannot happen for cap >= 2*ceil(scale)+1 (checked on the host)
-  double ww = 0.0;
-  for (int x = 0; x < xmax; ++x) ww += bilinear_filter(((double)(x + xmin) - center + 0.5) * ss);
-  for (int x = 0; x < xmax; ++x) {
-    double w = bilinear_filter(((double)(x + xmin) - center + 0.5) * ss);
-    if (ww != 0.0) w /= ww;
-    k[x] = w < 0.0 ? (int)(-0.5 + w * (double)(1 << PRECISION_BITS)) : (int)(0.5 + w * (double)(1 << PRECISION_BITS));
-  }
-  *count = xmax;
-  return xmin;
-}
-
-__device__ __forceinline__ unsigned char clip8(int v) { return (unsigned char)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
-
 constexpr int MAX_TAPS = 64;   // source / output size ratio up to 31
 
 // horizontal pass: tmp[b][y][xx][c] for crop rows y < h;  grid = (H, B), threads over xx (the

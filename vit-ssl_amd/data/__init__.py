@@ -6,3 +6,4 @@ from pkgutil import extend_path
 __path__ = extend_path(__path__, __name__)
 
 from .multicrop import GPUMultiCrop, ViewSpec, params_as_list, sample_batch_params, sample_view_params  # noqa: F401
+from .transforms import GPUTransform, TransformSpec, sample_transform_params  # noqa: F401

@@ -90,8 +90,9 @@ def gaussian_kernel1d(ksize: int, sigma: float) -> np.ndarray:
     return (pdf / pdf.sum(dtype=np.float32)).astype(np.float32)
 
 
-def sample_view_params(spec: ViewSpec, height: int, width: int, generator: Optional[torch.Generator] = None) -> dict:
-    """One view's random parameters, drawn in the order the transform list consumes them."""
+def sample_crop_flip(spec, height: int, width: int, generator: Optional[torch.Generator] = None) -> dict:
+    """RandomResizedCrop.get_params followed by the RandomHorizontalFlip draw: the head of every transform list that
+    starts with these two (`spec` needs .scale, .ratio and .flip_p: a ViewSpec or a data.transforms.TransformSpec)."""
     area = height * width
     log_ratio = (math.log(spec.ratio[0]), math.log(spec.ratio[1]))
     box = None
@@ -106,15 +107,26 @@ def sample_view_params(spec: ViewSpec, height: int, width: int, generator: Optio
             box = (top, left, h, w)
             break
     if box is None:                                      # fallback: centre crop inside the ratio range
-        in_ratio = width / height
-        if in_ratio < spec.ratio[0]:
-            w, h = width, int(round(width / spec.ratio[0]))
-        elif in_ratio > spec.ratio[1]:
-            h, w = height, int(round(height * spec.ratio[1]))
-        else:
-            w, h = width, height
-        box = ((height - h) // 2, (width - w) // 2, h, w)
+        box = _fallback_box(spec, height, width)
     flip = bool(torch.rand(1, generator=generator) < spec.flip_p)
+    return dict(top=box[0], left=box[1], h=box[2], w=box[3], flip=flip)
+
+
+def _fallback_box(spec, height: int, width: int):
+    """(top, left, h, w) of torchvision's fallback after 10 rejected tries: the centre crop inside the ratio range"""
+    in_ratio = width / height
+    if in_ratio < spec.ratio[0]:
+        w, h = width, int(round(width / spec.ratio[0]))
+    elif in_ratio > spec.ratio[1]:
+        h, w = height, int(round(height * spec.ratio[1]))
+    else:
+        w, h = width, height
+    return (height - h) // 2, (width - w) // 2, h, w
+
+
+def sample_view_params(spec: ViewSpec, height: int, width: int, generator: Optional[torch.Generator] = None) -> dict:
+    """One view's random parameters, drawn in the order the transform list consumes them."""
+    head = sample_crop_flip(spec, height, width, generator)
     order = [int(v) for v in torch.randperm(4, generator=generator)]
     jit = {}
     for k in ("brightness", "contrast", "saturation"):
@@ -123,18 +135,17 @@ def sample_view_params(spec: ViewSpec, height: int, width: int, generator: Optio
     jit["hue"] = _uniform(-spec.hue, spec.hue, generator) if spec.hue > 0 else 0.0
     gray = bool(torch.rand(1, generator=generator) < spec.gray_p) if spec.gray_p > 0 else False
     sigma = _uniform(spec.blur_sigma[0], spec.blur_sigma[1], generator)
-    return dict(top=box[0], left=box[1], h=box[2], w=box[3], flip=flip, order=order, gray=gray, sigma=sigma, **jit)
+    return dict(**head, order=order, gray=gray, sigma=sigma, **jit)
 
 
-def sample_batch_params(spec: ViewSpec, height: int, width: int, n: int,
-                        generator: Optional[torch.Generator] = None) -> dict:
-    """`n` independent parameter sets with the distributions of `sample_view_params`, drawn
-    from ONE block of uniforms and computed with NumPy array arithmetic (the scalar sampler
-    costs ~30 us per view: 75 ms of host time for a batch of 256 image sets).  Returns a dict
-    of arrays (same keys as the scalar sampler's dict; `order` is [n, 4]).  The mapping of
-    random numbers to parameters differs from the scalar sampler; the distributions do not:
-    integers are floor(u * range), the jitter order is the argsort of four uniforms."""
-    u = torch.rand(n, 32, generator=generator, dtype=torch.float64).numpy()
+CROP_FLIP_UNIFORMS = 23      # columns of the uniform block `crop_flip_from_uniforms` consumes
+
+
+def crop_flip_from_uniforms(spec, height: int, width: int, u: np.ndarray) -> dict:
+    """Crop boxes and flips of n images from an [n, >= 23] block of float64 uniforms: columns 2t, 2t+1 are try t's area
+    and log-ratio, 20 / 21 place the box, 22 decides the flip.  Shared by `sample_batch_params` (which draws 32 columns,
+    the rest being the colour and blur draws) and data.transforms.sample_transform_params (which draws only these)."""
+    n = u.shape[0]
     area = float(height * width)
     lr0, lr1 = math.log(spec.ratio[0]), math.log(spec.ratio[1])
     hh = np.zeros(n, np.int64)
@@ -151,15 +162,22 @@ def sample_batch_params(spec: ViewSpec, height: int, width: int, n: int,
     top = np.minimum((u[:, 20] * (height - hh + 1)).astype(np.int64), height - hh)
     left = np.minimum((u[:, 21] * (width - ww + 1)).astype(np.int64), width - ww)
     if not done.all():                                    # fallback: centre crop inside the ratio range
-        in_ratio = width / height
-        if in_ratio < spec.ratio[0]:
-            fw, fh = width, int(round(width / spec.ratio[0]))
-        elif in_ratio > spec.ratio[1]:
-            fh, fw = height, int(round(height * spec.ratio[1]))
-        else:
-            fw, fh = width, height
+        ft, fl, fh, fw = _fallback_box(spec, height, width)
         miss = ~done
-        hh[miss], ww[miss], top[miss], left[miss] = fh, fw, (height - fh) // 2, (width - fw) // 2
+        hh[miss], ww[miss], top[miss], left[miss] = fh, fw, ft, fl
+    return dict(top=top, left=left, h=hh, w=ww, flip=u[:, 22] < spec.flip_p)
+
+
+def sample_batch_params(spec: ViewSpec, height: int, width: int, n: int,
+                        generator: Optional[torch.Generator] = None) -> dict:
+    """`n` independent parameter sets with the distributions of `sample_view_params`, drawn
+    from ONE block of uniforms and computed with NumPy array arithmetic (the scalar sampler
+    costs ~30 us per view: 75 ms of host time for a batch of 256 image sets).  Returns a dict
+    of arrays (same keys as the scalar sampler's dict; `order` is [n, 4]).  The mapping of
+    random numbers to parameters differs from the scalar sampler; the distributions do not:
+    integers are floor(u * range), the jitter order is the argsort of four uniforms."""
+    u = torch.rand(n, 32, generator=generator, dtype=torch.float64).numpy()
+    head = crop_flip_from_uniforms(spec, height, width, u)
 
     def jitter(x, col):
         if x <= 0:
@@ -167,7 +185,7 @@ def sample_batch_params(spec: ViewSpec, height: int, width: int, n: int,
         lo = max(0.0, 1.0 - x)
         return lo + (1.0 + x - lo) * u[:, col]
 
-    return dict(top=top, left=left, h=hh, w=ww, flip=u[:, 22] < spec.flip_p,
+    return dict(**head,
                 brightness=jitter(spec.brightness, 23), contrast=jitter(spec.contrast, 24), saturation=jitter(spec.saturation, 25),
                 hue=(-spec.hue + 2.0 * spec.hue * u[:, 26]) if spec.hue > 0 else np.zeros(n),
                 order=np.argsort(u[:, 27:31], axis=1), gray=(u[:, 31] < spec.gray_p) if spec.gray_p > 0 else np.zeros(n, bool),

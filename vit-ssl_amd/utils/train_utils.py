@@ -6,7 +6,8 @@ Same entry points and config keys as the reference (utils/train_utils.py:12-51:
 read through `_spec` into a (name, kwargs) pair, and an AdamW request over a model that exposes
 its flat parameter store is answered with the fused flat-buffer optimizer kernel instead of
 torch.optim.AdamW.  `get_transforms` returns callables with the reference's per-image semantics that also carry the
-GPU multi-crop recipe (`.view_spec`, see `data.ViewSpec.from_config`).
+GPU multi-crop recipe (`.view_spec`, see `data.ViewSpec.from_config`) or, for the crop / flip / ToTensor and Resize / ToTensor
+lists, the recipe of the fused transform kernel (`.transform_spec`, see `data.TransformSpec.from_config`).
 """
 import logging
 import os
@@ -29,12 +30,12 @@ def _spec(config, *path):
 
 
 class _NeedsTorchvision:
-    """Stand-in for one transform list on a host without torchvision: carries the GPU recipe (`view_spec`), and says what
+    """Stand-in for one transform list on a host without torchvision: carries the GPU recipes (`view_spec`, `transform_spec`), and says what
     is missing when a dataset calls it the way the reference's datasets do (`self.transform(image)`,
     `self.transforms["globals"](image)`: data/datasets.py:36-38,119-123)."""
 
-    def __init__(self, key, sequence, view_spec):
-        self.key, self.sequence, self.view_spec = key, list(sequence), view_spec
+    def __init__(self, key, sequence, view_spec, transform_spec=None):
+        self.key, self.sequence, self.view_spec, self.transform_spec = key, list(sequence), view_spec, transform_spec
 
     def __call__(self, image):
         from vitssl_hip import VitsslError
@@ -42,11 +43,11 @@ class _NeedsTorchvision:
         raise VitsslError(
             f"transforms[{self.key!r}] ({names}) was called on the CPU, but torchvision is not installed on this host. "
             "The reference builds these lists from torchvision.transforms (utils/train_utils.py:54-68). Either install "
-            "torchvision, or feed uint8 [B,H,W,3] batches and let data.GPUMultiCrop render the views on the GPU from "
-            "this object's .view_spec (INTEGRATION.md section 4).")
+            "torchvision, or feed uint8 [B,H,W,3] batches and let data.GPUMultiCrop (from this object's .view_spec) or "
+            "data.GPUTransform (from its .transform_spec) render them on the GPU (INTEGRATION.md section 4).")
 
     def __repr__(self):
-        return f"_NeedsTorchvision({self.key!r}, view_spec={self.view_spec})"
+        return f"_NeedsTorchvision({self.key!r}, view_spec={self.view_spec}, transform_spec={self.transform_spec})"
 
 
 def _view_spec_or_none(sequence):
@@ -58,11 +59,22 @@ def _view_spec_or_none(sequence):
         return None
 
 
+def _transform_spec_or_none(sequence):
+    """The fused-kernel recipe of a crop / flip / ToTensor or Resize / ToTensor list, or None for any other list."""
+    from data import TransformSpec
+    try:
+        return TransformSpec.from_config(sequence)
+    except (ValueError, KeyError, TypeError):
+        return None
+
+
 def get_transforms(config):
     """`transforms:` section -> {name: callable}, the reference's contract (utils/train_utils.py:54-68: every list becomes
     a torchvision Compose built with getattr(T, name)(**params), which the datasets call per image on the CPU).  Each
     returned callable ALSO carries `.view_spec`: the same list reduced to the numbers `data.GPUMultiCrop` needs to render
-    the DINO views for a whole batch on the GPU (None for lists that are not crop / flip / jitter / gray / blur recipes).
+    the DINO views for a whole batch on the GPU (None for lists that are not crop / flip / jitter / gray / blur recipes),
+    and `.transform_spec`: the numbers `data.GPUTransform` needs (None unless the list is RandomResizedCrop, RandomHorizontalFlip,
+    ToTensor or Resize, ToTensor).
     Without torchvision the callables refuse to run with a message naming the GPU route."""
     try:
         from torchvision import transforms as T
@@ -71,12 +83,13 @@ def get_transforms(config):
     out = {}
     for key, sequence in dict(cfg_get(config, "transforms") or {}).items():
         sequence = [dict(name=cfg_get(e, "name"), params=dict(cfg_get(e, "params", default={}) or {})) for e in sequence]
-        spec = _view_spec_or_none(sequence)
+        spec, tspec = _view_spec_or_none(sequence), _transform_spec_or_none(sequence)
         if T is None:
-            out[key] = _NeedsTorchvision(key, sequence, spec)
+            out[key] = _NeedsTorchvision(key, sequence, spec, tspec)
             continue
         pipeline = T.Compose([getattr(T, e["name"])(**e["params"]) for e in sequence])
         pipeline.view_spec = spec
+        pipeline.transform_spec = tspec
         out[key] = pipeline
     return out
 

@@ -2,7 +2,8 @@
 criterion / optimizer / scheduler factories, epoch loop, checkpoint dict layout
 {epoch, model_state_dict, optimizer_state_dict, best_val_loss, config}.  The reference's
 rich Logger, MetricHandler and TrainingHistory are out of scope; stdlib logging reports
-the loss.  New: data-parallel gradient reduction when torch.distributed is initialised."""
+the loss.  New: data-parallel gradient reduction when torch.distributed is initialised; uint8 [B,H,W,3] batches are
+rendered on the GPU by the config's `transforms.train` / `transforms.val` list (`_batch`, data.GPUTransform)."""
 import logging
 import math
 import os
@@ -45,6 +46,8 @@ class BaseTrainer(ABC):
         self.reducer = None
         if self.world > 1:
             self._setup_data_parallel()
+        self._gpu_transforms = {}           # split -> data.GPUTransform, built on the first uint8 batch
+        self.transform_generator = None     # torch.Generator of the crop / flip draws (None: the global CPU generator)
 
     # ---- data parallel -----------------------------------------------------------
     def _dp_store(self):
@@ -69,6 +72,30 @@ class BaseTrainer(ABC):
             if p.grad is not None:
                 dist.all_reduce(p.grad)
                 p.grad.div_(self.world)
+
+    # ---- input ---------------------------------------------------------------------
+    def _batch(self, batch, split, non_blocking=True):
+        """What a loader yields -> (float32 images on the device, labels on the device or None).  A uint8 [B,H,W,3] tensor
+        of decoded images, alone or as the first element of (images, labels), is rendered on the GPU by the
+        `transforms.<split>` list of the config (the list the reference's datasets run per image on the CPU:
+        utils/train_utils.py:54-68); float batches pass through untouched.  `non_blocking`: how the batch is copied to the
+        device (each trainer keeps the copy it always made)."""
+        labels = None
+        if isinstance(batch, (tuple, list)):
+            batch, labels = batch[0], batch[1]
+            labels = labels.to(self.device, non_blocking=non_blocking)
+        images = batch.to(self.device, non_blocking=non_blocking)
+        if images.dtype == torch.uint8 and images.dim() == 4:
+            tf = self._gpu_transforms.get(split)
+            if tf is None:
+                from data import GPUTransform, TransformSpec
+                sequence = cfg_get(self.config, "transforms", split)
+                if sequence is None:
+                    raise ValueError(f"{type(self).__name__}: the loader yielded a uint8 batch {tuple(images.shape)} but the config has no "
+                                     f"`transforms.{split}` list to render it with")
+                tf = self._gpu_transforms[split] = GPUTransform(TransformSpec.from_config(sequence))
+            images = tf(images, self.transform_generator)
+        return images, labels
 
     # ---- abstract ------------------------------------------------------------------
     @abstractmethod

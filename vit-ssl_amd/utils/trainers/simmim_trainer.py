@@ -4,7 +4,9 @@ Step body = the reference's zero_grad -> forward -> criterion -> backward -> ste
 (-> warm-up).  With nn.L1Loss(mean) + AdamW (the reference's configs/simmim/training.yaml)
 the whole step runs fused in the HIP engine (SimMIMViT.train_step); any other criterion /
 optimizer takes the reference-style autograd path through the same kernels.  The loss is
-accumulated on the device and read once per epoch (the reference syncs every step)."""
+accumulated on the device and read once per epoch (the reference syncs every step).
+A loader may yield float batches (as the reference's) or decoded uint8 [B,H,W,3] images, alone
+or with labels, which `BaseTrainer._batch` renders on the GPU (transforms.train / transforms.val)."""
 import logging
 
 import torch
@@ -25,7 +27,7 @@ class SimMIMTrainer(BaseTrainer):
         running = None
         fused = self._fused_ok()
         for idx, inputs in enumerate(self.train_loader):
-            inputs = inputs.to(self.device, non_blocking=True)
+            inputs, _ = self._batch(inputs, "train")
             if fused:
                 loss = self.model.train_step(inputs, self.optimizer, self.reducer)
             else:
@@ -46,7 +48,7 @@ class SimMIMTrainer(BaseTrainer):
         total, running = 0, None
         with torch.no_grad():
             for idx, inputs in enumerate(self.val_loader):
-                inputs = inputs.to(self.device, non_blocking=True)
+                inputs, _ = self._batch(inputs, "val")
                 preds, targets = self.model(inputs)
                 loss = self.criterion(preds, targets)
                 running = loss if running is None else running + loss

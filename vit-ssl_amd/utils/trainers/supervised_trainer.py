@@ -1,6 +1,7 @@
 """Supervised / fine-tune trainer (reference: utils/trainers/supervised_trainer.py:30-48):
 logits = model(x); CrossEntropy; backward; step.  Runs the reference-style autograd path
-through the HIP engine (the supervised config is the reference's small plumbing case)."""
+through the HIP engine (the supervised config is the reference's small plumbing case).
+Batches are (images, labels); uint8 [B,H,W,3] images are rendered on the GPU (`BaseTrainer._batch`)."""
 import logging
 
 import torch
@@ -11,11 +12,17 @@ logger = logging.getLogger(__name__)
 
 
 class SupervisedTrainer(BaseTrainer):
+    def _labelled(self, batch, split):
+        inputs, labels = self._batch(batch, split, non_blocking=False)
+        if labels is None:
+            raise ValueError("SupervisedTrainer: the loader yielded images without labels; it must yield (images, labels)")
+        return inputs, labels
+
     def train_epoch(self, epoch: int):
         self.model.train()
         total, correct, seen, running = 0, 0, 0, None
-        for idx, (inputs, labels) in enumerate(self.train_loader):
-            inputs, labels = inputs.to(self.device), labels.to(self.device)
+        for idx, batch in enumerate(self.train_loader):
+            inputs, labels = self._labelled(batch, "train")
             self.optimizer.zero_grad(set_to_none=True)
             logits = self.model(inputs)
             loss = self.criterion(logits, labels)
@@ -33,8 +40,8 @@ class SupervisedTrainer(BaseTrainer):
         self.model.eval()
         total, correct, seen, running = 0, 0, 0, None
         with torch.no_grad():
-            for idx, (inputs, labels) in enumerate(self.val_loader):
-                inputs, labels = inputs.to(self.device), labels.to(self.device)
+            for idx, batch in enumerate(self.val_loader):
+                inputs, labels = self._labelled(batch, "val")
                 logits = self.model(inputs)
                 loss = self.criterion(logits, labels)
                 running = loss if running is None else running + loss

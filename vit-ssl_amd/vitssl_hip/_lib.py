@@ -8,6 +8,7 @@ import re
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VITSSL_LIB") or os.path.join(_HERE, "libvitssl_hip.so")   # VITSSL_LIB: developer override (kernel A/B builds)
 HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "vitssl_hip.h"))
+TRANSFORMS_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "vitssl_transforms.h"))
 
 
 class VitsslError(RuntimeError):
@@ -104,6 +105,13 @@ PROTOTYPES = {
     "vitssl_set_reserved_cus": [_i],
 }
 
+# include/vitssl_transforms.h (the fused transform-list kernel): same library, a table of its own, so that PROTOTYPES stays
+# the mirror of include/vitssl_hip.h.  Launching entry points only; the introspection getter
+# vitssl_debug_tf_tile_rows (returns a count) is bound in lib() beside the other vitssl_debug_* getters.
+PROTOTYPES_TRANSFORMS = {
+    "vitssl_tf_resized_crop_to_tensor": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
+}
+
 _lib = None
 
 
@@ -111,6 +119,13 @@ def header_symbols():
     """Entry points declared in include/vitssl_hip.h (int-returning `vitssl_*` functions)."""
     with open(HEADER_PATH) as f:
         txt = f.read()
+    return sorted(set(re.findall(r"\b(vitssl_[a-z0-9_]+)\s*\(", txt)))
+
+
+def transforms_header_symbols():
+    """Entry points declared in include/vitssl_transforms.h."""
+    with open(TRANSFORMS_HEADER_PATH) as f:
+        txt = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)        # the comments name functions of vitssl_hip.h
     return sorted(set(re.findall(r"\b(vitssl_[a-z0-9_]+)\s*\(", txt)))
 
 
@@ -153,7 +168,9 @@ def lib():
     for getter in ("vitssl_get_reserved_cus", "vitssl_debug_last_nt_grid", "vitssl_debug_last_attn_fwd_grid"):
         getattr(l, getter).restype = C.c_int
         getattr(l, getter).argtypes = []
-    for name, args in PROTOTYPES.items():
+    l.vitssl_debug_tf_tile_rows.restype = C.c_int
+    l.vitssl_debug_tf_tile_rows.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+    for name, args in list(PROTOTYPES.items()) + list(PROTOTYPES_TRANSFORMS.items()):
         fn = getattr(l, name)  # AttributeError if the symbol is missing
         fn.restype = C.c_int
         fn.argtypes = args

@@ -608,3 +608,28 @@ def aug_blur_to_tensor(img, fparams, out, ksize=7):
     B, S = img.shape[0], img.shape[1]
     call("vitssl_aug_blur_to_tensor", _chk(img, torch.uint8, "img", (B, S, S, 3)), _chk(fparams, F32, "fparams", (B, AUG_FP)),
          _chk(out, F32, "out", (B, 3, S, S)), B, S, ksize, _stream())
+
+
+# ---- SimMIM / supervised / eval transform lists (utils/train_utils.py:54-68; include/vitssl_transforms.h) ----
+TF_IP = 5
+
+
+def tf_tile_rows(H, W, SH, SW):
+    """output rows per workgroup tile of `tf_resized_crop_to_tensor` for this shape; raises where the kernel refuses it"""
+    l = L.lib()
+    tr = l.vitssl_debug_tf_tile_rows(int(H), int(W), int(SH), int(SW))
+    if tr <= 0:
+        raise L.VitsslError(f"vitssl_debug_tf_tile_rows failed ({tr}): {l.vitssl_last_error().decode()}")
+    return tr
+
+
+def tf_resized_crop_to_tensor(src, iparams, out):
+    """src u8 [B,H,W,3], iparams int32 [B,5] (top, left, h, w, flip; boxes inside the image), out f32 [B,3,SH,SW]"""
+    if src is None or src.dim() != 4 or src.shape[3] != 3:
+        raise L.VitsslError(f"tf_resized_crop_to_tensor: expected channel-last RGB [B,H,W,3], got {None if src is None else tuple(src.shape)}")
+    if out is None or out.dim() != 4:
+        raise L.VitsslError(f"tf_resized_crop_to_tensor: expected out [B,3,SH,SW], got {None if out is None else tuple(out.shape)}")
+    B, H, W, _ = src.shape
+    SH, SW = out.shape[2], out.shape[3]
+    call("vitssl_tf_resized_crop_to_tensor", _chk(src, torch.uint8, "src"), _chk(iparams, torch.int32, "iparams", (B, TF_IP)),
+         _chk(out, F32, "out", (B, 3, SH, SW)), B, H, W, SH, SW, _stream())
