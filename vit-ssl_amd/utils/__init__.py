@@ -1,7 +1,8 @@
 """Drop-in for the reference's ``utils`` package, hot-path subset:
 model factory, optimizer/criterion/scheduler factories and the trainers' step loops.
-The reference's Logger / MetricHandler / TrainingHistory (rich TUI, ignite, torcheval,
-matplotlib) are out of scope and intentionally not mirrored."""
+The reference's Logger / TrainingHistory (rich TUI, matplotlib) are out of scope and intentionally not
+mirrored; its MetricHandler (ignite, torcheval) is not mirrored either -- `utils.gpu_metrics.GPUMetricHandler` computes the same
+registry of metrics on the GPU, under a module name of its own so that `utils.metrics` below stays the reference's."""
 # The reference has packages of the same names (`utils`, `data`).  With this directory in front
 # of the reference checkout on sys.path, the modules this package does NOT replace
 # (utils.schemas, utils.logger, utils.metrics, utils.history, data.data_builder, data.datasets:

@@ -1,8 +1,9 @@
 """Common trainer scaffolding (reference: utils/trainers/base_trainer.py:16-123):
 criterion / optimizer / scheduler factories, epoch loop, checkpoint dict layout
 {epoch, model_state_dict, optimizer_state_dict, best_val_loss, config}.  The reference's
-rich Logger, MetricHandler and TrainingHistory are out of scope; stdlib logging reports
-the loss.  New: data-parallel gradient reduction when torch.distributed is initialised; uint8 [B,H,W,3] batches are
+rich Logger and TrainingHistory are out of scope; stdlib logging reports the loss.  Its MetricHandler is
+`utils.gpu_metrics.GPUMetricHandler`, built only when the config lists `metrics`; the listed names then decide which
+checkpoint is best (`_best_score`: the reference trainers' per-mode `_save_if_best` rules), otherwise the validation loss does.  New: data-parallel gradient reduction when torch.distributed is initialised; uint8 [B,H,W,3] batches are
 rendered on the GPU by the config's `transforms.train` / `transforms.val` list (`_batch`, data.GPUTransform)."""
 import logging
 import math
@@ -15,6 +16,7 @@ import torch.distributed as dist
 from vit_core._runtime import limit_host_threads
 
 from .._config import cfg_get, to_plain
+from ..gpu_metrics import GPUMetricHandler
 from ..train_utils import make_criterion, make_optimizer, make_schedulers
 
 logger = logging.getLogger(__name__)
@@ -38,6 +40,9 @@ class BaseTrainer(ABC):
         self.optimizer = make_optimizer(config, model)
         self.schedulers = make_schedulers(config, self.optimizer, self.num_epochs, self.warmup_epochs * len(train_loader))
         self.best_val_loss = math.inf
+        self.metric_handler = GPUMetricHandler.from_config(config)      # None unless the config lists `metrics`
+        self.best_val_score = -math.inf                                 # the reference's best_score (SimMIM, DINO)
+        self.best_val_acc = -math.inf                                   # (supervised, finetune)
         self.current_epoch = 0
         self.start_epoch = 0
 
@@ -118,7 +123,7 @@ class BaseTrainer(ABC):
             val_metrics = self.validate()
             self._update_schedulers(epoch)
             self._log_metrics(epoch, train_metrics, val_metrics)
-            self._save_if_best(epoch, val_metrics["Loss"])
+            self._save_if_best(epoch, val_metrics)
             self._save_last(epoch)
 
     def _update_schedulers(self, epoch):
@@ -139,12 +144,45 @@ class BaseTrainer(ABC):
         ckpt.update(extra)
         return ckpt
 
-    def _save_if_best(self, epoch, val_loss):
-        if self.rank == 0 and self.best_val_loss >= val_loss:
+    def _listed(self, *names):
+        """True when the config's `metrics` lists every one of `names`."""
+        have = self.metric_handler.metric_names if self.metric_handler is not None else ()
+        return all(n in have for n in names)
+
+    def _metric_values(self):
+        """The epoch's listed metrics ({} without a handler); the handler is reset for the next epoch or split."""
+        if self.metric_handler is None:
+            return {}
+        values = self.metric_handler.compute()
+        self.metric_handler.reset()
+        return values
+
+    def _best_score(self, val_metrics):
+        """(checkpoint key = trainer attribute, score) of the mode's metric rule -- larger is better, compared with `>` from
+        -inf as the reference trainers do -- or None: the validation loss decides (every trainer without listed metrics)."""
+        return None
+
+    def _save_if_best(self, epoch, val_metrics):
+        """Rank 0 decides from the metrics of its own shard, as it does for the loss."""
+        if self.rank != 0:
+            return
+        rule = self._best_score(val_metrics)
+        if rule is None:
+            val_loss = val_metrics["Loss"]
+            if not self.best_val_loss >= val_loss:
+                return
             self.best_val_loss = val_loss
             logger.info(f"New best validation loss: {self.best_val_loss:.4f}. Saving model...")
-            os.makedirs(self.save_path, exist_ok=True)
-            torch.save(self._checkpoint(epoch, best_val_loss=self.best_val_loss), os.path.join(self.save_path, "best_model.pth"))
+            extra = {"best_val_loss": self.best_val_loss}
+        else:
+            key, score = rule
+            if not score > getattr(self, key):
+                return
+            setattr(self, key, score)
+            logger.info(f"New best validation {'accuracy' if key == 'best_val_acc' else 'score'}: {score:.4f}. Saving model...")
+            extra = {key: score}
+        os.makedirs(self.save_path, exist_ok=True)
+        torch.save(self._checkpoint(epoch, **extra), os.path.join(self.save_path, "best_model.pth"))
 
     def _save_last(self, epoch):
         if self.rank == 0:

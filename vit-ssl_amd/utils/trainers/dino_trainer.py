@@ -6,7 +6,12 @@ first).  AdamW => the fused engine step; otherwise the reference-style autograd 
 New: when the loader yields ONE uint8 tensor [B, H, W, 3] of decoded images
 instead of the view list, the views are produced on the GPU by `data.GPUMultiCrop` from the
 `transforms.globals` / `transforms.locals` recipes of the config (the lists the reference
-feeds to torchvision on the CPU, data/datasets.py:80-123)."""
+feeds to torchvision on the CPU, data/datasets.py:80-123).
+
+With the DINO names in the config's `metrics` (CenterNorm, Teacher/Student Mean/STD/Var, CosineSim) the outputs of the
+epoch's LAST batch and `model.center` are reduced by one launch at the end of train_epoch and of validate (reference
+:114-118, :149-153), and the best checkpoint is the one with the largest CosineSim - |CenterNorm - 1| - |StudentSTD -
+TeacherSTD| (reference :157-173): the loss of a collapsed teacher looks fine, these do not."""
 import logging
 
 import torch
@@ -74,19 +79,37 @@ class DINOTrainer(BaseTrainer):
     def _loss(self, views):
         G = self.num_global_views
         teacher, student = self.model(views, G)
+        self._last_outputs = (teacher.detach(), student.detach())
         B = views[0].shape[0]
         K = teacher.shape[-1]
         return self.criterion(teacher.view(G, B, K), student.view(len(views), B, K), self.model.center)
+
+    def _last_batch_metrics(self, outputs):
+        """The listed metrics of (teacher [G*B, K], student [V*B, K]) with the centre as it stands now."""
+        if self.metric_handler is None or outputs is None:
+            return {}
+        teacher, student = outputs
+        G, K = self.num_global_views, teacher.shape[-1]
+        B = teacher.shape[0] // G
+        self.metric_handler.update_dino(teacher.reshape(G, B, K), student.reshape(-1, B, K), self.model.center)
+        return self._metric_values()
+
+    def _best_score(self, val_metrics):
+        if self._listed("CosineSim", "CenterNorm", "StudentSTD", "TeacherSTD"):
+            m = val_metrics
+            return "best_val_score", m["CosineSim"] - abs(m["CenterNorm"] - 1) - abs(m["StudentSTD"] - m["TeacherSTD"])
+        return None
 
     def train_epoch(self, epoch: int):
         self.model.train()
         self.criterion.teacher_temp, momentum = self.epoch_schedule(epoch)
         fused = self._is_fused()
-        total, running = 0, None
+        total, running, outputs = 0, None, None
         for idx, inputs in enumerate(self.train_loader):
             views = self._views(inputs)
             if fused:
                 loss = self.model.train_step(views, self.num_global_views, self.criterion, self.optimizer, self.reducer, momentum)
+                outputs = (self.model.last_teacher, self.model.last_student)
             else:
                 self.optimizer.zero_grad(set_to_none=True)
                 loss = self._loss(views)
@@ -95,18 +118,21 @@ class DINOTrainer(BaseTrainer):
                 self.optimizer.step()
                 self.model.momentum_update_teacher(momentum)
                 loss = loss.detach()
+                outputs = self._last_outputs
             self._warmup_step(epoch)
             running = loss if running is None else running + loss
             total += 1
-        return {"Loss": float(running) / max(total, 1), "TeacherTemp": self.criterion.teacher_temp, "Momentum": momentum}
+        return {**self._last_batch_metrics(outputs), "Loss": float(running) / max(total, 1), "TeacherTemp": self.criterion.teacher_temp,
+                "Momentum": momentum}
 
     def validate(self):
         self.model.eval()
-        total, running = 0, None
+        total, running, outputs = 0, None, None
         with torch.no_grad():
             for idx, inputs in enumerate(self.val_loader):
                 views = self._views(inputs)
                 loss = self._loss(views)
+                outputs = self._last_outputs
                 running = loss if running is None else running + loss
                 total += 1
-        return {"Loss": float(running) / max(total, 1) if total else float("nan")}
+        return {**self._last_batch_metrics(outputs), "Loss": float(running) / max(total, 1) if total else float("nan")}

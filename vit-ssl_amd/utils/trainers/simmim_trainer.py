@@ -6,7 +6,10 @@ the whole step runs fused in the HIP engine (SimMIMViT.train_step); any other cr
 optimizer takes the reference-style autograd path through the same kernels.  The loss is
 accumulated on the device and read once per epoch (the reference syncs every step).
 A loader may yield float batches (as the reference's) or decoded uint8 [B,H,W,3] images, alone
-or with labels, which `BaseTrainer._batch` renders on the GPU (transforms.train / transforms.val)."""
+or with labels, which `BaseTrainer._batch` renders on the GPU (transforms.train / transforms.val).
+With `metrics: [PSNR, SSIM]` in the config every step's predictions and targets are reduced on the GPU where they lie
+(utils/gpu_metrics.py; the reference keeps them all for the epoch, :79-96) and the best checkpoint is the one with the
+largest SSIM + 0.01 PSNR (reference :137-153)."""
 import logging
 
 import torch
@@ -21,6 +24,15 @@ class SimMIMTrainer(BaseTrainer):
     def _fused_ok(self):
         return self._is_fused() and isinstance(self.criterion, nn.L1Loss) and self.criterion.reduction == "mean"
 
+    def _update_metrics(self, preds, targets):
+        if self.metric_handler is not None:
+            self.metric_handler.update_recon(preds, targets, self.model.input_shape[0], self.model.patch_size)
+
+    def _best_score(self, val_metrics):
+        if self._listed("SSIM", "PSNR"):
+            return "best_val_score", val_metrics["SSIM"] + 0.01 * val_metrics["PSNR"]
+        return None
+
     def train_epoch(self, epoch: int):
         self.model.train()
         total = 0
@@ -30,6 +42,7 @@ class SimMIMTrainer(BaseTrainer):
             inputs, _ = self._batch(inputs, "train")
             if fused:
                 loss = self.model.train_step(inputs, self.optimizer, self.reducer)
+                self._update_metrics(self.model.last_pred, self.model.last_targets)
             else:
                 self.optimizer.zero_grad(set_to_none=True)
                 preds, targets = self.model(inputs)
@@ -38,10 +51,11 @@ class SimMIMTrainer(BaseTrainer):
                 self._generic_reduce()
                 self.optimizer.step()
                 loss = loss.detach()
+                self._update_metrics(preds, targets)
             self._warmup_step(epoch)
             running = loss if running is None else running + loss
             total += 1
-        return {"Loss": float(running) / max(total, 1)}
+        return {**self._metric_values(), "Loss": float(running) / max(total, 1)}
 
     def validate(self):
         self.model.eval()
@@ -51,6 +65,7 @@ class SimMIMTrainer(BaseTrainer):
                 inputs, _ = self._batch(inputs, "val")
                 preds, targets = self.model(inputs)
                 loss = self.criterion(preds, targets)
+                self._update_metrics(preds, targets)
                 running = loss if running is None else running + loss
                 total += 1
-        return {"Loss": float(running) / max(total, 1) if total else float("nan")}
+        return {**self._metric_values(), "Loss": float(running) / max(total, 1) if total else float("nan")}

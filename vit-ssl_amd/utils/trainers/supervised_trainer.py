@@ -1,7 +1,10 @@
 """Supervised / fine-tune trainer (reference: utils/trainers/supervised_trainer.py:30-48):
 logits = model(x); CrossEntropy; backward; step.  Runs the reference-style autograd path
 through the HIP engine (the supervised config is the reference's small plumbing case).
-Batches are (images, labels); uint8 [B,H,W,3] images are rendered on the GPU (`BaseTrainer._batch`)."""
+Batches are (images, labels); uint8 [B,H,W,3] images are rendered on the GPU (`BaseTrainer._batch`).
+The names of the config's `metrics` (Accuracy, F1Score, Recall, Precision) come from a confusion matrix accumulated on the
+device per batch (utils/gpu_metrics.py); with `Accuracy` listed the best checkpoint is the one with the highest validation
+accuracy, stored as `best_val_acc` (reference :126-138)."""
 import logging
 
 import torch
@@ -18,6 +21,15 @@ class SupervisedTrainer(BaseTrainer):
             raise ValueError("SupervisedTrainer: the loader yielded images without labels; it must yield (images, labels)")
         return inputs, labels
 
+    def _update_metrics(self, logits, labels):
+        if self.metric_handler is not None:
+            self.metric_handler.update_classification(logits.argmax(1), labels, logits.shape[1])
+
+    def _best_score(self, val_metrics):
+        if self._listed("Accuracy"):
+            return "best_val_acc", val_metrics["Accuracy"]
+        return None
+
     def train_epoch(self, epoch: int):
         self.model.train()
         total, correct, seen, running = 0, 0, 0, None
@@ -31,10 +43,11 @@ class SupervisedTrainer(BaseTrainer):
             self.optimizer.step()
             self._warmup_step(epoch)
             running = loss.detach() if running is None else running + loss.detach()
+            self._update_metrics(logits.detach(), labels)
             correct += int((logits.argmax(1) == labels).sum())
             seen += labels.numel()
             total += 1
-        return {"Loss": float(running) / max(total, 1), "Accuracy": correct / max(seen, 1)}
+        return {**self._metric_values(), "Loss": float(running) / max(total, 1), "Accuracy": correct / max(seen, 1)}
 
     def validate(self):
         self.model.eval()
@@ -45,7 +58,9 @@ class SupervisedTrainer(BaseTrainer):
                 logits = self.model(inputs)
                 loss = self.criterion(logits, labels)
                 running = loss if running is None else running + loss
+                self._update_metrics(logits, labels)
                 correct += int((logits.argmax(1) == labels).sum())
                 seen += labels.numel()
                 total += 1
-        return {"Loss": float(running) / max(total, 1) if total else float("nan"), "Accuracy": correct / max(seen, 1)}
+        return {**self._metric_values(), "Loss": float(running) / max(total, 1) if total else float("nan"),
+                "Accuracy": correct / max(seen, 1)}

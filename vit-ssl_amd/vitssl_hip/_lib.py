@@ -9,6 +9,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VITSSL_LIB") or os.path.join(_HERE, "libvitssl_hip.so")   # VITSSL_LIB: developer override (kernel A/B builds)
 HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "vitssl_hip.h"))
 TRANSFORMS_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "vitssl_transforms.h"))
+METRICS_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "vitssl_metrics.h"))
 
 
 class VitsslError(RuntimeError):
@@ -112,6 +113,13 @@ PROTOTYPES_TRANSFORMS = {
     "vitssl_tf_resized_crop_to_tensor": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
 }
 
+# include/vitssl_metrics.h (per-epoch training metrics): launching entry points; their sizing functions
+# vitssl_*_workspace_floats (return a count) are bound in lib() beside the other sizing functions.
+PROTOTYPES_METRICS = {
+    "vitssl_recon_metrics": [_vp, _vp, _vp, _i64, _i, _i, _vp, _i64, _vp],
+    "vitssl_dino_stats": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i64, _vp],
+}
+
 _lib = None
 
 
@@ -126,6 +134,13 @@ def transforms_header_symbols():
     """Entry points declared in include/vitssl_transforms.h."""
     with open(TRANSFORMS_HEADER_PATH) as f:
         txt = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)        # the comments name functions of vitssl_hip.h
+    return sorted(set(re.findall(r"\b(vitssl_[a-z0-9_]+)\s*\(", txt)))
+
+
+def metrics_header_symbols():
+    """Entry points and sizing functions declared in include/vitssl_metrics.h."""
+    with open(METRICS_HEADER_PATH) as f:
+        txt = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)        # the comments name functions in running text
     return sorted(set(re.findall(r"\b(vitssl_[a-z0-9_]+)\s*\(", txt)))
 
 
@@ -170,7 +185,11 @@ def lib():
         getattr(l, getter).argtypes = []
     l.vitssl_debug_tf_tile_rows.restype = C.c_int
     l.vitssl_debug_tf_tile_rows.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
-    for name, args in list(PROTOTYPES.items()) + list(PROTOTYPES_TRANSFORMS.items()):
+    l.vitssl_recon_metrics_workspace_floats.restype = C.c_int64
+    l.vitssl_recon_metrics_workspace_floats.argtypes = [C.c_int64, C.c_int, C.c_int]
+    l.vitssl_dino_stats_workspace_floats.restype = C.c_int64
+    l.vitssl_dino_stats_workspace_floats.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+    for name, args in list(PROTOTYPES.items()) + list(PROTOTYPES_TRANSFORMS.items()) + list(PROTOTYPES_METRICS.items()):
         fn = getattr(l, name)  # AttributeError if the symbol is missing
         fn.restype = C.c_int
         fn.argtypes = args

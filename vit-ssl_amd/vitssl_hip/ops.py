@@ -633,3 +633,40 @@ def tf_resized_crop_to_tensor(src, iparams, out):
     SH, SW = out.shape[2], out.shape[3]
     call("vitssl_tf_resized_crop_to_tensor", _chk(src, torch.uint8, "src"), _chk(iparams, torch.int32, "iparams", (B, TF_IP)),
          _chk(out, F32, "out", (B, 3, SH, SW)), B, H, W, SH, SW, _stream())
+
+
+# ---- per-epoch training metrics (utils/metrics.py of the reference; include/vitssl_metrics.h) ----
+F64 = torch.float64
+
+
+def _vp(t):
+    return C.c_void_p(t.data_ptr())
+
+
+RECON_ACC = 4          # squared error, sum of per-patch SSIM, elements, patches
+DINO_STATS = 8         # n, mean, M2 of the teacher; the same of the student; cosine sum; |center|^2
+
+
+def recon_metrics(pred, target, acc, C, P):
+    """acc f64 [4] += (sum((clamp(pred, 0, 1) - target)^2), sum over patches of the mean SSIM index, elements, patches) of
+    pred / target f32 [n, C*P*P] whose rows are [C, P, P] patches; n == 0 leaves acc untouched."""
+    if pred is None or pred.dim() != 2 or pred.shape[1] != C * P * P:
+        raise L.VitsslError(f"recon_metrics: expected pred [n, {C}*{P}*{P}], got {None if pred is None else tuple(pred.shape)}")
+    n = pred.shape[0]
+    a, b, c = _chk(pred, F32, "pred"), _chk(target, F32, "target", (n, C * P * P)), _chk(acc, F64, "acc", (RECON_ACC,))
+    ws = _tn_workspace(pred.device, int(L.lib().vitssl_recon_metrics_workspace_floats(n, C, P)))      # shared scratch: launches on one stream are ordered
+    call("vitssl_recon_metrics", a, b, c, n, C, P, _vp(ws), ws.numel(), _stream())
+
+
+def dino_stats(teacher, student, center, out):
+    """out f64 [8] = (n, mean, sum((x - mean)^2)) of teacher f32 [G,B,K] and of student f32 [V,B,K], the sum over (g, v, b) of
+    their rows' cosine similarities, and |center|^2 (center f32 [K] or None)."""
+    if teacher is None or teacher.dim() != 3 or student is None or student.dim() != 3:
+        raise L.VitsslError("dino_stats: expected teacher [G,B,K] and student [V,B,K], got "
+                            f"{None if teacher is None else tuple(teacher.shape)} and {None if student is None else tuple(student.shape)}")
+    G, B, K = teacher.shape
+    V = student.shape[0]
+    t, s = _chk(teacher, F32, "teacher"), _chk(student, F32, "student", (V, B, K))
+    c, o = _opt(center, F32, "center", (K,)), _chk(out, F64, "out", (DINO_STATS,))
+    ws = _tn_workspace(teacher.device, int(L.lib().vitssl_dino_stats_workspace_floats(G, V, B, K)))
+    call("vitssl_dino_stats", t, s, c, o, G, V, B, K, _vp(ws), ws.numel(), _stream())
