@@ -1,0 +1,276 @@
+// Classification loss of the supervised / fine-tune step (gfx950): nn.CrossEntropyLoss(mean, ignore_index, label_smoothing)
+// on the padded fp32 output of the classifier GEMM, the zero-padded bf16 d(logits) the head's backward GEMMs read, the bias
+// gradient, the predictions and the epoch counters.  include/vitssl_classify.h declares the entry point and its contract.
+//
+// One wave per row, CL_WAVES rows a workgroup; lane l owns columns 4 l .. 4 l + 3 of every 256-column chunk, so a wave reads
+// a chunk as 64 x 16 bytes and writes its bf16 gradient as 64 x 8 bytes.  All arithmetic is fp64 (the inputs are fp32, so
+// z - max is exact; gfx950 issues vector fp64 at half the fp32 rate and a row of classes is far too short to be bound by
+// it): the bf16 gradient is then the rounded image of the fp64 value and does not flip at rounding boundaries.
+// Sums over rows follow the library's rule (common.h, "deterministic sums"): a row stores its loss and its fp32 gradient in
+// its own slot of the caller's workspace; classify_finish_kernel and vs_reduce_parts add the slots in a fixed order.
+#include "../../include/vitssl_classify.h"
+#include "common.h"
+#include <math.h>
+
+namespace {
+
+constexpr int CL_THREADS = 256;
+constexpr int CL_WAVES = CL_THREADS / 64;
+constexpr int CL_CHUNK = 256;                 // columns a wave covers per step: 64 lanes x 4
+constexpr int CL_NV = 4;                      // chunks a wave keeps in registers: rows of up to 1024 classes
+constexpr int CL_MAX_C = 65536;
+constexpr int CL_MAX_B = 1 << 22;
+
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ int wave_sum_i(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// argmax order: NaN above everything, then the value, then the LOWER index (total, so every lane ends with the same answer)
+__device__ __forceinline__ bool arg_better(float v, int i, float bv, int bi) {
+  const bool vn = v != v, bn = bv != bv;
+  if (vn != bn) return vn;
+  if (!vn && v != bv) return v > bv;
+  return i < bi;
+}
+
+struct ClArgs {
+  const float* logits;
+  const long long* labels;
+  double* row_loss;          // workspace: [B]
+  float* parts;              // workspace: [B, cp] fp32 gradient rows (read by the bias-gradient sum), or nullptr
+  bf16_t* dlogits;           // or nullptr
+  long long* pred;
+  long long ignore_index;
+  double eps, upstream;
+  int B, C, ld, ld_out, cp;
+};
+
+__device__ __forceinline__ bool label_valid(long long l, long long ignore_index, int C) { return l != ignore_index && l >= 0 && l < C; }
+
+// REG: the row's chunks (C <= CL_NV * CL_CHUNK) stay in registers between the passes; otherwise every pass re-reads the row
+template <bool REG>
+__global__ __launch_bounds__(CL_THREADS) void classify_rows_kernel(ClArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * CL_WAVES + (threadIdx.x >> 6);
+  if (row >= a.B) return;                                        // (no barrier below: waves are independent)
+  const int C = a.C;
+  // n_valid: every wave counts the B labels itself (B / 64 coalesced reads), so the gradient's 1 / n_valid needs neither a
+  // launch of its own nor a host read
+  int nv = 0;
+  for (int i = lane; i < a.B; i += 64) nv += label_valid(a.labels[i], a.ignore_index, C) ? 1 : 0;
+  nv = wave_sum_i(nv);
+  const long long lab = a.labels[row];
+  const bool valid = label_valid(lab, a.ignore_index, C);
+  const int y = valid ? (int)lab : -1;                           // -1 matches no column: nothing is indexed by a bad label
+  const float* zr = a.logits + (long long)row * a.ld;
+  const int nk = (C + CL_CHUNK - 1) / CL_CHUNK;
+
+  f32x4 zc[REG ? CL_NV : 1];
+  double ec[REG ? CL_NV : 1][4];
+  // f(k): chunk k holds a column < C (wave-uniform)
+  auto chunks = [&](auto&& f) {
+    if constexpr (REG) {
+      static_for<CL_NV>([&](auto K) {
+        if (K.value < nk) f(K);
+      });
+    } else {
+      for (int k = 0; k < nk; ++k) f(k);
+    }
+  };
+  auto load = [&](auto k) -> f32x4 {
+    const int col = (int)k * CL_CHUNK + lane * 4;
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (col < C) v = *(const f32x4*)(zr + col);                  // ld % 4 == 0 and col < C <= ld: the 16 bytes lie in the row
+    return v;
+  };
+
+  // pass 1: max, argmax, sum of the logits
+  float m = -INFINITY, bv = -INFINITY;
+  int bi = INT_MAX;
+  double zs = 0.0;
+  chunks([&](auto k) {
+    const f32x4 v = load(k);
+    if constexpr (REG) zc[(int)k] = v;
+    const int col = (int)k * CL_CHUNK + lane * 4;
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (col + e < C) {
+        m = fmaxf(m, v[e]);
+        zs += (double)v[e];
+        if (arg_better(v[e], col + e, bv, bi)) bv = v[e], bi = col + e;
+      }
+  });
+  m = wave_max(m);
+  zs = wave_sum_d(zs);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(bv, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    if (arg_better(ov, oi, bv, bi)) bv = ov, bi = oi;
+  }
+
+  // pass 2: exp(z - max); the label's term apart, so that 1 - p[y] is a sum and not a difference
+  const double md = (double)m;
+  double so = 0.0, ey = 0.0, zy = 0.0;
+  chunks([&](auto k) {
+    f32x4 v;
+    if constexpr (REG) v = zc[(int)k]; else v = load(k);
+    const int col = (int)k * CL_CHUNK + lane * 4;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      double x = 0.0;
+      if (col + e < C) {
+        x = exp((double)v[e] - md);
+        if (col + e == y) ey = x, zy = (double)v[e]; else so += x;
+      }
+      if constexpr (REG) ec[(int)k][e] = x;
+    }
+  });
+  so = wave_sum_d(so);
+  ey = wave_sum_d(ey);
+  zy = wave_sum_d(zy);
+  const double s = so + ey;
+  if (lane == 0) {
+    double loss = 0.0;
+    if (valid) {
+      const double ls = ey == 1.0 ? log1p(so) : log(s);         // the label is the row's maximum: s = 1 + so
+      loss = (1.0 - a.eps) * ((md - zy) + ls);
+      if (a.eps > 0.0) loss += a.eps * ((md + log(s)) - zs / (double)C);
+    }
+    a.row_loss[row] = loss;
+    a.pred[row] = bi;
+  }
+  if (!a.dlogits && !a.parts) return;
+
+  // pass 3: the gradient, to the bf16 operand (every column below ld_out) and to the row's slot of the bias-gradient sum
+  const double scale = a.upstream / (double)nv, inv_s = 1.0 / s, sm = a.eps / (double)C;
+  const double gy = (a.eps * (1.0 - 1.0 / (double)C) - so * inv_s) * scale;       // p[y] - (1 - eps) - eps / C
+  bf16_t* dr = a.dlogits ? a.dlogits + (long long)row * a.ld_out : nullptr;
+  float* pr = a.parts ? a.parts + (long long)row * a.cp : nullptr;
+  chunks([&](auto k) {
+    const int col = (int)k * CL_CHUNK + lane * 4;
+    if (col >= C) return;
+    f32x4 g = {0.f, 0.f, 0.f, 0.f};
+    if (valid) {
+      f32x4 v;
+      if constexpr (!REG) v = load(k);
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (col + e < C) {
+          double x;
+          if constexpr (REG) x = ec[(int)k][e]; else x = exp((double)v[e] - md);
+          g[e] = (float)(col + e == y ? gy : (x * inv_s - sm) * scale);
+        }
+    }
+    if (dr) {                                                    // col < C <= ld_out and ld_out % 4 == 0
+      const u32x2 w = {pack_bf2(g[0], g[1]), pack_bf2(g[2], g[3])};
+      *(u32x2*)(dr + col) = w;
+    }
+    if (pr) *(f32x4*)(pr + col) = g;                             // cp = C rounded up to 4
+  });
+  if (dr) {                                                      // the zero padding: columns cp .. ld_out-1 (both multiples of 4)
+    const u32x2 z = {0u, 0u};
+    for (int col = a.cp + lane * 4; col < a.ld_out; col += CL_CHUNK) *(u32x2*)(dr + col) = z;
+  }
+}
+
+// one workgroup: loss_out = {sum of the row losses in a fixed order, n_valid}; counters and bad_labels accumulated
+__global__ __launch_bounds__(CL_THREADS) void classify_finish_kernel(const double* __restrict__ row_loss, const long long* __restrict__ labels,
+                                                                     const long long* __restrict__ pred, long long ignore_index, int B, int C,
+                                                                     float* __restrict__ loss_out, long long* __restrict__ counters,
+                                                                     int* __restrict__ bad_labels) {
+  __shared__ double red[CL_WAVES];
+  __shared__ int cnt[CL_WAVES][3];
+  const int tid = threadIdx.x;
+  double sum = 0.0;
+  int nvalid = 0, ncorrect = 0, nbad = 0;
+  for (int i = tid; i < B; i += CL_THREADS) {
+    const long long l = labels[i];
+    if (label_valid(l, ignore_index, C)) {
+      sum += row_loss[i];
+      ++nvalid;
+      ncorrect += pred[i] == l ? 1 : 0;
+    } else if (l != ignore_index) {
+      ++nbad;
+    }
+  }
+  sum = wave_sum_d(sum);
+  nvalid = wave_sum_i(nvalid);
+  ncorrect = wave_sum_i(ncorrect);
+  nbad = wave_sum_i(nbad);
+  if ((tid & 63) == 0) {
+    red[tid >> 6] = sum;
+    cnt[tid >> 6][0] = nvalid;
+    cnt[tid >> 6][1] = ncorrect;
+    cnt[tid >> 6][2] = nbad;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    const int v = cnt[0][0] + cnt[1][0] + cnt[2][0] + cnt[3][0];
+    loss_out[0] = (float)(((red[0] + red[1]) + red[2]) + red[3]);
+    loss_out[1] = (float)v;
+    counters[0] += cnt[0][1] + cnt[1][1] + cnt[2][1] + cnt[3][1];
+    counters[1] += v;
+    bad_labels[0] += cnt[0][2] + cnt[1][2] + cnt[2][2] + cnt[3][2];
+  }
+}
+
+inline long long cl_cp(int C) { return ((long long)C + 3) / 4 * 4; }
+inline long long cl_loss_floats(int B) { return ((long long)2 * B + 3) / 4 * 4; }   // B doubles, the gradient rows behind them 16-byte aligned
+
+}  // namespace
+
+extern "C" int64_t vitssl_classify_loss_workspace_floats(int B, int C) {
+  if (B < 1 || B > CL_MAX_B || C < 2 || C > CL_MAX_C) return 0;
+  return cl_loss_floats(B) + (long long)B * cl_cp(C);
+}
+
+extern "C" int vitssl_classify_loss(const float* logits, const int64_t* labels, int B, int C, int ld, double label_smoothing,
+                                    int64_t ignore_index, float upstream, float* loss_out, void* dlogits_bf16, int ld_out,
+                                    float* dbias, int64_t* pred, int64_t* counters, int32_t* bad_labels, float* workspace,
+                                    int64_t workspace_floats, void* stream) {
+  VS_CHECK_ARG(logits && labels && loss_out && pred && counters && bad_labels, "classify_loss: null pointer");
+  VS_CHECK_ARG(B >= 1 && B <= CL_MAX_B, "classify_loss: B = %d rows is outside 1 <= B <= 2^22", B);
+  VS_CHECK_ARG(C >= 2 && C <= CL_MAX_C, "classify_loss: C = %d classes is outside 2 <= C <= 65536", C);
+  VS_CHECK_ARG(ld >= C && ld % 4 == 0, "classify_loss: C = %d classes need a row length ld >= C that is a multiple of 4, got ld = %d", C, ld);
+  VS_CHECK_ARG(label_smoothing >= 0.0 && label_smoothing <= 1.0, "classify_loss: label_smoothing = %g is outside 0 <= eps <= 1",
+               label_smoothing);
+  if (dlogits_bf16)
+    VS_CHECK_ARG(ld_out >= C && ld_out % 64 == 0, "classify_loss: dlogits needs a row length ld_out >= C = %d that is a multiple of 64, got ld_out = %d",
+                 C, ld_out);
+  VS_CHECK_ARG((((uintptr_t)logits | (uintptr_t)dlogits_bf16 | (uintptr_t)workspace) & 15) == 0,
+               "classify_loss: logits, dlogits and workspace must be 16-byte aligned");
+  VS_CHECK_ARG((((uintptr_t)labels | (uintptr_t)pred | (uintptr_t)counters) & 7) == 0, "classify_loss: labels, pred and counters must be 8-byte aligned");
+  if (!vs_parts(workspace, workspace_floats, vitssl_classify_loss_workspace_floats(B, C), "classify_loss", "vitssl_classify_loss_workspace_floats"))
+    return VITSSL_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  ClArgs a;
+  a.logits = logits;
+  a.labels = (const long long*)labels;
+  a.row_loss = (double*)workspace;
+  a.parts = dbias ? workspace + cl_loss_floats(B) : nullptr;
+  a.dlogits = (bf16_t*)dlogits_bf16;
+  a.pred = (long long*)pred;
+  a.ignore_index = ignore_index;
+  a.eps = label_smoothing;
+  a.upstream = (double)upstream;
+  a.B = B, a.C = C, a.ld = ld, a.ld_out = ld_out, a.cp = (int)cl_cp(C);
+  const dim3 grid((unsigned)((B + CL_WAVES - 1) / CL_WAVES)), block(CL_THREADS);
+  if (C <= CL_NV * CL_CHUNK)
+    hipLaunchKernelGGL(classify_rows_kernel<true>, grid, block, 0, s, a);
+  else
+    hipLaunchKernelGGL(classify_rows_kernel<false>, grid, block, 0, s, a);
+  VS_CHECK_LAUNCH("classify_loss");
+  hipLaunchKernelGGL(classify_finish_kernel, dim3(1), block, 0, s, (const double*)a.row_loss, a.labels, (const long long*)a.pred, (long long)ignore_index,
+                     B, C, loss_out, (long long*)counters, bad_labels);
+  VS_CHECK_LAUNCH("classify_loss (finish)");
+  if (dbias) return vs_reduce_parts(dbias, a.parts, B, C, a.cp, s);
+  return VITSSL_OK;
+}

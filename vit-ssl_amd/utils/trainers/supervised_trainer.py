@@ -1,20 +1,128 @@
 """Supervised / fine-tune trainer (reference: utils/trainers/supervised_trainer.py:30-48):
-logits = model(x); CrossEntropy; backward; step.  Runs the reference-style autograd path
-through the HIP engine (the supervised config is the reference's small plumbing case).
+logits = model(x); CrossEntropy; backward; step.  By default it runs the reference-style autograd path
+through the HIP engine; with `training.fused_step: true` (and the fused AdamW, a model with `train_step`, and
+nn.CrossEntropyLoss(weight=None, reduction="mean")) every step is `ViT.train_step` / `ViT.eval_step`: loss, backward,
+all-reduce and AdamW as one engine schedule that does only the work the model's frozen state needs, with one host read
+per epoch.  Anything else falls back to the autograd path and says so once.
 Batches are (images, labels); uint8 [B,H,W,3] images are rendered on the GPU (`BaseTrainer._batch`).
 The names of the config's `metrics` (Accuracy, F1Score, Recall, Precision) come from a confusion matrix accumulated on the
 device per batch (utils/gpu_metrics.py); with `Accuracy` listed the best checkpoint is the one with the highest validation
-accuracy, stored as `best_val_acc` (reference :126-138)."""
+accuracy, stored as `best_val_acc` (reference :126-138).
+`training.freeze_backbone` with `freeze_backbone_epochs` (under `training`, else the top-level key the reference reads,
+:16-19): at the start of that epoch the patch embedding and the encoder blocks train again and the optimizer is rebuilt
+with fresh moments (reference :88-90, :120-124).  Deviation, on purpose: the new optimizer takes over the old one's
+current learning rate and the existing schedulers are re-pointed at it; the reference leaves its schedulers driving the
+discarded optimizer, which freezes the learning rate at its initial value."""
 import logging
+import math
 
 import torch
+from torch import nn
 
+from .._config import cfg_get
+from ..train_utils import make_optimizer
 from .base_trainer import BaseTrainer
 
 logger = logging.getLogger(__name__)
 
 
 class SupervisedTrainer(BaseTrainer):
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self._read_schedule_keys()
+        if self.reducer is not None and self._fused_path():
+            self._rebuild_reducer()
+
+    def _read_schedule_keys(self):
+        self.freeze_backbone = bool(cfg_get(self.config, "training", "freeze_backbone", default=False))
+        epochs = cfg_get(self.config, "training", "freeze_backbone_epochs")
+        if epochs is None:
+            epochs = cfg_get(self.config, "freeze_backbone_epochs")
+        self.freeze_backbone_epochs = math.inf if epochs is None else epochs
+        self.fused_step = bool(cfg_get(self.config, "training", "fused_step", default=False))
+        self._fallback_logged = False
+        self._step_counters = None
+
+    # ---- fused path --------------------------------------------------------------
+    def _fused_path(self) -> bool:
+        """training.fused_step, the fused optimizer over a model with train_step, and a criterion the loss kernel implements."""
+        if not getattr(self, "fused_step", False):
+            return False
+        c = self.criterion
+        ok = self._is_fused() and type(c) is nn.CrossEntropyLoss and c.weight is None and c.reduction == "mean"
+        if not ok and not self._fallback_logged:
+            logger.warning("training.fused_step is set, but the fused step needs the fused AdamW, a model with train_step and "
+                           "nn.CrossEntropyLoss(weight=None, reduction='mean'): using the autograd path")
+            self._fallback_logged = True
+        return ok
+
+    def _rebuild_reducer(self):
+        """Data parallel: the reducer expects the gradient ranges of the model's current frozen state."""
+        from vitssl_hip.engine import GradReducer
+        self.reducer = GradReducer(self._dp_store().gflat, expect=self.model.reduce_ranges())
+
+    def _counters(self):
+        """(correct, valid) of the epoch on the device: one host read at its end."""
+        if self._step_counters is None:
+            self._step_counters = torch.zeros(2, dtype=torch.int64, device=self.device)
+        self._step_counters.zero_()
+        return self._step_counters
+
+    def _epoch_values(self, running, total, counters):
+        self.model.check_labels()
+        correct, valid = counters.tolist()
+        loss = float(running) / total if total else float("nan")
+        return {**self._metric_values(), "Loss": loss, "Accuracy": correct / max(valid, 1)}
+
+    def _fused_update_metrics(self, labels):
+        if self.metric_handler is not None:
+            self.metric_handler.update_classification(self.model.last_pred, labels, self.model.num_classes)
+
+    def _train_epoch_fused(self, epoch):
+        c = self.criterion
+        total, running, counters = 0, None, self._counters()
+        for batch in self.train_loader:
+            inputs, labels = self._labelled(batch, "train")
+            loss = self.model.train_step(inputs, labels, self.optimizer, self.reducer, label_smoothing=c.label_smoothing,
+                                         ignore_index=c.ignore_index, counters=counters)
+            self._warmup_step(epoch)
+            running = loss if running is None else running + loss
+            self._fused_update_metrics(labels)
+            total += 1
+        return self._epoch_values(running, total, counters)
+
+    def _validate_fused(self):
+        c = self.criterion
+        total, running, counters = 0, None, self._counters()
+        for batch in self.val_loader:
+            inputs, labels = self._labelled(batch, "val")
+            loss = self.model.eval_step(inputs, labels, label_smoothing=c.label_smoothing, ignore_index=c.ignore_index, counters=counters)
+            running = loss if running is None else running + loss
+            self._fused_update_metrics(labels)
+            total += 1
+        return self._epoch_values(running, total, counters)
+
+    # ---- un-freeze -----------------------------------------------------------------
+    def _maybe_unfreeze(self, epoch):
+        if not getattr(self, "freeze_backbone", False) or epoch != self.freeze_backbone_epochs:
+            return
+        for part in (self.model.patch_embedding, self.model.encoder_blocks):
+            for p in part.parameters():
+                p.requires_grad = True
+        old = self.optimizer
+        self.optimizer = make_optimizer(self.config, self.model)             # fresh moments, as in the reference
+        for new_group, old_group in zip(self.optimizer.param_groups, old.param_groups):
+            new_group["lr"] = old_group["lr"]
+            if "initial_lr" in old_group:
+                new_group["initial_lr"] = old_group["initial_lr"]
+        for scheduler in self.schedulers.values():
+            if scheduler is not None:
+                scheduler.optimizer = self.optimizer
+        if self.reducer is not None and self._fused_path():
+            self._rebuild_reducer()
+        logger.info("epoch %d: backbone un-frozen, optimizer rebuilt at lr %g", epoch, self.optimizer.param_groups[0]["lr"])
+
+    # ---- reference-style path ----------------------------------------------------
     def _labelled(self, batch, split):
         inputs, labels = self._batch(batch, split, non_blocking=False)
         if labels is None:
@@ -32,6 +140,9 @@ class SupervisedTrainer(BaseTrainer):
 
     def train_epoch(self, epoch: int):
         self.model.train()
+        self._maybe_unfreeze(epoch)
+        if self._fused_path():
+            return self._train_epoch_fused(epoch)
         total, correct, seen, running = 0, 0, 0, None
         for idx, batch in enumerate(self.train_loader):
             inputs, labels = self._labelled(batch, "train")
@@ -51,6 +162,8 @@ class SupervisedTrainer(BaseTrainer):
 
     def validate(self):
         self.model.eval()
+        if self._fused_path():
+            return self._validate_fused()
         total, correct, seen, running = 0, 0, 0, None
         with torch.no_grad():
             for idx, batch in enumerate(self.val_loader):

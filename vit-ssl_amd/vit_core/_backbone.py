@@ -68,8 +68,10 @@ class BackboneRuntime:
             self.rec[slot] = dict(B=B, T=T, tokens=tokens, patches=patches, pos_graph=pos_graph)
         return feats, probs
 
-    def backward(self, dfeats, slot: str, reducer=None):
-        """dfeats: fp32 [B, D] gradient wrt the CLS features; accumulates parameter grads."""
+    def backward(self, dfeats, slot: str, reducer=None, input_grad_only=False, proj_wgrad=True):
+        """dfeats: fp32 [B, D] gradient wrt the CLS features; accumulates parameter grads.
+        `input_grad_only`: the blocks are frozen (EncoderStack.backward); `proj_wgrad=False`: so is the patch projection,
+        its weight-gradient GEMM is not launched."""
         st, ws = self.store, self.ws
         rec = self.rec[slot]
         B, T, tokens = rec["B"], rec["T"], rec["tokens"]
@@ -77,7 +79,7 @@ class BackboneRuntime:
         gv = st.gview
         g = ws.get(f"{slot}.g", (B * T, self.D), F32, dev)
         ops.scatter_cls_f32(R.as_f32(dfeats), g, B, T, self.D)
-        g = self.stack.backward(g, slot=slot, reducer=reducer)
+        g = self.stack.backward(g, slot=slot, reducer=reducer, input_grad_only=input_grad_only)
         dproj = ws.get(f"{slot}.dproj", (B * tokens, self.D), BF16, dev)
         if rec["pos_graph"] is None:
             dpos = gv(self.names["pos"], (T, self.D))
@@ -89,6 +91,7 @@ class BackboneRuntime:
             gpos = gv(self.names["pos"], (self.T0, self.D))
             gpos[0].add_(dpos[0])                               # CLS row: identity
             ops.bicubic_resize_bwd(dpos[1:], gpos[1:], self.grid[0], self.grid[1], gh, gw)
-        ops.gemm_tn(dproj, rec["patches"], gv(self.names["weight"], (self.D, self.Pd)))
+        if proj_wgrad:
+            ops.gemm_tn(dproj, rec["patches"], gv(self.names["weight"], (self.D, self.Pd)))
         # the CLS position also receives the CLS-row gradient through `cls + pos[0]`:
         # embed_bwd already added row 0 of every image to dpos[0] and to dcls.

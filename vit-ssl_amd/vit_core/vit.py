@@ -1,5 +1,11 @@
 """Supervised ViT (reference: vit_core/vit.py:9-45): ConvolutionalPatchEmbedding ->
-encoder blocks -> CLS token -> MLPHead, run as one engine schedule on a flat store."""
+encoder blocks -> CLS token -> MLPHead, run as one engine schedule on a flat store.
+
+Two ways to train, as for SimMIMViT:
+  * reference style: ``loss = criterion(model(x), y); loss.backward()`` (one torch.autograd.Function around the engine);
+  * fused: ``loss = model.train_step(x, y, optimizer, reducer)`` -- cross-entropy (csrc/classify.hip), backward into the flat
+    gradient buffer, overlapped all-reduce and flat AdamW with no autograd graph; ``model.eval_step(x, y)`` is its no-grad
+    half.  The backward does only what the parameters' `requires_grad` asks for (`_ViTRuntime.schedule`)."""
 import torch
 from torch import nn
 from torch.autograd import Function
@@ -31,6 +37,13 @@ class _ViTRuntime:
         self.ncls = model.num_classes
         self.rec = None
         self.save_gen = 0
+        # fused step
+        self.ws = R.Workspace()
+        self.frec = None                  # what the fused forward keeps for its backward
+        self._head = None                 # cached GEMM operands of the classifier (head_operands)
+        self._head_key = None
+        self.counters = torch.zeros(2, dtype=torch.int64, device=device)      # (correct, valid) when the caller brings none
+        self.bad_labels = torch.zeros(1, dtype=torch.int32, device=device)    # labels outside [0, C) seen so far
 
     def valid_for(self, device):
         return device == self.device and self.store.is_attached()
@@ -90,6 +103,109 @@ class _ViTRuntime:
         self.bb.backward(dfeats, "a", reducer)
         if reducer is not None:
             reducer.ready(*st.span("patch_embedding.cls_token", "patch_embedding.conv.bias"))
+
+
+    # ------------------------------------------------------------------ fused step
+    HEAD_SPAN = ("classification_head.norm.weight", "classification_head.linear.bias")
+    EMBED_SPAN = ("patch_embedding.cls_token", "patch_embedding.conv.bias")
+
+    def schedule(self) -> str:
+        """Which backward the parameters' requires_grad asks for (read at every call; about 150 flags):
+        "full": an encoder-block parameter trains -- the schedule of `backward`;
+        "input_grad": the blocks are frozen and something below them trains (utils.model_builder.freeze_backbone leaves the
+            CLS token trainable) -- the input-gradient chain without the blocks' weight-gradient GEMMs (bf16 operands; with
+            fp8 operands this case runs the full schedule);
+        "head": nothing below the classification head trains -- the backbone forward saves nothing and the backward ends
+            after the head's LayerNorm."""
+        blocks = below = False
+        for n, p in zip(self.store.names, self.store.params):
+            if not p.requires_grad:
+                continue
+            if n.startswith("encoder_blocks."):
+                blocks = True
+                break
+            below = below or n.startswith("patch_embedding.")
+        if blocks or (below and self.bb.stack.fp8):
+            return "full"
+        return "input_grad" if below else "head"
+
+    def reduce_ranges(self):
+        """The ranges of the flat gradient buffer one fused backward hands to a GradReducer in the current frozen state:
+        None = the whole buffer (full schedule), else the list for GradReducer(expect=...)."""
+        sched, st = self.schedule(), self.store
+        if sched == "full":
+            return None
+        head = st.span(*self.HEAD_SPAN)
+        return [head] if sched == "head" else [st.span(*self.EMBED_SPAN), head]
+
+    def head_operands(self):
+        """(bf16 classifier weight [Nk, D] zero-padded to the GEMM granule, its transpose [D, Nk], padded fp32 bias [Nk], Nk),
+        rebuilt only when the store's weights_key() has changed."""
+        st, D, C = self.store, self.D, self.ncls
+        key = st.weights_key()
+        if self._head is None:
+            Nk = _round_up(C, 64)
+            self._head = dict(w32=torch.zeros(Nk, D, dtype=F32, device=self.device), wb=torch.empty(Nk, D, dtype=BF16, device=self.device),
+                              wt=torch.empty(D, Nk, dtype=BF16, device=self.device), bias=torch.zeros(Nk, dtype=F32, device=self.device), Nk=Nk)
+            self._head_key = None
+        hd = self._head
+        if key != self._head_key:
+            hd["w32"][:C].copy_(st.view("classification_head.linear.weight", (C, D)))
+            hd["bias"][:C].copy_(st.view("classification_head.linear.bias"))
+            ops.cast_transpose_bf16(hd["w32"], hd["wb"], hd["wt"])
+            self._head_key = key
+        return hd["wb"], hd["wt"], hd["bias"], hd["Nk"]
+
+    def fused_forward(self, x, training, save_backbone, tag):
+        """-> padded logits f32 [B, Nk] and the head's saved tensors.  `tag` separates the buffers of a forward that saves
+        nothing (eval_step) from those a pending backward still needs."""
+        st, g = self.store, self.ws.get
+        st.refresh_weights()
+        seed = R.next_seed() if (training and self.bb.stack.p > 0) else 0
+        feats, _ = self.bb.forward(x, training, seed, save=save_backbone, slot="a")
+        B, dev = feats.shape[0], feats.device
+        h = g(tag + "h", (B, self.D), BF16, dev)
+        mean, rstd = g(tag + "mean", (B,), F32, dev), g(tag + "rstd", (B,), F32, dev)
+        ops.layernorm_fwd(feats, st.view("classification_head.norm.weight"), st.view("classification_head.norm.bias"), h, mean, rstd)
+        wb, wt, bias, Nk = self.head_operands()
+        logits = g(tag + "logits", (B, Nk), F32, dev)
+        ops.gemm_nt(h, wb, logits, L.EPI_F32, bias=bias)
+        return logits, dict(feats=feats, h=h, mean=mean, rstd=rstd, wt=wt, Nk=Nk, B=B)
+
+    def fused_loss(self, logits, labels, tag, label_smoothing, ignore_index, counters, dlogits=None, dbias=None):
+        """csrc/classify.hip on the padded logits -> (loss as a device scalar, pred i64 [B])."""
+        B, dev = logits.shape[0], logits.device
+        if labels.dtype != torch.int64 or not labels.is_contiguous():
+            labels = labels.to(torch.int64).contiguous()
+        loss_out = self.ws.get(tag + "loss_out", (2,), F32, dev)
+        pred = self.ws.get(tag + "pred", (B,), torch.int64, dev)
+        ops.classify_loss(logits, labels, self.ncls, loss_out, pred, self.counters if counters is None else counters, self.bad_labels,
+                          dlogits=dlogits, dbias=dbias, label_smoothing=label_smoothing, ignore_index=ignore_index)
+        return loss_out[0] / loss_out[1], pred         # 0 / 0 = nan when every row is ignored, as torch gives
+
+    def fused_backward(self, rec, dlb, sched, reducer=None):
+        """dlb: bf16 [B, Nk] from the loss kernel (which has already accumulated the classifier's bias gradient)."""
+        st, g = self.store, self.ws.get
+        B, Nk, C, D = rec["B"], rec["Nk"], self.ncls, self.D
+        dev = dlb.device
+        gv = st.gview
+        dw = g("head.dw", (Nk, D), F32, dev)
+        dw.zero_()
+        ops.gemm_tn(dlb, rec["h"], dw)
+        gv("classification_head.linear.weight", (C, D)).add_(dw[:C])
+        dh = g("head.dh", (B, D), BF16, dev)
+        ops.gemm_nt(dlb, rec["wt"], dh, L.EPI_BF16)
+        dfeats = g("head.dfeats", (B, D), F32, dev)
+        ops.layernorm_bwd(dh, rec["feats"], rec["mean"], rec["rstd"], st.view("classification_head.norm.weight"), None, dfeats,
+                          None, gv("classification_head.norm.weight"), gv("classification_head.norm.bias"))
+        if reducer is not None:
+            reducer.ready(*st.span(*self.HEAD_SPAN))
+        if sched == "head":
+            return
+        proj = sched == "full" or self.model.patch_embedding.conv.weight.requires_grad
+        self.bb.backward(dfeats, "a", reducer, input_grad_only=sched == "input_grad", proj_wgrad=proj)
+        if reducer is not None:
+            reducer.ready(*st.span(*self.EMBED_SPAN))
 
 
 class _ViTFn(Function):
@@ -156,3 +272,64 @@ class ViT(nn.Module):
         if return_attn:
             return logits, probs
         return logits
+
+    # ------------------------------------------------------------------ fused step
+    def reduce_ranges(self):
+        """`expect` of the GradReducer that fits the model's current frozen state (None: the whole gradient buffer)."""
+        return self.runtime().reduce_ranges()
+
+    def check_labels(self):
+        """Raise if a fused step has seen a label outside [0, num_classes) that was not the ignore_index (the kernel treats
+        such a row as ignored and counts it on the device).  One host read: call it once per epoch."""
+        rt = self.runtime()
+        n = int(rt.bad_labels.item())
+        if n:
+            rt.bad_labels.zero_()
+            raise L.VitsslError(f"ViT: {n} label(s) outside [0, {self.num_classes}) reached train_step / eval_step; their rows were ignored")
+
+    def train_step(self, x: torch.Tensor, labels: torch.Tensor, optimizer, reducer=None, label_smoothing: float = 0.0,
+                   ignore_index: int = -100, counters=None) -> torch.Tensor:
+        """One full optimisation step (zero_grad -> forward -> CrossEntropyLoss(mean, label_smoothing, ignore_index) ->
+        backward -> gradient all-reduce -> AdamW) with no autograd graph; returns the loss as a device scalar (no host sync).
+        Equivalent to utils/trainers/supervised_trainer.py:33-40 of the reference.  Leaves `last_logits` ([B, C] view of the
+        padded GEMM output) and `last_pred` (i64 [B]) on the model; `counters` (i64 [2] on the device, default: the
+        runtime's own) accumulates (correct, valid) rows."""
+        R.require_gpu(x, "ViT.train_step")
+        rt = self.runtime(x.device)
+        st = rt.store
+        if getattr(self, "_pacer", None) is None:
+            object.__setattr__(self, "_pacer", R.StepPacer())
+        self._pacer.begin_step()
+        with torch.no_grad():
+            sched = rt.schedule()
+            st.gflat.zero_()
+            if reducer is not None:
+                reducer.begin()
+            if sched == "head":                        # nothing below the head trains: no activations are kept
+                rt.bb.rec.pop("a", None)
+                rt.bb.stack._saved.pop("a", None)
+            logits, rec = rt.fused_forward(x, True, sched != "head", "head.")
+            dlb = rt.ws.get("head.dlogits", tuple(logits.shape), BF16, x.device)
+            loss, pred = rt.fused_loss(logits, labels, "head.", label_smoothing, ignore_index, counters, dlogits=dlb,
+                                       dbias=st.gview("classification_head.linear.bias"))
+            rt.fused_backward(rec, dlb, sched, reducer)
+            gscale = 1.0
+            if reducer is not None:
+                reducer.finish()
+                gscale = reducer.grad_scale
+            optimizer.step_flat(gscale)
+            self.last_logits, self.last_pred = logits[:, :self.num_classes], pred
+            self._pacer.end_step()
+            return loss
+
+    @torch.no_grad()
+    def eval_step(self, x: torch.Tensor, labels: torch.Tensor, label_smoothing: float = 0.0, ignore_index: int = -100,
+                  counters=None) -> torch.Tensor:
+        """The no-grad half of train_step: forward in eval mode (no dropout) and the loss kernel without a gradient.  Saves
+        nothing and leaves the buffers of a pending backward alone; same `last_logits`, `last_pred` and counters."""
+        R.require_gpu(x, "ViT.eval_step")
+        rt = self.runtime(x.device)
+        logits, _ = rt.fused_forward(x, False, False, "head.tmp.")
+        loss, pred = rt.fused_loss(logits, labels, "head.tmp.", label_smoothing, ignore_index, counters)
+        self.last_logits, self.last_pred = logits[:, :self.num_classes], pred
+        return loss

@@ -10,6 +10,7 @@ LIB_PATH = os.environ.get("VITSSL_LIB") or os.path.join(_HERE, "libvitssl_hip.so
 HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "vitssl_hip.h"))
 TRANSFORMS_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "vitssl_transforms.h"))
 METRICS_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "vitssl_metrics.h"))
+CLASSIFY_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "vitssl_classify.h"))
 
 
 class VitsslError(RuntimeError):
@@ -120,6 +121,12 @@ PROTOTYPES_METRICS = {
     "vitssl_dino_stats": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i64, _vp],
 }
 
+# include/vitssl_classify.h (classification loss of the supervised / fine-tune step): the launching entry point; its sizing
+# function vitssl_classify_loss_workspace_floats (returns a count) is bound in lib() beside the other sizing functions.
+PROTOTYPES_CLASSIFY = {
+    "vitssl_classify_loss": [_vp, _vp, _i, _i, _i, C.c_double, _i64, _f, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
+}
+
 _lib = None
 
 
@@ -140,6 +147,13 @@ def transforms_header_symbols():
 def metrics_header_symbols():
     """Entry points and sizing functions declared in include/vitssl_metrics.h."""
     with open(METRICS_HEADER_PATH) as f:
+        txt = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)        # the comments name functions in running text
+    return sorted(set(re.findall(r"\b(vitssl_[a-z0-9_]+)\s*\(", txt)))
+
+
+def classify_header_symbols():
+    """Entry points and sizing functions declared in include/vitssl_classify.h."""
+    with open(CLASSIFY_HEADER_PATH) as f:
         txt = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)        # the comments name functions in running text
     return sorted(set(re.findall(r"\b(vitssl_[a-z0-9_]+)\s*\(", txt)))
 
@@ -189,7 +203,10 @@ def lib():
     l.vitssl_recon_metrics_workspace_floats.argtypes = [C.c_int64, C.c_int, C.c_int]
     l.vitssl_dino_stats_workspace_floats.restype = C.c_int64
     l.vitssl_dino_stats_workspace_floats.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
-    for name, args in list(PROTOTYPES.items()) + list(PROTOTYPES_TRANSFORMS.items()) + list(PROTOTYPES_METRICS.items()):
+    l.vitssl_classify_loss_workspace_floats.restype = C.c_int64
+    l.vitssl_classify_loss_workspace_floats.argtypes = [C.c_int, C.c_int]
+    for name, args in (list(PROTOTYPES.items()) + list(PROTOTYPES_TRANSFORMS.items()) + list(PROTOTYPES_METRICS.items())
+                       + list(PROTOTYPES_CLASSIFY.items())):
         fn = getattr(l, name)  # AttributeError if the symbol is missing
         fn.restype = C.c_int
         fn.argtypes = args

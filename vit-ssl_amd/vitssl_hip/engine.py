@@ -263,11 +263,13 @@ class GradReducer:
     >= `bucket_elems` and all-reduced (sum) on a side stream.  The 1/world factor is
     folded into the optimizer kernel.  On CPU tensors (gloo, tests) it runs inline."""
 
-    def __init__(self, gflat: torch.Tensor, group=None, bucket_mb: float = 32.0, expect: Optional[Tuple[int, int]] = None,
+    def __init__(self, gflat: torch.Tensor, group=None, bucket_mb: float = 32.0, expect=None,
                  reserve_cus: int = RESERVED_CUS_DEFAULT):
         """`expect` = (lo, hi) range of the flat buffer that one backward must hand over exactly once
         (default: the whole buffer); finish() checks it, so a schedule change that forgets or repeats a
-        range fails loudly on one GPU instead of silently de-synchronising replicas on eight."""
+        range fails loudly on one GPU instead of silently de-synchronising replicas on eight.
+        A LIST of (lo, hi) ranges (the trainable spans of a partly frozen model, ViT.reduce_ranges) is checked as exactly
+        those: every one handed over once and nothing outside them."""
         import torch.distributed as dist
         self.dist = dist
         self.gflat = gflat
@@ -362,6 +364,8 @@ class GradReducer:
     def _assert_covered(self):
         """Every element of the expected range was handed over exactly once (alignment padding between
         parameters may be skipped: it is never read)."""
+        if isinstance(self.expect, list):
+            return self._assert_covered_ranges()
         pos = self.expect[0]
         for lo, hi in sorted(self.launched):
             if lo < pos:
@@ -371,6 +375,35 @@ class GradReducer:
             pos = hi
         if self.expect[1] - pos >= ALIGN:
             raise L.VitsslError(f"GradReducer: gradient range [{pos}, {self.expect[1]}) was never handed to the reducer")
+
+    @staticmethod
+    def _minus(a, b):
+        """the pieces of the ranges `a` that the sorted ranges `b` do not cover (alignment padding does not count)"""
+        out = []
+        for lo, hi in sorted(a):
+            pos = lo
+            for blo, bhi in b:
+                if bhi <= pos or blo >= hi:
+                    continue
+                if blo - pos >= ALIGN:
+                    out.append((pos, blo))
+                pos = max(pos, bhi)
+            if hi - pos >= ALIGN:
+                out.append((pos, hi))
+        return out
+
+    def _assert_covered_ranges(self):
+        """`expect` is a list: every range of the list was handed over once, and nothing outside the list."""
+        got, want = sorted(self.launched), sorted(self.expect)
+        pos = None
+        for lo, hi in got:
+            if pos is not None and lo < pos:
+                raise L.VitsslError(f"GradReducer: gradient range [{lo}, {hi}) was reduced twice (previous range ended at {pos})")
+            pos = hi
+        for lo, hi in self._minus(want, got):
+            raise L.VitsslError(f"GradReducer: gradient range [{lo}, {hi}) was never handed to the reducer")
+        for lo, hi in self._minus(got, want):
+            raise L.VitsslError(f"GradReducer: gradient range [{lo}, {hi}) is outside the expected ranges {want}")
 
     def stats(self):
         """(number of buckets, bytes) of the last step."""
@@ -515,12 +548,16 @@ class EncoderStack:
 
     # backward ---------------------------------------------------------------
     def backward(self, g: torch.Tensor, slot: str = "a", reducer: Optional[GradReducer] = None,
-                 scale_key: Optional[str] = None) -> torch.Tensor:
+                 scale_key: Optional[str] = None, input_grad_only: bool = False) -> torch.Tensor:
         """g: fp32 [M, D] gradient wrt the stack output (overwritten in place; returned
         holding the gradient wrt the stack input).  Parameter gradients are ACCUMULATED
         into the store's flat gradient buffer.  `scale_key` (fp8 operands only) names the delayed-scaling state this pass
         uses; default = the slot, i.e. one state per kind of pass (callers that merely rotate slot names over the same kind
-        of pass -- vit_core._functions.StackRunner -- pass one fixed key)."""
+        of pass -- vit_core._functions.StackRunner -- pass one fixed key).
+        `input_grad_only` (bf16 operands; every block parameter frozen): the input-gradient chain runs as always, no
+        weight-gradient GEMM is launched and no block range is handed to the reducer.  The per-column sums the chain's kernels
+        write anyway (bias and LayerNorm gradients) still land in the blocks' slots of the gradient buffer; nothing applies
+        them.  With fp8 operands the full schedule runs."""
         if self.fp8:
             return self._backward_fp8(g, slot, reducer, scale_key or slot)
         st, D, H, F, dh = self.store, self.D, self.H, self.F, self.dh
@@ -542,7 +579,8 @@ class EncoderStack:
         # gradient operands must then all be alive at that point: the LayerNorm-2 backward writes its bf16 image into a second
         # buffer (gm2) instead of over gm.  VITSSL_TN_BATCH=0: one launch per gradient, as before.
         batch = _os.environ.get("VITSSL_TN_BATCH", "1") != "0"
-        gm2 = w(bw + "gm2", (M, D), BF16, dev) if batch else gm
+        wgrad = not input_grad_only
+        gm2 = w(bw + "gm2", (M, D), BF16, dev) if batch and wgrad else gm
         # top of the chain: dropout-mask + cast of g, and the last block's linear_out bias grad
         ops.grad_mask_cast(g, gm, gv(self._n(last, "feed_forward.linear_out.bias")), self._drop(last, 2, seed, training))
         for i in range(last, -1, -1):
@@ -555,23 +593,23 @@ class EncoderStack:
                       (dqkv, s["h1"], st.span_view(a_ + "w_query.weight", a_ + "w_value.weight", (3 * D, D), grad=True))]
             ops.gemm_nt(gm, st.w(self._n(i, "w2") + ".T"), du, L.EPI_DGELU, aux=s["u"],
                         colsum=gv(self._n(i, "feed_forward.linear_in.bias")))   # s["u"] holds g' = keep*scale*gelu'(u)
-            if not batch:
+            if wgrad and not batch:
                 ops.gemm_tn(*wgrads[0])
             ops.gemm_nt(du, st.w(self._n(i, "w1") + ".T"), dh_, L.EPI_BF16)
-            if not batch:
+            if wgrad and not batch:
                 ops.gemm_tn(*wgrads[1])
             ops.layernorm_bwd(dh_, s["xmid"], s["mean2"], s["rstd2"], st.view(self._n(i, "layer_norm2.weight")), g, g, gm2,
                               gv(self._n(i, "layer_norm2.weight")), gv(self._n(i, "layer_norm2.bias")), None,
                               self._drop(i, 0, seed, training))
             # attention
             ops.gemm_nt(gm2, st.w(self._n(i, "wo") + ".T"), dh_, L.EPI_BF16)
-            if not batch:
+            if wgrad and not batch:
                 ops.gemm_tn(*wgrads[2])
             ops.attn_bwd(s["qkv"], s["att"], dh_, s["lse"], dqkv, delta, B, T, H, dh)
             ops.gemm_nt(dqkv, st.w(self._n(i, "wqkv") + ".T"), dh_, L.EPI_BF16)
-            if batch:
+            if wgrad and batch:
                 ops.gemm_tn_batch(wgrads)      # before the LayerNorm-1 backward below overwrites gm for the next block
-            else:
+            elif wgrad:
                 ops.gemm_tn(*wgrads[3])
             if i > 0:
                 ops.layernorm_bwd(dh_, s["xin"], s["mean1"], s["rstd1"], st.view(self._n(i, "layer_norm1.weight")), g, g, gm,
@@ -580,7 +618,7 @@ class EncoderStack:
             else:
                 ops.layernorm_bwd(dh_, s["xin"], s["mean1"], s["rstd1"], st.view(self._n(i, "layer_norm1.weight")), g, g, None,
                                   gv(self._n(i, "layer_norm1.weight")), gv(self._n(i, "layer_norm1.bias")), None, ops.NO_DROP)
-            if reducer is not None:
+            if reducer is not None and wgrad:
                 # every gradient of block i is final, except linear_out.bias of block i-1,
                 # which belongs to the next (lower) range
                 lo, hi = self.block_span(i)

@@ -670,3 +670,34 @@ def dino_stats(teacher, student, center, out):
     c, o = _opt(center, F32, "center", (K,)), _chk(out, F64, "out", (DINO_STATS,))
     ws = _tn_workspace(teacher.device, int(L.lib().vitssl_dino_stats_workspace_floats(G, V, B, K)))
     call("vitssl_dino_stats", t, s, c, o, G, V, B, K, _vp(ws), ws.numel(), _stream())
+
+
+# ---- classification loss of the supervised / fine-tune step (include/vitssl_classify.h) ----
+I64, I32 = torch.int64, torch.int32
+
+
+def classify_loss(logits, labels, C, loss_out, pred, counters, bad_labels, dlogits=None, dbias=None, label_smoothing=0.0,
+                  ignore_index=-100, upstream=1.0, workspace=None):
+    """nn.CrossEntropyLoss(mean, ignore_index, label_smoothing) on the first C columns of logits f32 [B, ld] (the padded
+    classifier GEMM output): loss_out f32 [2] = (sum of the valid rows' losses, n_valid), overwritten; pred i64 [B] = argmax;
+    counters i64 [2] += (correct, valid); bad_labels i32 [1] += labels outside [0, C) that are not ignore_index.  With
+    dlogits bf16 [B, ld_out] (ld_out % 64 == 0): the zero-padded gradient scaled by upstream / n_valid; dbias f32 [C] += its
+    column sums.  `workspace`: f32, at least vitssl_classify_loss_workspace_floats(B, C) (default: the shared scratch)."""
+    if logits is None or logits.dim() != 2 or not 2 <= int(C) <= logits.shape[1]:
+        raise L.VitsslError(f"classify_loss: expected logits [B, ld] with 2 <= C = {C} <= ld, got {None if logits is None else tuple(logits.shape)}")
+    B, ld = logits.shape
+    ld_out = 0
+    if dlogits is not None:
+        if dlogits.dim() != 2 or dlogits.shape[0] != B or dlogits.shape[1] % 64 != 0 or dlogits.shape[1] < C:
+            raise L.VitsslError(f"classify_loss: dlogits must be [{B}, ld_out] with ld_out % 64 == 0 and ld_out >= {C}, got {tuple(dlogits.shape)}")
+        ld_out = dlogits.shape[1]
+    z, y = _chk(logits, F32, "logits"), _chk(labels, I64, "labels", (B,))
+    lo, pr = _chk(loss_out, F32, "loss_out", (2,)), _chk(pred, I64, "pred", (B,))
+    ct, bl = _chk(counters, I64, "counters", (2,)), _chk(bad_labels, I32, "bad_labels", (1,))
+    dl, db = _opt(dlogits, BF16, "dlogits"), _opt(dbias, F32, "dbias", (C,))
+    need = int(L.lib().vitssl_classify_loss_workspace_floats(B, C))
+    ws = _tn_workspace(logits.device, need) if workspace is None else workspace      # shared scratch: launches on one stream are ordered
+    if workspace is not None:
+        _chk(ws, F32, "workspace")
+    call("vitssl_classify_loss", z, y, B, int(C), ld, float(label_smoothing), int(ignore_index), float(upstream), lo, dl, ld_out, db,
+         pr, ct, bl, _vp(ws), ws.numel(), _stream())
