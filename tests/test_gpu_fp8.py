@@ -182,10 +182,13 @@ def test_attention_fwd_fp8_image():
     assert float(same) > 0.95    # expected ~0.97: 1 in 2^5 values sits where the two roundings disagree
 
 
-def test_attention_bwd_fp8_image():
+# one or two lengths per backward kernel: fused (37: NS = 2, two waves; 128: NS = 4, full last tile), persistent (197),
+# pipelined (225: one row in the last tile; 256: full).  All three share one e4m3 epilogue (csrc/attention_bwd.h).
+@pytest.mark.parametrize("N", [37, 128, 197, 225, 256])
+def test_attention_bwd_fp8_image(N):
     from vitssl_hip import ops
     torch.manual_seed(5)
-    B, N, H, dh = 2, 197, 3, 64
+    B, H, dh = 2, 3, 64
     qkv = torch.randn(B * N, 3 * H * dh).to(torch.bfloat16).to(DEV)
     out = torch.empty(B * N, H * dh, dtype=torch.bfloat16, device=DEV)
     lse = torch.empty(B, H, N, device=DEV)
@@ -203,6 +206,12 @@ def test_attention_bwd_fp8_image():
     same = (d8.cpu().view(torch.uint8) == _q8_torch(d1.cpu().float() * 2.0 ** 13).view(torch.uint8)).float().mean()
     assert float(same) > 0.95
     assert rel_l2(_f32(d8) / 2.0 ** 13, d1) < 4e-2
+    # without the bf16 image (the engine's calls after its first backward): the same e4m3 image and maximum, bit for bit
+    d8n = torch.empty_like(d8)
+    amaxn = torch.zeros(1, device=DEV)
+    ops.attn_bwd(qkv, out, dout, lse, None, delta, B, N, H, dh, dqkv_fp8=d8n, scale=scale, amax=amaxn)
+    assert torch.equal(d8n.view(torch.uint8), d8.view(torch.uint8))
+    assert torch.equal(amaxn.view(torch.int32), amax.view(torch.int32))
 
 
 SHAPES = [(300, 128, 128), (1000, 384, 256), (517, 264, 1024), (4096, 512, 512)]   # N % 8 == 0 (fp8 operands); ragged M, N

@@ -29,6 +29,7 @@
 #include <stdlib.h>
 #include "common.h"
 #include "attention_tiles.h"
+#include "attention_bwd.h"
 
 #ifdef VITSSL_ATTN_STAMPS
 __device__ unsigned long long* g_attn_stamps = nullptr;   // [workgroup][4] x 100 MHz ticks (tools/attn_stamps.py)
@@ -44,7 +45,7 @@ __device__ unsigned long long* g_attn_stamps = nullptr;   // [workgroup][4] x 10
 
 namespace {
 
-using namespace vitssl_attn;   // tile layout and fragment helpers (attention_tiles.h)
+using namespace vitssl_attn;   // tile layout and fragment helpers (attention_tiles.h), shared backward parts (attention_bwd.h)
 
 // Start-up stagger (developer knob VITSSL_ATTN_STAGGER, in 10 ns ticks; 0 = off).  Every workgroup
 // is load -> compute -> store on equal work, so the chip runs the three phases in lock-step: the load phase
@@ -526,7 +527,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_bwd_fused_kernel(const bf16_t
                                                              const float* __restrict__ qscale, float* qamax) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int Np = 32 * NS;
-  constexpr int SROW = Np * 2 + 16;
+  constexpr int SROW = SX_ROW<NS>;
   // fp8 path: dq8 = e4m3(dqkv * *qscale) written next to the bf16 image, max |dqkv| recorded in *qamax
   const float qsc = (dq8 && qscale) ? *qscale : 1.0f;
   float qmax = 0.f;
@@ -566,8 +567,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_bwd_fused_kernel(const bf16_t
 #pragma unroll
     for (int kt = 0; kt < 2; ++kt) {
       const int key = wave * 32 + kt * 16 + li;
-      const float mi = key < N ? 0.f : -INFINITY;   // masked keys: scores start at -inf -> p = dS = 0
-      kinit[kt] = f32x4{mi, mi, mi, mi};
+      kinit[kt] = key_mask_init1(key, N);
 #pragma unroll
       for (int kk = 0; kk < 2; ++kk) vf[kt][kk] = glb_frag(vg, stride, key, kk, N, lane);
     }
@@ -612,13 +612,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_bwd_fused_kernel(const bf16_t
 
   const f32x4 c4 = {SCALE_LOG2E, SCALE_LOG2E, SCALE_LOG2E, SCALE_LOG2E}, sc4 = {SCALE, SCALE, SCALE, SCALE};
   f32x4 dv[4][2], dk[4][2];
-#pragma unroll
-  for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-    for (int kt = 0; kt < 2; ++kt) {
-      dv[dt][kt] = f32x4{0.f, 0.f, 0.f, 0.f};
-      dk[dt][kt] = dv[dt][kt];
-    }
+  zero_dkdv(dk, dv);
   // dQ^T[d][q] = sum_key K[key][d] dS[q][key]: the 8 tiles (2 query tiles x 4 column slices) of
   // a 32-query step are dealt round-robin to the NW waves (NW = 4: a wave gets both query
   // tiles of one column slice).  Two accumulators halve the dependent-MFMA chain.
@@ -750,11 +744,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_bwd_fused_kernel(const bf16_t
       }
     }
   }
-  if (dq8 && qamax) {
-    qmax = wave_max(qmax);
-    unsigned* slot = (unsigned*)qamax;
-    if (lane == 0 && __float_as_uint(qmax) > __builtin_nontemporal_load(slot)) atomicMax(slot, __float_as_uint(qmax));
-  }
+  if (dq8 && qamax) publish_amax(qmax, qamax, lane);
 #ifdef VITSSL_ATTN_STAMPS
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
@@ -778,11 +768,6 @@ __device__ __forceinline__ void dma_rows8(__amdgpu_buffer_rsrc_t rs, char* lds_r
   const unsigned voff = (unsigned)((long long)(grow0 + rl) * stride * 2 + sc * 16);
   dma16_to_lds(rs, lds_rows, voff);
 }
-__device__ __forceinline__ bf16x8 join_tr(const s16x4& lo, const s16x4& hi) {
-  typedef __attribute__((ext_vector_type(8))) short s16x8;
-  const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8, v);
-}
 
 template <int NS>
 __global__ __launch_bounds__(512) void attn_bwd_pipe_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ outp,
@@ -794,7 +779,7 @@ __global__ __launch_bounds__(512) void attn_bwd_pipe_kernel(const bf16_t* __rest
   constexpr int NW = 8;
   constexpr int Np = 32 * NS;
   constexpr int TILE = Np * ROWB;
-  constexpr int SROW = Np * 2 + 16;
+  constexpr int SROW = SX_ROW<NS>;
   const float qsc = (dq8 && qscale) ? *qscale : 1.0f;
   float qmax = 0.f;
   startup_stagger(stagger_wgs, stagger_ticks);
@@ -838,22 +823,7 @@ __global__ __launch_bounds__(512) void attn_bwd_pipe_kernel(const bf16_t* __rest
       dma_rows8(rsD, Dt + (32 * s + 8 * j) * ROWB, 32 * s + 8 * j, ostride, 32 * s + 8 * j, lane);
     }
   };
-  // delta (pre-multiplied by 1/sqrt(dh)) of slice s, by ONE wave: 2 lanes per row
-  auto delta_slice = [&](int s) {
-    const int rl = lane >> 1, half = lane & 1;
-    const int row = 32 * s + rl;
-    const char* orow = Or + (s % 3) * 32 * ROWB;
-    float part = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const u32x4 ov = *(const u32x4*)(orow + tile_off(rl, half * 4 + j));
-      const u32x4 dv = *(const u32x4*)(Dt + tile_off(row, half * 4 + j));
-#pragma unroll
-      for (int w = 0; w < 4; ++w) part += bf_lo(ov[w]) * bf_lo(dv[w]) + bf_hi(ov[w]) * bf_hi(dv[w]);
-    }
-    part += __shfl_xor(part, 1, 64);
-    if (half == 0) del_s[row] = row < N ? part * SCALE : 0.f;
-  };
+  auto delta_slice = [&](int s) { vitssl_attn::delta_slice(del_s, Or, Dt, s, N, lane); };
 
   // ---- prologue: K tile, slices 0 and 1, V fragments, lse
   ATTN_STAMP(0);
@@ -866,8 +836,7 @@ __global__ __launch_bounds__(512) void attn_bwd_pipe_kernel(const bf16_t* __rest
 #pragma unroll
     for (int kt = 0; kt < 2; ++kt) {
       const int key = wave * 32 + kt * 16 + li;
-      const float mi = key < N ? 0.f : -INFINITY;
-      kinit[kt] = f32x4{mi, mi, mi, mi};
+      kinit[kt] = key_mask_init1(key, N);
 #pragma unroll
       for (int kk = 0; kk < 2; ++kk) vf[kt][kk] = glb_frag(vg, stride, key, kk, N, lane);
     }
@@ -891,13 +860,7 @@ __global__ __launch_bounds__(512) void attn_bwd_pipe_kernel(const bf16_t* __rest
 
   const f32x4 c4 = {SCALE_LOG2E, SCALE_LOG2E, SCALE_LOG2E, SCALE_LOG2E}, sc4 = {SCALE, SCALE, SCALE, SCALE};
   f32x4 dv[4][2], dk[4][2];
-#pragma unroll
-  for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-    for (int kt = 0; kt < 2; ++kt) {
-      dv[dt][kt] = f32x4{0.f, 0.f, 0.f, 0.f};
-      dk[dt][kt] = dv[dt][kt];
-    }
+  zero_dkdv(dk, dv);
   // transposed-read addresses (as tr_frag): tile base + row 4 g + q, chunk of column slice dt; + 4096 per 32-row step, + 2048
   // for the second 16 rows, + TILE from the Q tile to the dO tile
   const int tq = (lane >> 2) & 3, tpp = lane & 3;
@@ -913,31 +876,8 @@ __global__ __launch_bounds__(512) void attn_bwd_pipe_kernel(const bf16_t* __rest
   // this wave's K^T fragments (16 head dimensions x all keys) are the same in every step: read once, 4 NS registers
   // (re-reading them in every step instead: 223 against 218 us at B = 256, H = 12, N = 196)
   s16x4 klo[NS], khi[NS];
-  auto load_kt = [&]() {
-    static_for<NS>([&](auto st_c) {
-      constexpr int st = decltype(st_c)::value;
-      ds_read_tr16<4096 * st>(klo[st], kaddr);
-      ds_read_tr16<4096 * st + 2048>(khi[st], kaddr);
-    });
-  };
   auto dq_tile = [&](const char* sx, int qs) {
-    const char* rowp = sx + (16 * qt_w + li) * SROW + 8 * g;
-    u32x2 dlo[NS], dhi[NS];
-#pragma unroll
-    for (int st = 0; st < NS; ++st) {
-      dlo[st] = *(const u32x2*)(rowp + 64 * st);        // keys 32st + 4g .. +3
-      dhi[st] = *(const u32x2*)(rowp + 64 * st + 32);   // keys 32st + 16 + 4g .. +3
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = acc0;
-#pragma unroll
-    for (int st = 0; st < NS; ++st) {
-      const u32x4 w = {dlo[st][0], dlo[st][1], dhi[st][0], dhi[st][1]};
-      if (st & 1) acc1 = MFMA16(join_tr(klo[st], khi[st]), __builtin_bit_cast(bf16x8, w), acc1);
-      else acc0 = MFMA16(join_tr(klo[st], khi[st]), __builtin_bit_cast(bf16x8, w), acc0);
-    }
-    const f32x4 acc = acc0 + acc1;
+    const f32x4 acc = dq_product<NS>(sx, qt_w, g, li, klo, khi);
     const int q = qs * 32 + 16 * qt_w + li;
     // unconditional stores through descriptors (rows >= N are out of range and dropped): every wave issues exactly one
     // store per image and call, so the step's wait can be a counted one that leaves them in flight
@@ -949,7 +889,8 @@ __global__ __launch_bounds__(512) void attn_bwd_pipe_kernel(const bf16_t* __rest
     }
   };
 
-  load_kt();                                       // (the K tile landed with the prologue's wait; the step's lgkmcnt(0) covers the reads)
+  // (the K tile landed with the prologue's wait; the step's lgkmcnt(0) covers the reads)
+  load_kt<NS>(klo, khi, kaddr);
 #pragma unroll 1
   for (int qs = 0; qs < NS; ++qs) {
     char* sx = Sx + (qs & 1) * 32 * SROW;
@@ -1084,11 +1025,7 @@ __global__ __launch_bounds__(512) void attn_bwd_pipe_kernel(const bf16_t* __rest
       }
     }
   }
-  if (dq8 && qamax) {
-    qmax = wave_max(qmax);
-    unsigned* slot = (unsigned*)qamax;
-    if (lane == 0 && __float_as_uint(qmax) > __builtin_nontemporal_load(slot)) atomicMax(slot, __float_as_uint(qmax));
-  }
+  if (dq8 && qamax) publish_amax(qmax, qamax, lane);
 #ifdef VITSSL_ATTN_STAMPS
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
@@ -1113,6 +1050,8 @@ __global__ __launch_bounds__(512) void attn_bwd_pipe_kernel(const bf16_t* __rest
 // store windows of the slower waves from the next item's first writes / requests.
 // (Q8 = the fp8 operand path's extras -- e4m3 image of dqkv, its scale and maximum -- as a template flag: as run-time arguments they
 // cost a dozen scalar registers the bf16 launches never use, in a kernel that is short of them.)
+// (The sweep step, the dQ stores and the dK / dV epilogues are written out here as in the pipelined kernel, not shared through
+// attention_bwd.h: as function calls they re-number this kernel's registers, and its allocation sits at the edge of the budget.)
 template <int NS, bool Q8>
 __global__ __launch_bounds__(512) void attn_bwd_pers_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ outp,
                                                             const bf16_t* __restrict__ dout, const float* __restrict__ lse,
@@ -1127,7 +1066,7 @@ __global__ __launch_bounds__(512) void attn_bwd_pers_kernel(const bf16_t* __rest
   constexpr int NW = 8;
   constexpr int Np = 32 * NS;
   constexpr int TILE = Np * ROWB;
-  constexpr int SROW = Np * 2 + 16;
+  constexpr int SROW = SX_ROW<NS>;
   const float qsc = (Q8 && qscale) ? *qscale : 1.0f;
   float qmax = 0.f;
   char* Qt = smem;
@@ -1204,22 +1143,7 @@ __global__ __launch_bounds__(512) void attn_bwd_pers_kernel(const bf16_t* __rest
     const float l = row < N ? lse[(long long)it * N + row] : 0.f;
     if ((threadIdx.x & 1) == 0 && row < Np) lse_s[buf * Np + row] = row < N ? l * LOG2E : INFINITY;
   };
-  // delta (pre-multiplied by 1/sqrt(dh)) of slice s, by ONE wave: 2 lanes per row
-  auto delta_slice = [&](int s) {
-    const int rl = lane >> 1, half = lane & 1;
-    const int row = 32 * s + rl;
-    const char* orow = Or + (s % 3) * 32 * ROWB;
-    float part = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const u32x4 ov = *(const u32x4*)(orow + tile_off(rl, half * 4 + j));
-      const u32x4 dv = *(const u32x4*)(Dt + tile_off(row, half * 4 + j));
-#pragma unroll
-      for (int w = 0; w < 4; ++w) part += bf_lo(ov[w]) * bf_lo(dv[w]) + bf_hi(ov[w]) * bf_hi(dv[w]);
-    }
-    part += __shfl_xor(part, 1, 64);
-    if (half == 0) del_s[row] = row < N ? part * SCALE : 0.f;
-  };
+  auto delta_slice = [&](int s) { vitssl_attn::delta_slice(del_s, Or, Dt, s, N, lane); };
 
   // ---- the first item's operands
   Item cur = item_of(item);
@@ -1243,10 +1167,7 @@ __global__ __launch_bounds__(512) void attn_bwd_pers_kernel(const bf16_t* __rest
                          (unsigned)(tile_off(4 * g + tq, 2 * dt_w + (tpp >> 1)) - tile_off(4 * g + tq, (tpp >> 1)));
   f32x4 kinit[2];
 #pragma unroll
-  for (int kt = 0; kt < 2; ++kt) {
-    const float mi = wave * 32 + kt * 16 + li < N ? 0.f : -INFINITY;
-    kinit[kt] = f32x4{mi, mi, mi, mi};
-  }
+  for (int kt = 0; kt < 2; ++kt) kinit[kt] = key_mask_init1(wave * 32 + kt * 16 + li, N);
 
   for (int par = 0;; par ^= 1) {
     const int next = item + G;
@@ -1265,11 +1186,7 @@ __global__ __launch_bounds__(512) void attn_bwd_pers_kernel(const bf16_t* __rest
         }
     }
     s16x4 klo[NS], khi[NS];
-    static_for<NS>([&](auto st_c) {
-      constexpr int st = decltype(st_c)::value;
-      ds_read_tr16<4096 * st>(klo[st], kaddr);
-      ds_read_tr16<4096 * st + 2048>(khi[st], kaddr);
-    });
+    load_kt<NS>(klo, khi, kaddr);
     if (delta_wave) delta_slice(0);
     // lgkmcnt(0): the K / V tiles are free behind the barrier.  A raw s_barrier: __syncthreads() would also wait for the previous
     // item's last stores (vmcnt(0)), which step 0's own wait absorbs half a step later.
@@ -1277,26 +1194,8 @@ __global__ __launch_bounds__(512) void attn_bwd_pers_kernel(const bf16_t* __rest
     raw_barrier();
 
     auto dq_tile = [&](const char* sx, int qs) {
-      const char* rowp = sx + (16 * qt_w + li) * SROW + 8 * g;
-      u32x2 dlo[NS], dhi[NS];
-#pragma unroll
-      for (int st = 0; st < NS; ++st) {
-        dlo[st] = *(const u32x2*)(rowp + 64 * st);        // keys 32st + 4g .. +3
-        dhi[st] = *(const u32x2*)(rowp + 64 * st + 32);   // keys 32st + 16 + 4g .. +3
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_sched_barrier(0);
-      f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = acc0;
-#pragma unroll
-      for (int st = 0; st < NS; ++st) {
-        const u32x4 w = {dlo[st][0], dlo[st][1], dhi[st][0], dhi[st][1]};
-        if (st & 1) acc1 = MFMA16(join_tr(klo[st], khi[st]), __builtin_bit_cast(bf16x8, w), acc1);
-        else acc0 = MFMA16(join_tr(klo[st], khi[st]), __builtin_bit_cast(bf16x8, w), acc0);
-      }
-      const f32x4 acc = acc0 + acc1;
+      const f32x4 acc = dq_product<NS>(sx, qt_w, g, li, klo, khi);
       const int q = qs * 32 + 16 * qt_w + li;
-      // unconditional stores through descriptors (rows >= N are out of range and dropped): every wave issues exactly one
-      // store per image and call, so the step's wait can be a counted one that leaves them in flight
       // (descriptors of this item's dq rows, [N, 3 H dh] with row stride `stride`, built here from the item's q offset: scalar work)
       const unsigned qoff = (unsigned)q * (unsigned)(stride * 2) + (unsigned)((dt_w * 16 + 4 * g) * 2);
       if (!Q8 || dqkv) {
@@ -1311,13 +1210,7 @@ __global__ __launch_bounds__(512) void attn_bwd_pers_kernel(const bf16_t* __rest
     };
 
     f32x4 dv[4][2], dk[4][2];
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-      for (int kt = 0; kt < 2; ++kt) {
-        dv[dt][kt] = f32x4{0.f, 0.f, 0.f, 0.f};
-        dk[dt][kt] = dv[dt][kt];
-      }
+    zero_dkdv(dk, dv);
 
 #pragma unroll 1
     for (int qs = 0; qs < NS; ++qs) {
@@ -1481,11 +1374,7 @@ __global__ __launch_bounds__(512) void attn_bwd_pers_kernel(const bf16_t* __rest
     item = next;
     cur = item_of(next);
   }
-  if (Q8 && qamax) {
-    qmax = wave_max(qmax);
-    unsigned* slot = (unsigned*)qamax;
-    if (lane == 0 && __float_as_uint(qmax) > __builtin_nontemporal_load(slot)) atomicMax(slot, __float_as_uint(qmax));
-  }
+  if (Q8 && qamax) publish_amax(qmax, qamax, lane);
 }
 
 // CUs the launches of this file size themselves for: the device's count minus the reserve in force (vitssl_set_reserved_cus).  The
