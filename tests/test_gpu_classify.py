@@ -123,10 +123,10 @@ def test_kernel_nan_row_has_a_defined_prediction():
 
 
 # ---------------------------------------------------------------------------------------------- fused step against autograd
-def tiny(dropout=0.0, seed=21):
+def tiny(dropout=0.0, seed=21, classes=10):
     from vit_core.vit import ViT
     torch.manual_seed(seed)
-    return ViT(num_classes=10, num_blocks=2, input_shape=(3, 32, 32), embed_dim=128, patch_size=8, num_heads=2, mlp_dim=256,
+    return ViT(num_classes=classes, num_blocks=2, input_shape=(3, 32, 32), embed_dim=128, patch_size=8, num_heads=2, mlp_dim=256,
                dropout=dropout).to(DEV).train()
 
 
@@ -230,6 +230,65 @@ def test_eval_step_is_the_no_grad_forward():
     assert counters.tolist() == [int((logits.argmax(1) == y).sum()), 8]
     for k, v in saved.items():                                               # the buffers of the pending backward are untouched
         assert torch.equal(m.runtime().bb.stack._saved["a"]["blocks"][0][k], v), k
+
+
+# ---------------------------------------------------------------------------------------------- the autograd adapter
+@gpu
+@pytest.mark.parametrize("classes", [10, 64])
+def test_autograd_logits_do_not_alias_engine_storage(classes):
+    """The head writes its padded logits into a workspace buffer that the next forward overwrites; with 64 classes the [:, :C]
+    slice of that buffer is already contiguous, so only a copy keeps the first result."""
+    m = tiny(classes=classes)
+    x1, _ = batch()
+    y1 = m(x1)
+    kept = y1.detach().clone()
+    y2 = m(1.0 - x1)
+    torch.cuda.synchronize()
+    assert y1.shape == (8, classes) and y1.requires_grad and not torch.equal(y2, kept)
+    assert torch.equal(y1, kept)
+
+
+@gpu
+@pytest.mark.parametrize("sched", ["full", "head"])
+def test_stale_graph_is_refused_after_a_fused_step(sched):
+    """A fused step replaces the activations the engine keeps for the one pending backward, as a second grad forward does."""
+    from utils.model_builder import freeze_backbone
+    from vitssl_hip import VitsslError
+    x, y = batch()
+    m = tiny()
+    if sched == "head":
+        freeze_backbone(m)
+        m.patch_embedding.cls_token.requires_grad = False
+    assert m.runtime().schedule() == sched
+    out = m(x)
+    m.train_step(x, y, Recorder(m.flat_store()))
+    with pytest.raises(VitsslError, match=r"backward of forward #1, but a later grad-enabled forward \(#2\)"):
+        out.sum().backward()
+
+
+@gpu
+def test_no_grad_forward_between_forward_and_backward_changes_no_gradient():
+    """no_grad forwards (train or eval mode) and eval_step write the head's "head.tmp." buffers (and the backbone's ".tmp" ones), never those a pending
+    backward reads: its gradients are bit-identical to a run without the interloper."""
+    x, y = batch()
+    grads = []
+    for interloper in (False, True):
+        m = tiny(dropout=0.1)
+        torch.manual_seed(3)
+        loss = F.cross_entropy(m(x), y)
+        if interloper:
+            with torch.no_grad():
+                m(1.0 - x)
+            m.eval()
+            with torch.no_grad():
+                m(1.0 - x)
+            m.train()
+            m.eval_step(1.0 - x, y)
+        loss.backward()
+        grads.append({n: p.grad.clone() for n, p in m.named_parameters()})
+    assert len(grads[0]) == len(m.flat_store().names)
+    for n, g in grads[0].items():
+        assert g.any() and torch.equal(g, grads[1][n]), n
 
 
 # ---------------------------------------------------------------------------------------------- frozen schedules

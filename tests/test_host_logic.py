@@ -462,3 +462,75 @@ def test_fuzz_slice_out_of_time_is_not_a_pass(capsys):
     assert fuzz_ops.run(seed=1, kinds="ln", budget_s=0.0, max_cases=3) != 0
     assert "after 0 of 3 cases" in capsys.readouterr().out
     assert fuzz_ops.run(seed=1, kinds="ln", budget_s=0.0) == 0        # a time-bounded sweep without a count
+
+
+class _StepLog:
+    """pacer, reducer and optimizer stubs of R.fused_step writing into one event list"""
+
+    grad_scale = 0.25
+
+    def __init__(self, gflat):
+        self.events, self.gflat = [], gflat
+        self._pacer = self                                   # the dummy model's pre-set pacer
+
+    def begin_step(self):
+        self.events.append("begin_step")
+
+    def end_step(self):
+        self.events.append("end_step")
+
+    def begin(self):
+        self.events.append(("reducer.begin", float(self.gflat.abs().sum())))
+
+    def finish(self):
+        self.events.append("reducer.finish")
+
+    def step_flat(self, gscale=1.0):
+        self.events.append(("step_flat", gscale))
+
+
+def test_fused_step_orders_the_step_and_restores_grad_mode():
+    from types import SimpleNamespace
+    from vit_core import _runtime as R
+    store = SimpleNamespace(gflat=torch.ones(8))
+    log = _StepLog(store.gflat)
+    assert torch.is_grad_enabled()
+    with R.fused_step(log, store, log, log) as apply:
+        log.events.append(("body", float(store.gflat.abs().sum()), torch.is_grad_enabled()))
+        apply()
+    assert log.events == ["begin_step", ("reducer.begin", 0.0), ("body", 0.0, False), "reducer.finish", ("step_flat", 0.25), "end_step"]
+    assert torch.is_grad_enabled()
+
+    store.gflat.fill_(1.0)
+    log = _StepLog(store.gflat)
+    with torch.no_grad():                                    # "as it found it": off stays off
+        with R.fused_step(log, store, log) as apply:         # no reducer: the scale is 1.0
+            apply()
+        assert not torch.is_grad_enabled()
+    assert log.events == ["begin_step", ("step_flat", 1.0), "end_step"] and not store.gflat.any()
+
+    log = _StepLog(store.gflat)
+    with pytest.raises(ZeroDivisionError):
+        with R.fused_step(log, store, log, log) as apply:
+            assert not torch.is_grad_enabled()
+            1 / 0
+            apply()
+    assert log.events == ["begin_step", ("reducer.begin", 0.0)] and torch.is_grad_enabled()
+
+
+def test_prefix_span_is_the_name_pair_it_replaces():
+    from vit_core.ssl.dino.model import DINOViT
+    from vit_core.vit import ViT
+    from vitssl_hip import engine
+    tiny = dict(num_blocks=2, input_shape=(3, 32, 32), embed_dim=128, patch_size=8, num_heads=2, mlp_dim=256)
+    st = engine.FlatStore(ViT(num_classes=10, **tiny), torch.device("cpu"))
+    assert st.prefix_span("classification_head.") == st.span("classification_head.norm.weight", "classification_head.linear.bias")
+    assert st.prefix_span("patch_embedding.") == st.span("patch_embedding.cls_token", "patch_embedding.conv.bias")
+    stack = engine.EncoderStack(st, ["encoder_blocks.0.", "encoder_blocks.1."], 128, 2, 256, 0.0)
+    for i in range(2):
+        b = f"encoder_blocks.{i}."
+        assert stack.block_span(i) == st.prefix_span(b) == st.span(b + "self_attention.w_query.weight", b + "layer_norm2.bias")
+    sd = engine.FlatStore(DINOViT(output_dim=256, **tiny), torch.device("cpu"), only=lambda n: n.startswith("student_"))
+    assert sd.prefix_span("student_head.") == sd.span("student_head.mlp.0.weight", "student_head.fully_connected.parametrizations.weight.original1")
+    assert sd.prefix_span("student_backbone.patch_embedding.") == sd.span("student_backbone.patch_embedding.cls_token",
+                                                                          "student_backbone.patch_embedding.proj.bias")

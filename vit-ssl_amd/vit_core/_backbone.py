@@ -68,6 +68,12 @@ class BackboneRuntime:
             self.rec[slot] = dict(B=B, T=T, tokens=tokens, patches=patches, pos_graph=pos_graph)
         return feats, probs
 
+    def forget(self, slot: str):
+        """Drop what a saving forward kept for `slot` (a step that keeps no backbone activations must not leave an older
+        forward's behind)."""
+        self.rec.pop(slot, None)
+        self.stack._saved.pop(slot, None)
+
     def backward(self, dfeats, slot: str, reducer=None, input_grad_only=False, proj_wgrad=True):
         """dfeats: fp32 [B, D] gradient wrt the CLS features; accumulates parameter grads.
         `input_grad_only`: the blocks are frozen (EncoderStack.backward); `proj_wgrad=False`: so is the patch projection,

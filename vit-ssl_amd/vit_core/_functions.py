@@ -9,15 +9,11 @@ import torch
 from torch.autograd import Function
 
 from . import _runtime as R
-from ._runtime import BF16, F32, L, ops
+from ._runtime import BF16, F32, L, _round_up, ops
 
 
 def _empty(shape, dtype, like):
     return torch.empty(shape, dtype=dtype, device=like.device)
-
-
-def _round_up(n, a):
-    return (n + a - 1) // a * a
 
 
 def to_bf16(x: torch.Tensor) -> torch.Tensor:

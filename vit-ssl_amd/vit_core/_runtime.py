@@ -1,5 +1,6 @@
 """Shared plumbing of the drop-in vit_core modules: lazy flat-store materialisation on
 the module's device and loud failure when there is no GPU / no HIP library."""
+import contextlib
 import os
 import sys
 
@@ -11,7 +12,7 @@ if _PKG not in sys.path:
 
 from vitssl_hip import _lib as L  # noqa: E402
 from vitssl_hip import ops  # noqa: E402
-from vitssl_hip.engine import EncoderStack, FlatStore, GradReducer, Workspace  # noqa: E402,F401
+from vitssl_hip.engine import EncoderStack, FlatStore, GradReducer, Workspace, _round_up  # noqa: E402,F401
 
 BF16 = torch.bfloat16
 F32 = torch.float32
@@ -40,6 +41,27 @@ def check_saved_generation(who: str, graph_gen: int, live_gen: int):
             f"{who}: backward of forward #{graph_gen}, but a later grad-enabled forward (#{live_gen}) has replaced its "
             "saved activations. Call backward() before the next training forward (or run the extra forward under "
             "torch.no_grad()); gradient accumulation over micro-batches works as forward/backward pairs.")
+
+
+def backward_grads(who: str, graph_gen: int, live_gen: int, store, run):
+    """The common part of the models' autograd.Function.backward: refuse a stale graph, zero the flat gradient buffer, `run()`
+    the engine backward into it, and return one clone per parameter of `store` (None where it is frozen)."""
+    check_saved_generation(who, graph_gen, live_gen)
+    store.gflat.zero_()
+    run()
+    return tuple(store.gview(n, p.shape).clone() if p.requires_grad else None for n, p in zip(store.names, store.params))
+
+
+def model_runtime(model, who: str, cls, anchor: torch.Tensor, device=None):
+    """`model._rt`, (re)built as `cls(model, device)` when there is none or the parameters have moved; the device defaults
+    to `anchor`'s."""
+    device = device or anchor.device
+    if device.type != "cuda":
+        raise L.VitsslError(f"{who}: parameters are on the CPU; move the model to 'cuda' (no CPU fallback)")
+    if model._rt is None or not model._rt.valid_for(device):
+        L.lib()
+        object.__setattr__(model, "_rt", cls(model, device))
+    return model._rt
 
 
 def as_f32(x: torch.Tensor) -> torch.Tensor:
@@ -88,3 +110,25 @@ class StepPacer:
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream())
         self.events.append(ev)
+
+
+@contextlib.contextmanager
+def fused_step(model, store, optimizer, reducer=None):
+    """The frame of a fused train step, shared by the three models: pace the host (`model._pacer`), switch autograd off, zero
+    `store.gflat` and open the reducer; the body runs forward, loss and backward and then calls the yielded `apply()`
+    (finish the all-reduce, flat optimizer step).  A body that raises records no step."""
+    if getattr(model, "_pacer", None) is None:
+        object.__setattr__(model, "_pacer", StepPacer())
+    model._pacer.begin_step()
+
+    def apply():
+        if reducer is not None:
+            reducer.finish()
+        optimizer.step_flat(reducer.grad_scale if reducer is not None else 1.0)
+
+    with torch.no_grad():
+        store.gflat.zero_()
+        if reducer is not None:
+            reducer.begin()
+        yield apply
+    model._pacer.end_step()

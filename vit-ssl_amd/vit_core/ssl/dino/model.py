@@ -117,12 +117,10 @@ class _DINORuntime:
         head.finish_backward()
         st = self.stores["student"]
         if reducer is not None:
-            names = [n for n in st.names if n.startswith("student_head.")]
-            reducer.ready(*st.span(names[0], names[-1]))
+            reducer.ready(*st.prefix_span("student_head."))
         bb.backward(dfg, "g", reducer)
         if reducer is not None:
-            names = [n for n in st.names if n.startswith("student_backbone.patch_embedding.")]
-            reducer.ready(*st.span(names[0], names[-1]))
+            reducer.ready(*st.prefix_span("student_backbone.patch_embedding."))
 
 
 class _DINOFn(Function):
@@ -136,15 +134,14 @@ class _DINOFn(Function):
     @staticmethod
     def backward(ctx, _dt, dstudent):
         rt = ctx.rt
-        R.check_saved_generation("DINOViT", ctx.gen, rt.save_gen)
-        st = rt.stores["student"]
-        st.gflat.zero_()
-        d = R.as_f32(dstudent)
-        db = torch.empty(d.shape, dtype=BF16, device=d.device)
-        ops.cast_bf16(d, db)
-        rt.backward(db)
-        grads = [st.gview(n, p.shape).clone() if p.requires_grad else None for n, p in zip(st.names, st.params)]
-        return (None, None, None, None, None, *grads)
+
+        def run():
+            d = R.as_f32(dstudent)
+            db = torch.empty(d.shape, dtype=BF16, device=d.device)
+            ops.cast_bf16(d, db)
+            rt.backward(db)
+
+        return (None, None, None, None, None, *R.backward_grads("DINOViT", ctx.gen, rt.save_gen, rt.stores["student"], run))
 
 
 class DINOViT(nn.Module):
@@ -179,13 +176,7 @@ class DINOViT(nn.Module):
 
     # ------------------------------------------------------------------ runtime
     def runtime(self, device=None) -> _DINORuntime:
-        device = device or self.center.device
-        if device.type != "cuda":
-            raise L.VitsslError("DINOViT: parameters are on the CPU; move the model to 'cuda' (no CPU fallback)")
-        if self._rt is None or not self._rt.valid_for(device):
-            L.lib()
-            object.__setattr__(self, "_rt", _DINORuntime(self, device))
-        return self._rt
+        return R.model_runtime(self, "DINOViT", _DINORuntime, self.center, device)
 
     def flat_store(self):
         return self.runtime().stores["student"]
@@ -236,14 +227,7 @@ class DINOViT(nn.Module):
         (reference: utils/trainers/dino_trainer.py:82-105)."""
         R.require_gpu(views[0], "DINOViT.train_step")
         rt = self.runtime(views[0].device)
-        st = rt.stores["student"]
-        if getattr(self, "_pacer", None) is None:
-            object.__setattr__(self, "_pacer", R.StepPacer())
-        self._pacer.begin_step()
-        with torch.no_grad():
-            st.gflat.zero_()
-            if reducer is not None:
-                reducer.begin()
+        with R.fused_step(self, rt.stores["student"], optimizer, reducer) as apply:
             teacher, student = rt.forward(list(views), num_global_views, True, save=True)
             G, V, B, K = num_global_views, len(views), views[0].shape[0], rt.K
             dev = student.device
@@ -254,13 +238,7 @@ class DINOViT(nn.Module):
             ops.dino_loss(teacher, student, self.center.view(-1), t_ws, loss, dstudent, G, V, B, K,
                           float(criterion.teacher_temp), float(criterion.student_temp), 1.0)
             rt.backward(dstudent, reducer)
-            gscale = 1.0
-            if reducer is not None:
-                reducer.finish()
-                gscale = reducer.grad_scale
-            optimizer.step_flat(gscale)
+            apply()
             self.momentum_update_teacher(teacher_momentum)
             self.last_teacher, self.last_student = teacher, student
-            out = loss[0].clone()
-            self._pacer.end_step()
-            return out
+            return loss[0].clone()

@@ -179,16 +179,15 @@ class _SimMIMFn(Function):
     @staticmethod
     def backward(ctx, dpred, _dt, _dm):
         rt = ctx.rt
-        R.check_saved_generation("SimMIMViT", ctx.gen, rt.save_gen)
-        st = rt.store
-        st.gflat.zero_()
-        dp = R.as_f32(dpred)
-        dpb = torch.empty(dp.shape, dtype=BF16, device=dp.device)
-        if dp.numel() > 0:
-            ops.cast_bf16(dp, dpb)
-        rt.backward(dpb)
-        grads = [st.gview(n, p.shape).clone() if p.requires_grad else None for n, p in zip(st.names, st.params)]
-        return (None, None, None, None, *grads)
+
+        def run():
+            dp = R.as_f32(dpred)
+            dpb = torch.empty(dp.shape, dtype=BF16, device=dp.device)
+            if dp.numel() > 0:
+                ops.cast_bf16(dp, dpb)
+            rt.backward(dpb)
+
+        return (None, None, None, None, *R.backward_grads("SimMIMViT", ctx.gen, rt.save_gen, rt.store, run))
 
 
 class SimMIMViT(nn.Module):
@@ -224,13 +223,7 @@ class SimMIMViT(nn.Module):
 
     # ------------------------------------------------------------------ runtime
     def runtime(self, device=None) -> _SimMIMRuntime:
-        device = device or self.mask_token.device
-        if device.type != "cuda":
-            raise L.VitsslError("SimMIMViT: parameters are on the CPU; move the model to 'cuda' (no CPU fallback)")
-        if self._rt is None or not self._rt.valid_for(device):
-            L.lib()
-            object.__setattr__(self, "_rt", _SimMIMRuntime(self, device))
-        return self._rt
+        return R.model_runtime(self, "SimMIMViT", _SimMIMRuntime, self.mask_token, device)
 
     def flat_store(self):
         return self.runtime().store
@@ -269,14 +262,7 @@ class SimMIMViT(nn.Module):
         of the reference with criterion nn.L1Loss(mean)."""
         R.require_gpu(x, "SimMIMViT.train_step")
         rt = self.runtime(x.device)
-        st = rt.store
-        if getattr(self, "_pacer", None) is None:
-            object.__setattr__(self, "_pacer", R.StepPacer())
-        self._pacer.begin_step()
-        with torch.no_grad():
-            st.gflat.zero_()
-            if reducer is not None:
-                reducer.begin()
+        with R.fused_step(self, rt.store, optimizer, reducer) as apply:
             pred, targets, _ = rt.forward(x, True, save=True, mask_cpu=mask_cpu, prepared=prepared)
             n = pred.numel()
             loss_sum = rt.ws.get("loss_sum", (1,), F32, x.device)
@@ -291,12 +277,6 @@ class SimMIMViT(nn.Module):
                 dpb = rt.ws.get("dpred", tuple(pred.shape), BF16, x.device)
                 ops.l1_loss(pred, targets, loss_sum, dpb, gscale=1.0 / n)
                 rt.backward(dpb, reducer)
-            gscale = 1.0
-            if reducer is not None:
-                reducer.finish()
-                gscale = reducer.grad_scale
-            optimizer.step_flat(gscale)
+            apply()
             self.last_pred, self.last_targets = pred, targets
-            loss = loss_sum[0] / n
-            self._pacer.end_step()
-            return loss
+            return loss_sum[0] / n

@@ -5,21 +5,20 @@ Two ways to train, as for SimMIMViT:
   * reference style: ``loss = criterion(model(x), y); loss.backward()`` (one torch.autograd.Function around the engine);
   * fused: ``loss = model.train_step(x, y, optimizer, reducer)`` -- cross-entropy (csrc/classify.hip), backward into the flat
     gradient buffer, overlapped all-reduce and flat AdamW with no autograd graph; ``model.eval_step(x, y)`` is its no-grad
-    half.  The backward does only what the parameters' `requires_grad` asks for (`_ViTRuntime.schedule`)."""
+    half.  The backward does only what the parameters' `requires_grad` asks for (`_ViTRuntime.schedule`).
+Both run the one classification head of `_ViTRuntime` (`forward` / `loss` / `backward`: workspace buffers, GEMM operands cached
+on the store's `weights_key()`); `_ViTFn` only slices and copies the logits out and pads the incoming gradient.  The runtime keeps
+the activations of ONE saving forward, whichever path made it: a backward through an older graph raises VitsslError."""
 import torch
 from torch import nn
 from torch.autograd import Function
 
 from . import _runtime as R
-from ._runtime import BF16, F32, L, ops
+from ._runtime import BF16, F32, L, _round_up, ops
 from ._backbone import BackboneRuntime
 from .encoder_block import EncoderBlock
 from .mlp_head import MLPHead
 from .patch_embedding import ConvolutionalPatchEmbedding
-
-
-def _round_up(n, a):
-    return (n + a - 1) // a * a
 
 
 class _ViTRuntime:
@@ -35,11 +34,9 @@ class _ViTRuntime:
                          cls="patch_embedding.cls_token", pos="patch_embedding.positional_embedding"),
             len(model.encoder_blocks), C, P, (Hh // P, Ww // P), self.D, model.num_heads, model.mlp_dim, model.dropout_p)
         self.ncls = model.num_classes
-        self.rec = None
-        self.save_gen = 0
-        # fused step
+        self.rec = None                   # what the last saving forward keeps of the head for its backward
+        self.save_gen = 0                 # id of that forward
         self.ws = R.Workspace()
-        self.frec = None                  # what the fused forward keeps for its backward
         self._head = None                 # cached GEMM operands of the classifier (head_operands)
         self._head_key = None
         self.counters = torch.zeros(2, dtype=torch.int64, device=device)      # (correct, valid) when the caller brings none
@@ -48,70 +45,9 @@ class _ViTRuntime:
     def valid_for(self, device):
         return device == self.device and self.store.is_attached()
 
-    def _head_weights(self):
-        """bf16 copies of the (tiny) classifier weight, zero-padded to the GEMM granules."""
-        st, D, C = self.store, self.D, self.ncls
-        Nk = _round_up(C, 64)
-        w = torch.zeros(Nk, D, dtype=F32, device=self.device)
-        w[:C] = st.view("classification_head.linear.weight", (C, D))
-        wb = torch.empty(Nk, D, dtype=BF16, device=self.device)
-        wt = torch.empty(D, Nk, dtype=BF16, device=self.device)
-        ops.cast_transpose_bf16(w, wb, wt)
-        return wb, wt, Nk
-
-    def forward(self, x, training, save, return_attn=False):
-        st = self.store
-        st.refresh_weights()
-        seed = R.next_seed() if (training and self.bb.stack.p > 0) else 0
-        feats, probs = self.bb.forward(x, training, seed, save=save, slot="a", return_attn=return_attn)
-        B = feats.shape[0]
-        dev = feats.device
-        h = torch.empty(B, self.D, dtype=BF16, device=dev)
-        mean = torch.empty(B, dtype=F32, device=dev)
-        rstd = torch.empty(B, dtype=F32, device=dev)
-        ops.layernorm_fwd(feats, st.view("classification_head.norm.weight"), st.view("classification_head.norm.bias"), h, mean, rstd)
-        wb, wt, Nk = self._head_weights()
-        bias = torch.zeros(Nk, dtype=F32, device=dev)
-        bias[:self.ncls] = st.view("classification_head.linear.bias")
-        logits = torch.empty(B, Nk, dtype=F32, device=dev)
-        ops.gemm_nt(h, wb, logits, L.EPI_F32, bias=bias)
-        if save:
-            self.save_gen += 1
-            self.rec = dict(feats=feats, h=h, mean=mean, rstd=rstd, wt=wt, Nk=Nk, B=B)
-        return logits[:, :self.ncls].contiguous(), probs
-
-    def backward(self, dlogits, reducer=None):
-        st, rec = self.store, self.rec
-        B, Nk, C, D = rec["B"], rec["Nk"], self.ncls, self.D
-        dev = dlogits.device
-        gv = st.gview
-        dl = torch.zeros(B, Nk, dtype=F32, device=dev)
-        dl[:, :C] = R.as_f32(dlogits)
-        dlb = torch.empty(B, Nk, dtype=BF16, device=dev)
-        ops.cast_bf16(dl, dlb)
-        gv("classification_head.linear.bias").add_(dl[:, :C].sum(0))
-        dw = torch.zeros(Nk, D, dtype=F32, device=dev)
-        ops.gemm_tn(dlb, rec["h"], dw)
-        gv("classification_head.linear.weight", (C, D)).add_(dw[:C])
-        dh = torch.empty(B, D, dtype=BF16, device=dev)
-        ops.gemm_nt(dlb, rec["wt"], dh, L.EPI_BF16)
-        dfeats = torch.empty(B, D, dtype=F32, device=dev)
-        ops.layernorm_bwd(dh, rec["feats"], rec["mean"], rec["rstd"], st.view("classification_head.norm.weight"), None, dfeats,
-                          None, gv("classification_head.norm.weight"), gv("classification_head.norm.bias"))
-        if reducer is not None:
-            reducer.ready(*st.span("classification_head.norm.weight", "classification_head.linear.bias"))
-        self.bb.backward(dfeats, "a", reducer)
-        if reducer is not None:
-            reducer.ready(*st.span("patch_embedding.cls_token", "patch_embedding.conv.bias"))
-
-
-    # ------------------------------------------------------------------ fused step
-    HEAD_SPAN = ("classification_head.norm.weight", "classification_head.linear.bias")
-    EMBED_SPAN = ("patch_embedding.cls_token", "patch_embedding.conv.bias")
-
     def schedule(self) -> str:
         """Which backward the parameters' requires_grad asks for (read at every call; about 150 flags):
-        "full": an encoder-block parameter trains -- the schedule of `backward`;
+        "full": an encoder-block parameter trains -- every gradient (what the autograd path always runs);
         "input_grad": the blocks are frozen and something below them trains (utils.model_builder.freeze_backbone leaves the
             CLS token trainable) -- the input-gradient chain without the blocks' weight-gradient GEMMs (bf16 operands; with
             fp8 operands this case runs the full schedule);
@@ -135,8 +71,8 @@ class _ViTRuntime:
         sched, st = self.schedule(), self.store
         if sched == "full":
             return None
-        head = st.span(*self.HEAD_SPAN)
-        return [head] if sched == "head" else [st.span(*self.EMBED_SPAN), head]
+        head = st.prefix_span("classification_head.")
+        return [head] if sched == "head" else [st.prefix_span("patch_embedding."), head]
 
     def head_operands(self):
         """(bf16 classifier weight [Nk, D] zero-padded to the GEMM granule, its transpose [D, Nk], padded fp32 bias [Nk], Nk),
@@ -156,13 +92,16 @@ class _ViTRuntime:
             self._head_key = key
         return hd["wb"], hd["wt"], hd["bias"], hd["Nk"]
 
-    def fused_forward(self, x, training, save_backbone, tag):
-        """-> padded logits f32 [B, Nk] and the head's saved tensors.  `tag` separates the buffers of a forward that saves
-        nothing (eval_step) from those a pending backward still needs."""
+    def forward(self, x, training, save, save_backbone=None, return_attn=False):
+        """-> (padded logits f32 [B, Nk] in a workspace buffer, attention probabilities or None).  A saving forward keeps the
+        head's tensors in `rec` (and the backbone's unless `save_backbone` is False: the "head" schedule) and takes a new
+        `save_gen`; one that saves nothing (no_grad, eval_step) leaves the buffers of a pending backward alone."""
         st, g = self.store, self.ws.get
+        tag = "head." if save else "head.tmp."
         st.refresh_weights()
         seed = R.next_seed() if (training and self.bb.stack.p > 0) else 0
-        feats, _ = self.bb.forward(x, training, seed, save=save_backbone, slot="a")
+        feats, probs = self.bb.forward(x, training, seed, save=save if save_backbone is None else save_backbone, slot="a",
+                                       return_attn=return_attn)
         B, dev = feats.shape[0], feats.device
         h = g(tag + "h", (B, self.D), BF16, dev)
         mean, rstd = g(tag + "mean", (B,), F32, dev), g(tag + "rstd", (B,), F32, dev)
@@ -170,9 +109,12 @@ class _ViTRuntime:
         wb, wt, bias, Nk = self.head_operands()
         logits = g(tag + "logits", (B, Nk), F32, dev)
         ops.gemm_nt(h, wb, logits, L.EPI_F32, bias=bias)
-        return logits, dict(feats=feats, h=h, mean=mean, rstd=rstd, wt=wt, Nk=Nk, B=B)
+        if save:
+            self.save_gen += 1
+            self.rec = dict(feats=feats, h=h, mean=mean, rstd=rstd, wt=wt, Nk=Nk, B=B)
+        return logits, probs
 
-    def fused_loss(self, logits, labels, tag, label_smoothing, ignore_index, counters, dlogits=None, dbias=None):
+    def loss(self, logits, labels, tag, label_smoothing, ignore_index, counters, dlogits=None, dbias=None):
         """csrc/classify.hip on the padded logits -> (loss as a device scalar, pred i64 [B])."""
         B, dev = logits.shape[0], logits.device
         if labels.dtype != torch.int64 or not labels.is_contiguous():
@@ -183,9 +125,10 @@ class _ViTRuntime:
                           dlogits=dlogits, dbias=dbias, label_smoothing=label_smoothing, ignore_index=ignore_index)
         return loss_out[0] / loss_out[1], pred         # 0 / 0 = nan when every row is ignored, as torch gives
 
-    def fused_backward(self, rec, dlb, sched, reducer=None):
-        """dlb: bf16 [B, Nk] from the loss kernel (which has already accumulated the classifier's bias gradient)."""
-        st, g = self.store, self.ws.get
+    def backward(self, dlb, sched, reducer=None):
+        """dlb: bf16 [B, Nk], the gradient of the padded logits; the classifier's bias gradient is the caller's (the loss
+        kernel accumulates it)."""
+        st, g, rec = self.store, self.ws.get, self.rec
         B, Nk, C, D = rec["B"], rec["Nk"], self.ncls, self.D
         dev = dlb.device
         gv = st.gview
@@ -199,34 +142,40 @@ class _ViTRuntime:
         ops.layernorm_bwd(dh, rec["feats"], rec["mean"], rec["rstd"], st.view("classification_head.norm.weight"), None, dfeats,
                           None, gv("classification_head.norm.weight"), gv("classification_head.norm.bias"))
         if reducer is not None:
-            reducer.ready(*st.span(*self.HEAD_SPAN))
+            reducer.ready(*st.prefix_span("classification_head."))
         if sched == "head":
             return
         proj = sched == "full" or self.model.patch_embedding.conv.weight.requires_grad
         self.bb.backward(dfeats, "a", reducer, input_grad_only=sched == "input_grad", proj_wgrad=proj)
         if reducer is not None:
-            reducer.ready(*st.span(*self.EMBED_SPAN))
+            reducer.ready(*st.prefix_span("patch_embedding."))
 
 
 class _ViTFn(Function):
+    """The autograd path: a thin adapter over the runtime's one head forward / backward."""
+
     @staticmethod
     def forward(ctx, rt, x, training, return_attn, need, *params):
         logits, probs = rt.forward(x, training, save=need, return_attn=return_attn)
         ctx.rt, ctx.gen = rt, rt.save_gen
         if return_attn:
             ctx.mark_non_differentiable(probs)
-            return logits, probs
-        return logits, None
+        return logits[:, :rt.ncls].clone(), probs        # a copy: the workspace buffer belongs to the next forward
 
     @staticmethod
     def backward(ctx, dlogits, _dp):
         rt = ctx.rt
-        R.check_saved_generation("ViT", ctx.gen, rt.save_gen)
-        st = rt.store
-        st.gflat.zero_()
-        rt.backward(dlogits)
-        grads = [st.gview(n, p.shape).clone() if p.requires_grad else None for n, p in zip(st.names, st.params)]
-        return (None, None, None, None, None, *grads)
+        st, C = rt.store, rt.ncls
+
+        def run():
+            dl = torch.zeros(dlogits.shape[0], rt.rec["Nk"], dtype=F32, device=dlogits.device)
+            dl[:, :C] = R.as_f32(dlogits)
+            dlb = torch.empty(dl.shape, dtype=BF16, device=dl.device)
+            ops.cast_bf16(dl, dlb)
+            st.gview("classification_head.linear.bias").add_(dl[:, :C].sum(0))
+            rt.backward(dlb, "full")
+
+        return (None, None, None, None, None, *R.backward_grads("ViT", ctx.gen, rt.save_gen, st, run))
 
 
 class ViT(nn.Module):
@@ -253,13 +202,7 @@ class ViT(nn.Module):
         self._rt = None
 
     def runtime(self, device=None) -> _ViTRuntime:
-        device = device or self.patch_embedding.cls_token.device
-        if device.type != "cuda":
-            raise L.VitsslError("ViT: parameters are on the CPU; move the model to 'cuda' (no CPU fallback)")
-        if self._rt is None or not self._rt.valid_for(device):
-            L.lib()
-            object.__setattr__(self, "_rt", _ViTRuntime(self, device))
-        return self._rt
+        return R.model_runtime(self, "ViT", _ViTRuntime, self.patch_embedding.cls_token, device)
 
     def flat_store(self):
         return self.runtime().store
@@ -297,29 +240,17 @@ class ViT(nn.Module):
         R.require_gpu(x, "ViT.train_step")
         rt = self.runtime(x.device)
         st = rt.store
-        if getattr(self, "_pacer", None) is None:
-            object.__setattr__(self, "_pacer", R.StepPacer())
-        self._pacer.begin_step()
-        with torch.no_grad():
+        with R.fused_step(self, st, optimizer, reducer) as apply:
             sched = rt.schedule()
-            st.gflat.zero_()
-            if reducer is not None:
-                reducer.begin()
             if sched == "head":                        # nothing below the head trains: no activations are kept
-                rt.bb.rec.pop("a", None)
-                rt.bb.stack._saved.pop("a", None)
-            logits, rec = rt.fused_forward(x, True, sched != "head", "head.")
+                rt.bb.forget("a")
+            logits, _ = rt.forward(x, True, save=True, save_backbone=sched != "head")
             dlb = rt.ws.get("head.dlogits", tuple(logits.shape), BF16, x.device)
-            loss, pred = rt.fused_loss(logits, labels, "head.", label_smoothing, ignore_index, counters, dlogits=dlb,
-                                       dbias=st.gview("classification_head.linear.bias"))
-            rt.fused_backward(rec, dlb, sched, reducer)
-            gscale = 1.0
-            if reducer is not None:
-                reducer.finish()
-                gscale = reducer.grad_scale
-            optimizer.step_flat(gscale)
+            loss, pred = rt.loss(logits, labels, "head.", label_smoothing, ignore_index, counters, dlogits=dlb,
+                                 dbias=st.gview("classification_head.linear.bias"))
+            rt.backward(dlb, sched, reducer)
+            apply()
             self.last_logits, self.last_pred = logits[:, :self.num_classes], pred
-            self._pacer.end_step()
             return loss
 
     @torch.no_grad()
@@ -329,7 +260,7 @@ class ViT(nn.Module):
         nothing and leaves the buffers of a pending backward alone; same `last_logits`, `last_pred` and counters."""
         R.require_gpu(x, "ViT.eval_step")
         rt = self.runtime(x.device)
-        logits, _ = rt.fused_forward(x, False, False, "head.tmp.")
-        loss, pred = rt.fused_loss(logits, labels, "head.tmp.", label_smoothing, ignore_index, counters)
+        logits, _ = rt.forward(x, False, save=False)
+        loss, pred = rt.loss(logits, labels, "head.tmp.", label_smoothing, ignore_index, counters)
         self.last_logits, self.last_pred = logits[:, :self.num_classes], pred
         return loss

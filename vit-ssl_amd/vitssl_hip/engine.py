@@ -144,6 +144,11 @@ class FlatStore:
         o, n = self.offsets[last]
         return lo, o + n
 
+    def prefix_span(self, prefix: str) -> Tuple[int, int]:
+        """span() of the parameters whose names start with `prefix` (one submodule: adjacent in the store)."""
+        names = [n for n in self.names if n.startswith(prefix)]
+        return self.span(names[0], names[-1])
+
     def span_view(self, first: str, last: str, shape, grad=False) -> torch.Tensor:
         lo, hi = self.span(first, last)
         buf = self.gflat if grad else self.flat
@@ -460,8 +465,7 @@ class EncoderStack:
         return self.bp[i] + leaf
 
     def block_span(self, i) -> Tuple[int, int]:
-        names = [n for n in self.store.names if n.startswith(self.bp[i])]
-        return self.store.span(names[0], names[-1])
+        return self.store.prefix_span(self.bp[i])
 
     def _drop(self, i, which, seed, training):
         if not training or self.p <= 0.0:
