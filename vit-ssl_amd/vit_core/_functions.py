@@ -225,12 +225,13 @@ class _SDPAFn(Function):
     @staticmethod
     def forward(ctx, q, k, v, return_attn):
         Bn, H, N, dh = q.shape
+        ops.attn_family(dh)                                      # an unsupported head dim is refused before any launch
         qkv = torch.stack([q, k, v], dim=2)                      # [B,H,3,N,dh]
         qkv = to_bf16(R.as_f32(qkv.permute(0, 3, 2, 1, 4)).reshape(Bn * N, 3 * H * dh))
         out = _empty((Bn * N, H * dh), BF16, q)
         lse = _empty((Bn, H, N), F32, q)
         probs = _empty((Bn, H, N, N), F32, q) if return_attn else None
-        ops.attn_fwd(qkv, out, lse, Bn, N, H, dh, probs=probs)
+        ops.attn_fwd_any(qkv, out, lse, Bn, N, H, dh, probs=probs)
         ctx.save_for_backward(qkv, out, lse)
         ctx.meta = (Bn, H, N, dh)
         o = out.float().view(Bn, N, H, dh).transpose(1, 2)
@@ -246,7 +247,7 @@ class _SDPAFn(Function):
         dout = to_bf16(R.as_f32(do.transpose(1, 2)).reshape(Bn * N, H * dh))
         dqkv = _empty(qkv.shape, BF16, qkv)
         delta = _empty((Bn, H, N), F32, qkv)
-        ops.attn_bwd(qkv, out, dout, lse, dqkv, delta, Bn, N, H, dh)
+        ops.attn_bwd_any(qkv, out, dout, lse, dqkv, delta, Bn, N, H, dh)
         d = dqkv.float().view(Bn, N, 3, H, dh).permute(2, 0, 3, 1, 4)
         return d[0], d[1], d[2], None
 
@@ -274,6 +275,7 @@ class _MHAFn(Function):
     def forward(ctx, query, key, value, wq, wk, wv, wo, H, return_attn):
         Bn, N, D = query.shape
         dh = D // H
+        ops.attn_family(dh)                                      # an unsupported head dim is refused before any launch
         same = (key is query or key.data_ptr() == query.data_ptr()) and (value is query or value.data_ptr() == query.data_ptr())
         rows = Bn * N
         if same:
@@ -298,7 +300,7 @@ class _MHAFn(Function):
         att = _empty((rows, D), BF16, query)
         lse = _empty((Bn, H, N), F32, query)
         probs = _empty((Bn, H, N, N), F32, query) if return_attn else None
-        ops.attn_fwd(qkv, att, lse, Bn, N, H, dh, probs=probs)
+        ops.attn_fwd_any(qkv, att, lse, Bn, N, H, dh, probs=probs)
         wob, wot = weight_bf16(wo)
         y = _empty((rows, D), F32, query)
         ops.gemm_nt(att, wob, y, L.EPI_F32)
@@ -326,7 +328,7 @@ class _MHAFn(Function):
         ops.gemm_tn(dyb, att, dwo)
         dqkv = _empty((rows, 3 * D), BF16, dyb)
         delta = _empty((Bn, H, N), F32, dyb)
-        ops.attn_bwd(qkv, att, datt, lse, dqkv, delta, Bn, N, H, dh)
+        ops.attn_bwd_any(qkv, att, datt, lse, dqkv, delta, Bn, N, H, dh)
         if same:
             dx = _empty((rows, D), F32, dyb)
             ops.gemm_nt(dqkv, wts[0], dx, L.EPI_F32)

@@ -11,6 +11,7 @@ HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "vitss
 TRANSFORMS_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "vitssl_transforms.h"))
 METRICS_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "vitssl_metrics.h"))
 CLASSIFY_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "vitssl_classify.h"))
+ATTENTION_HD_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "vitssl_attention_hd.h"))
 
 
 class VitsslError(RuntimeError):
@@ -127,6 +128,13 @@ PROTOTYPES_CLASSIFY = {
     "vitssl_classify_loss": [_vp, _vp, _i, _i, _i, C.c_double, _i64, _f, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
 }
 
+# include/vitssl_attention_hd.h (attention for head dims 8 .. 128 other than the dh = 64 family of vitssl_hip.h): both entry
+# points launch; argument order as vitssl_attn_fwd / vitssl_attn_bwd.
+PROTOTYPES_ATTENTION_HD = {
+    "vitssl_attn_hd_fwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    "vitssl_attn_hd_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
+}
+
 _lib = None
 
 
@@ -155,6 +163,13 @@ def classify_header_symbols():
     """Entry points and sizing functions declared in include/vitssl_classify.h."""
     with open(CLASSIFY_HEADER_PATH) as f:
         txt = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)        # the comments name functions in running text
+    return sorted(set(re.findall(r"\b(vitssl_[a-z0-9_]+)\s*\(", txt)))
+
+
+def attention_hd_header_symbols():
+    """Entry points declared in include/vitssl_attention_hd.h."""
+    with open(ATTENTION_HD_HEADER_PATH) as f:
+        txt = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)        # the comments name functions of vitssl_hip.h
     return sorted(set(re.findall(r"\b(vitssl_[a-z0-9_]+)\s*\(", txt)))
 
 
@@ -206,7 +221,7 @@ def lib():
     l.vitssl_classify_loss_workspace_floats.restype = C.c_int64
     l.vitssl_classify_loss_workspace_floats.argtypes = [C.c_int, C.c_int]
     for name, args in (list(PROTOTYPES.items()) + list(PROTOTYPES_TRANSFORMS.items()) + list(PROTOTYPES_METRICS.items())
-                       + list(PROTOTYPES_CLASSIFY.items())):
+                       + list(PROTOTYPES_CLASSIFY.items()) + list(PROTOTYPES_ATTENTION_HD.items())):
         fn = getattr(l, name)  # AttributeError if the symbol is missing
         fn.restype = C.c_int
         fn.argtypes = args

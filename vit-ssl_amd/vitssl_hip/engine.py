@@ -473,8 +473,13 @@ class EncoderStack:
         return ops.make_dropout(self.p, seed, self.site_base + 3 * i + which)
 
     def check_tokens(self, T: int):
-        """Refuse a sequence length the attention kernels of this operand mode do not cover.  Models call it at the top of
+        """Refuse a head dim or a sequence length the attention kernels of this operand mode do not cover.  Models call it at the top of
         their forward, before the first kernel of the step; forward() below repeats it for lone blocks."""
+        if self.fp8 and self.dh != 64:
+            raise L.VitsslError(f"fp8 linear operands support head dim 64 only, got embed_dim / num_heads = {self.D} / {self.H} = "
+                                f"{self.dh}: use bf16 operands (set_linear_operands('bf16') or VITSSL_LINEAR_OPERANDS=bf16), which "
+                                f"cover {ops.HD_SUPPORTED}")
+        ops.attn_family(self.dh)      # an unsupported head dim is refused here, before the first kernel of the step
         if self.fp8 and T > FP8_MAX_TOKENS:
             raise L.VitsslError(f"fp8 linear operands support sequences of up to {FP8_MAX_TOKENS} tokens, got {T}: use bf16 "
                                 f"operands (set_linear_operands('bf16') or VITSSL_LINEAR_OPERANDS=bf16), which cover up to "
@@ -535,7 +540,7 @@ class EncoderStack:
             else:
                 ops.layernorm_fwd(*ln1, h1, mean1, rstd1)
                 ops.gemm_nt(h1, st.w(self._n(i, "wqkv")), qkv, L.EPI_BF16)
-                ops.attn_fwd(qkv, att, lse, B, T, H, dh, probs=probs if i == self.L - 1 else None)
+                ops.attn_fwd_any(qkv, att, lse, B, T, H, dh, probs=probs if i == self.L - 1 else None)
                 ops.gemm_nt(att, st.w(self._n(i, "wo")), xmid, L.EPI_RESID, aux=cur, drop=self._drop(i, 0, seed, training))
                 ops.layernorm_fwd(*ln2, h2, mean2, rstd2)
                 ops.gemm_nt(h2, st.w(self._n(i, "w1")), u, L.EPI_GELU, bias=b1, out1=a, drop=self._drop(i, 1, seed, training))
@@ -609,7 +614,7 @@ class EncoderStack:
             ops.gemm_nt(gm2, st.w(self._n(i, "wo") + ".T"), dh_, L.EPI_BF16)
             if wgrad and not batch:
                 ops.gemm_tn(*wgrads[2])
-            ops.attn_bwd(s["qkv"], s["att"], dh_, s["lse"], dqkv, delta, B, T, H, dh)
+            ops.attn_bwd_any(s["qkv"], s["att"], dh_, s["lse"], dqkv, delta, B, T, H, dh)
             ops.gemm_nt(dqkv, st.w(self._n(i, "wqkv") + ".T"), dh_, L.EPI_BF16)
             if wgrad and batch:
                 ops.gemm_tn_batch(wgrads)      # before the LayerNorm-1 backward below overwrites gm for the next block

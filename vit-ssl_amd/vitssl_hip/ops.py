@@ -2,6 +2,7 @@
 host (a wrong shape must never reach a hand-written kernel), then enqueue on torch's
 current stream.  No computation happens in Python and there is no fallback path."""
 import ctypes as C
+import operator
 
 import torch
 
@@ -364,6 +365,48 @@ def _attn_bwd(qkv, out, dout, lse, dqkv, delta_ws, B, N, H, dh):
     call("vitssl_attn_bwd", _chk(qkv, BF16, "qkv", (B * N, 3 * H * dh)), _chk(out, BF16, "out", (B * N, H * dh)),
          _chk(dout, BF16, "dout", (B * N, H * dh)), _chk(lse, F32, "lse", (B, H, N)),
          _chk(dqkv, BF16, "dqkv", (B * N, 3 * H * dh)), _chk(delta_ws, F32, "delta_ws", (B, H, N)), B, N, H, dh, _stream())
+
+
+# ---- head dims other than 64 (include/vitssl_attention_hd.h) and the dispatch between the two families
+HD_MIN, HD_MAX, HD_STEP = 8, 128, 8
+HD_SUPPORTED = "head dims 8, 16, ..., 128 (multiples of 8; 64 runs the dh = 64 kernels)"
+
+
+def attn_hd_fwd(qkv, out, lse, B, N, H, dh, probs=None):
+    ev = _prof_begin()
+    call("vitssl_attn_hd_fwd", _chk(qkv, BF16, "qkv", (B * N, 3 * H * dh)), _chk(out, BF16, "out", (B * N, H * dh)),
+         _chk(lse, F32, "lse", (B, H, N)), _opt(probs, F32, "probs", (B, H, N, N)), B, N, H, dh, _stream())
+    _prof_end(ev, f"attn_hd_fwd B{B} N{N} H{H} dh{dh}", 4.0 * B * H * N * N * dh)
+
+
+def attn_hd_bwd(qkv, out, dout, lse, dqkv, delta_ws, B, N, H, dh):
+    ev = _prof_begin()
+    call("vitssl_attn_hd_bwd", _chk(qkv, BF16, "qkv", (B * N, 3 * H * dh)), _chk(out, BF16, "out", (B * N, H * dh)),
+         _chk(dout, BF16, "dout", (B * N, H * dh)), _chk(lse, F32, "lse", (B, H, N)),
+         _chk(dqkv, BF16, "dqkv", (B * N, 3 * H * dh)), _chk(delta_ws, F32, "delta_ws", (B, H, N)), B, N, H, dh, _stream())
+    _prof_end(ev, f"attn_hd_bwd B{B} N{N} H{H} dh{dh}", 8.0 * B * H * N * N * dh)
+
+
+def attn_family(dh):
+    """-> (attn_fwd, attn_bwd) of the kernel family that serves head dim `dh` with bf16 operands: the dh = 64 kernels for 64,
+    the head-dim-templated streaming kernels for every other supported value.  Raises before anything is launched."""
+    try:
+        d = operator.index(dh)        # Python, numpy and symbolic integers alike
+    except TypeError:
+        d = None
+    if d == 64:
+        return attn_fwd, attn_bwd
+    if d is not None and HD_MIN <= d <= HD_MAX and d % HD_STEP == 0:
+        return attn_hd_fwd, attn_hd_bwd
+    raise L.VitsslError(f"head dim {dh} (embed_dim / num_heads) unsupported by the attention kernels: supported are {HD_SUPPORTED}")
+
+
+def attn_fwd_any(qkv, out, lse, B, N, H, dh, probs=None):
+    attn_family(dh)[0](qkv, out, lse, B, N, H, dh, probs=probs)
+
+
+def attn_bwd_any(qkv, out, dout, lse, dqkv, delta_ws, B, N, H, dh):
+    attn_family(dh)[1](qkv, out, dout, lse, dqkv, delta_ws, B, N, H, dh)
 
 
 def patchify_bf16(img, patches, P):
