@@ -16,12 +16,17 @@ class BackboneRuntime:
         self.names = embed_names
         self.C, self.P, self.grid = in_ch, patch, tuple(grid)
         self.D = D
-        self.Pd = in_ch * patch * patch
+        self.geo = R.PatchGeometry(in_ch, patch)     # widths of the patch path (padded inside the engine where the GEMMs need it)
+        self.Pd, self.Pdp = self.geo.Pd, self.geo.Pdp
         self.T0 = grid[0] * grid[1] + 1
         blocks = [f"{prefix}encoder_blocks.{i}." for i in range(num_blocks)]
         self.stack = R.EncoderStack(store, blocks, D, H, Fd, p_drop, site_base=site_base)
         self.wkey = prefix + "patch_proj"
-        store.register_weight(self.wkey, lambda: store.view(embed_names["weight"], (D, self.Pd)), transposed_too=False)
+        if self.geo.native:
+            store.register_weight(self.wkey, lambda: store.view(embed_names["weight"], (D, self.Pd)), transposed_too=False)
+        else:     # the projection image carries zero pad columns
+            store.register_padded_weight(self.wkey, lambda: store.view(embed_names["weight"], (D, self.Pd)), D, self.Pdp,
+                                         transposed_too=False)
         self.ws = R.Workspace()
         self.rec = {}
 
@@ -55,8 +60,8 @@ class BackboneRuntime:
         # a forward that saves nothing (no_grad / eval) must not touch the buffers a pending
         # backward of the same slot still needs
         wtag = slot if save else slot + ".tmp"
-        patches = ws.get(f"{wtag}.patches", (B * tokens, self.Pd), BF16, dev)
-        ops.patchify_bf16(x, patches, self.P)
+        patches = ws.get(f"{wtag}.patches", (B * tokens, self.Pdp), BF16, dev)
+        self.geo.patchify(x, patches)
         x0 = ws.get(f"{wtag}.x0", (B * T, self.D), F32, dev)
         ops.gemm_nt(patches, st.w(self.wkey), x0, L.EPI_EMBED, bias=st.view(self.names["bias"]),
                     embed=(None, None, pos, tokens, T, 1))
@@ -98,6 +103,6 @@ class BackboneRuntime:
             gpos[0].add_(dpos[0])                               # CLS row: identity
             ops.bicubic_resize_bwd(dpos[1:], gpos[1:], self.grid[0], self.grid[1], gh, gw)
         if proj_wgrad:
-            ops.gemm_tn(dproj, rec["patches"], gv(self.names["weight"], (self.D, self.Pd)))
+            self.geo.proj_wgrad(dproj, rec["patches"], gv(self.names["weight"], (self.D, self.Pd)), ws)
         # the CLS position also receives the CLS-row gradient through `cls + pos[0]`:
         # embed_bwd already added row 0 of every image to dpos[0] and to dcls.

@@ -437,11 +437,18 @@ class _PatchEmbedFn(Function):
         T = tokens + 1
         if pos.shape[0] != T:
             raise L.VitsslError(f"positional embedding has {pos.shape[0]} rows, input needs {T}")
-        patches = _empty((Bn * tokens, Pd), BF16, img)
-        ops.patchify_bf16(img, patches, P)
-        wb, _ = weight_bf16(w, want_t=False)
-        if wb.shape[0] != D:
+        if D % 8 != 0:
             raise L.VitsslError("patch embedding: embed dim must be a multiple of 8")
+        geo = R.PatchGeometry(Cc, P)
+        if geo.Pd != Pd:
+            raise L.VitsslError(f"patch embedding: weight has {Pd} input features, a {Cc}-channel patch of side {P} has {geo.Pd}")
+        patches = _empty((Bn * tokens, geo.Pdp), BF16, img)
+        geo.patchify(img, patches)
+        if geo.native:
+            wb, _ = weight_bf16(w, want_t=False)
+        else:     # zero pad columns in the weight image, as in the patches
+            wb = torch.zeros(D, geo.Pdp, dtype=BF16, device=img.device)
+            ops.CastPlanLd().run([(R.as_f32(w.detach()), wb, None)])
         out = _empty((Bn * T, D), F32, img)
         posf = R.as_f32(pos.detach())
         ops.gemm_nt(patches, wb, out, L.EPI_EMBED, bias=R.as_f32(b.detach()), embed=(None, None, posf, tokens, T, 1))
@@ -449,6 +456,7 @@ class _PatchEmbedFn(Function):
         out[:, 0] = cls.detach().reshape(D).float() + posf[0]
         ctx.save_for_backward(patches)
         ctx.meta = (Bn, tokens, T, D, Pd)
+        ctx.geo = geo
         return out
 
     @staticmethod
@@ -463,7 +471,7 @@ class _PatchEmbedFn(Function):
         dcls = torch.zeros(D, dtype=F32, device=dev)
         ops.embed_bwd(d, None, dproj, dpos, None, dbias, dcls, Bn, tokens, 1, D)
         dw = torch.zeros(D, Pd, dtype=F32, device=dev)
-        ops.gemm_tn(dproj, patches, dw)
+        ctx.geo.proj_wgrad(dproj, patches, dw, R.Workspace())
         return None, dw, dbias, dcls.view(1, 1, D), dpos, None
 
 

@@ -33,14 +33,20 @@ class _SimMIMRuntime:
         self.P = model.patch_size
         self.C, self.H, self.W = C, H, W
         self.N = (H // self.P) * (W // self.P)
-        self.Pd = C * self.P * self.P
+        self.geo = R.PatchGeometry(C, self.P)     # widths of the patch path (padded inside the engine where the GEMMs need it)
+        self.Pd, self.Pdp, self.Np = self.geo.Pd, self.geo.Pdp, self.geo.Np
         self.D = model.embed_dim
         self.store = R.FlatStore(model, device)
         st = self.store
         prefixes = [f"encoder_blocks.{i}." for i in range(len(model.encoder_blocks))]
         self.stack = R.EncoderStack(st, prefixes, self.D, model.num_heads, model.mlp_dim, model.dropout_p)
-        st.register_weight("proj", lambda: st.view("projection.weight", (self.D, self.Pd)), transposed_too=False)
-        st.register_weight("head", lambda: st.view("simmim_head.weight", (self.Pd, self.D)))
+        if self.geo.native:
+            st.register_weight("proj", lambda: st.view("projection.weight", (self.D, self.Pd)), transposed_too=False)
+            st.register_weight("head", lambda: st.view("simmim_head.weight", (self.Pd, self.D)))
+        else:     # zero pad columns in the projection image, zero pad rows / columns in the head image and its transpose
+            st.register_padded_weight("proj", lambda: st.view("projection.weight", (self.D, self.Pd)), self.D, self.Pdp,
+                                      transposed_too=False)
+            st.register_padded_weight("head", lambda: st.view("simmim_head.weight", (self.Pd, self.D)), self.Pdp, self.D)
         self.ws = R.Workspace()
         self.rec = None
         self.save_gen = 0      # id of the forward whose activations `rec` / the stack hold
@@ -56,8 +62,8 @@ class _SimMIMRuntime:
         st, ws = self.store, self.ws
         B = x.shape[0]
         M = B * self.N
-        patches = ws.get(tag + "patches", (M, self.Pd), BF16, x.device)
-        ops.patchify_bf16(x, patches, self.P)
+        patches = ws.get(tag + "patches", (M, self.Pdp), BF16, x.device)
+        self.geo.patchify(x, patches)
         x0 = ws.get(tag + "x0", (M, self.D), F32, x.device)
         ops.gemm_nt(patches, st.w("proj"), x0, L.EPI_EMBED, bias=st.view("projection.bias"),
                     embed=(mask_d, st.view("mask_token") if mask_d is not None else None,
@@ -125,14 +131,27 @@ class _SimMIMRuntime:
                 self.save_gen += 1
                 self.rec = dict(B=B, M=M, Mm=0)
             return torch.empty(0, self.Pd, dtype=F32, device=dev), targets, mask_d.view(B, self.N, 1).bool()
-        ops.gather_patches_f32(x, idx_d, targets, self.P)
+        if self.geo.native:
+            ops.gather_patches_f32(x, idx_d, targets, self.P)
+        else:
+            ops.gather_patches_any_f32(x, idx_d, targets, self.P)
         tag = "" if save else "tmp."
         x0, patches = self.embed(x, mask_d, tag)
         xL, _ = self.stack.forward(x0, B, self.N, training, seed, save=save, slot="a")
         sel = ws.get(tag + "sel", (Mm, self.D), BF16, dev)
         ops.gather_rows_bf16(xL, idx_d, sel)
-        pred = torch.empty(Mm, self.Pd, dtype=F32, device=dev)
-        ops.gemm_nt(sel, st.w("head"), pred, L.EPI_F32, bias=st.view("simmim_head.bias"))
+        if self.Np == self.Pd:
+            pred = torch.empty(Mm, self.Pd, dtype=F32, device=dev)
+            ops.gemm_nt(sel, st.w("head")[:self.Pd], pred, L.EPI_F32, bias=st.view("simmim_head.bias"))
+        else:
+            # Pd % 4 != 0: the head GEMM writes the padded width (zero weight rows and zero bias give zero pad columns);
+            # the public prediction is the column prefix of that buffer
+            bias = ws.get("pad.head_bias", (self.Np,), F32, dev)
+            bias.zero_()
+            bias[:self.Pd].copy_(st.view("simmim_head.bias"))
+            wide = torch.empty(Mm, self.Np, dtype=F32, device=dev)
+            ops.gemm_nt(sel, st.w("head"), wide, L.EPI_F32, bias=bias)
+            pred = wide[:, :self.Pd]
         if save:
             self.save_gen += 1
             self.rec = dict(B=B, M=M, Mm=Mm, idx=idx_d, inv=inv_d, mask=mask_d, patches=patches, sel=sel)
@@ -140,8 +159,8 @@ class _SimMIMRuntime:
 
     # ------------------------------------------------------------------ backward
     def backward(self, dpred_bf16, reducer=None):
-        """dpred_bf16: bf16 [Mm, Pd].  Accumulates every parameter gradient into the
-        store's flat gradient buffer (caller zeroes it)."""
+        """dpred_bf16: bf16 [Mm, Pdp] (Pdp = Pd unless the geometry is padded; pad columns zero).  Accumulates every parameter
+        gradient into the store's flat gradient buffer (caller zeroes it)."""
         st, ws, rec = self.store, self.ws, self.rec
         B, M, Mm = rec["B"], rec["M"], rec["Mm"]
         if Mm == 0:                                      # empty prediction: every gradient is zero (the buffer already is)
@@ -150,8 +169,19 @@ class _SimMIMRuntime:
             return
         dev = dpred_bf16.device
         gv = st.gview
-        ops.colsum_bf16(dpred_bf16, gv("simmim_head.bias"))
-        ops.gemm_tn(dpred_bf16, rec["sel"], gv("simmim_head.weight", (self.Pd, self.D)))
+        if self.geo.native:
+            ops.colsum_bf16(dpred_bf16, gv("simmim_head.bias"))
+            ops.gemm_tn(dpred_bf16, rec["sel"], gv("simmim_head.weight", (self.Pd, self.D)))
+        else:
+            # bias and weight gradients at the padded width, then their first Pd entries / rows into the flat buffer
+            hb = ws.get("pad.head_bgrad", (1, self.Pdp), F32, dev)
+            hw = ws.get("pad.head_wgrad", (self.Pdp, self.D), F32, dev)
+            hb.zero_()
+            hw.zero_()
+            ops.colsum_bf16(dpred_bf16, hb.view(self.Pdp))
+            ops.gemm_tn(dpred_bf16, rec["sel"], hw)
+            ops.accumulate_ld_f32(gv("simmim_head.bias", (1, self.Pd)), hb)
+            ops.accumulate_ld_f32(gv("simmim_head.weight", (self.Pd, self.D)), hw[:self.Pd])
         dsel = ws.get("dsel", (Mm, self.D), BF16, dev)
         ops.gemm_nt(dpred_bf16, st.w("head.T"), dsel, L.EPI_BF16)
         g = ws.get("g", (M, self.D), F32, dev)
@@ -162,7 +192,7 @@ class _SimMIMRuntime:
         dproj = ws.get("dproj", (M, self.D), BF16, dev)
         ops.embed_bwd(g, rec["mask"], dproj, gv("positional_embedding", (self.N, self.D)), gv("mask_token"),
                       gv("projection.bias"), None, B, self.N, 0, self.D)
-        ops.gemm_tn(dproj, rec["patches"], gv("projection.weight", (self.D, self.Pd)))
+        self.geo.proj_wgrad(dproj, rec["patches"], gv("projection.weight", (self.D, self.Pd)), ws)
         if reducer is not None:
             reducer.ready(*st.span("mask_token", "positional_embedding"))
             reducer.ready(*st.span("projection.weight", "projection.bias"))
@@ -185,6 +215,10 @@ class _SimMIMFn(Function):
             dpb = torch.empty(dp.shape, dtype=BF16, device=dp.device)
             if dp.numel() > 0:
                 ops.cast_bf16(dp, dpb)
+            if rt.Pdp != rt.Pd and dp.numel() > 0:      # the engine's backward reads the padded width
+                wide = torch.zeros(dp.shape[0], rt.Pdp, dtype=BF16, device=dp.device)
+                wide[:, :rt.Pd] = dpb
+                dpb = wide
             rt.backward(dpb)
 
         return (None, None, None, None, *R.backward_grads("SimMIMViT", ctx.gen, rt.save_gen, rt.store, run))
@@ -274,8 +308,11 @@ class SimMIMViT(nn.Module):
                 n = 1
                 rt.backward(pred, reducer)
             else:
-                dpb = rt.ws.get("dpred", tuple(pred.shape), BF16, x.device)
-                ops.l1_loss(pred, targets, loss_sum, dpb, gscale=1.0 / n)
+                dpb = rt.ws.get("dpred", (pred.shape[0], rt.Pdp), BF16, x.device)
+                if rt.geo.native:
+                    ops.l1_loss(pred, targets, loss_sum, dpb, gscale=1.0 / n)
+                else:
+                    ops.l1_loss_ld(pred, targets, loss_sum, dpb, gscale=1.0 / n)
                 rt.backward(dpb, reducer)
             apply()
             self.last_pred, self.last_targets = pred, targets

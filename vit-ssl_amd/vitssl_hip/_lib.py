@@ -12,6 +12,7 @@ TRANSFORMS_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "inclu
 METRICS_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "vitssl_metrics.h"))
 CLASSIFY_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "vitssl_classify.h"))
 ATTENTION_HD_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "vitssl_attention_hd.h"))
+PATCH_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "vitssl_patch.h"))
 
 
 class VitsslError(RuntimeError):
@@ -135,6 +136,16 @@ PROTOTYPES_ATTENTION_HD = {
     "vitssl_attn_hd_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
 }
 
+# include/vitssl_patch.h (the patch path for any patch side and channel count: matrices with a row stride whose pad columns
+# stay zero): every entry point launches.
+PROTOTYPES_PATCH = {
+    "vitssl_patchify_ld_bf16": [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
+    "vitssl_gather_patches_any_f32": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
+    "vitssl_l1_loss_ld": [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _f, _i64, _i, _vp, _i64, _vp],
+    "vitssl_accumulate_ld_f32": [_vp, _vp, _i64, _i, _i64, _vp],
+    "vitssl_cast_transpose_batch_ld": [_vp, _vp, _i, _i, _vp],
+}
+
 _lib = None
 
 
@@ -169,6 +180,13 @@ def classify_header_symbols():
 def attention_hd_header_symbols():
     """Entry points declared in include/vitssl_attention_hd.h."""
     with open(ATTENTION_HD_HEADER_PATH) as f:
+        txt = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)        # the comments name functions of vitssl_hip.h
+    return sorted(set(re.findall(r"\b(vitssl_[a-z0-9_]+)\s*\(", txt)))
+
+
+def patch_header_symbols():
+    """Entry points declared in include/vitssl_patch.h."""
+    with open(PATCH_HEADER_PATH) as f:
         txt = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)        # the comments name functions of vitssl_hip.h
     return sorted(set(re.findall(r"\b(vitssl_[a-z0-9_]+)\s*\(", txt)))
 
@@ -221,7 +239,7 @@ def lib():
     l.vitssl_classify_loss_workspace_floats.restype = C.c_int64
     l.vitssl_classify_loss_workspace_floats.argtypes = [C.c_int, C.c_int]
     for name, args in (list(PROTOTYPES.items()) + list(PROTOTYPES_TRANSFORMS.items()) + list(PROTOTYPES_METRICS.items())
-                       + list(PROTOTYPES_CLASSIFY.items()) + list(PROTOTYPES_ATTENTION_HD.items())):
+                       + list(PROTOTYPES_CLASSIFY.items()) + list(PROTOTYPES_ATTENTION_HD.items()) + list(PROTOTYPES_PATCH.items())):
         fn = getattr(l, name)  # AttributeError if the symbol is missing
         fn.restype = C.c_int
         fn.argtypes = args

@@ -56,6 +56,44 @@ def _round_up(n: int, a: int) -> int:
     return (n + a - 1) // a * a
 
 
+class PatchGeometry:
+    """Widths of the patch path of one model.  Pd = C * P * P is the contraction length of the patch projection and of the SimMIM
+    head's input-gradient GEMM, and the output width of the head.  A geometry the kernels of vitssl_hip.h take as it is
+    (P % 4 == 0 and Pd % 64 == 0) keeps its entry points and buffers.  Every other one runs at the padded width
+    Pdp = round_up(Pd, 64) inside the engine (include/vitssl_patch.h): patches, the bf16 weight images and the head's gradient
+    carry zero pad columns; parameters, gradients and the public tensors keep the reference's shapes."""
+
+    def __init__(self, C: int, P: int):
+        self.C, self.P = int(C), int(P)
+        self.Pd = self.C * self.P * self.P
+        self.native = self.P % 4 == 0 and self.Pd % 64 == 0
+        self.Pdp = self.Pd if self.native else _round_up(self.Pd, 64)
+        if self.C < 1 or self.P < 1:
+            raise L.VitsslError(f"patch_size={P} and the channel count {C} of input_shape must be positive")
+        if not self.native and self.C * self.P * (self.P + 31) > 16000:      # the LDS tile of csrc/patch.hip (include/vitssl_patch.h)
+            raise L.VitsslError(f"patch_size={P} with {C} channels: the channel rows of one patch do not fit the patchify kernel's "
+                                f"LDS tile (C * P * (P + 31) = {self.C * self.P * (self.P + 31)} > 16000); a patch size that is a multiple "
+                                "of 4 with C * P * P a multiple of 64 has no such limit")
+        # output width of the head GEMM (N % 4 == 0): Pd itself where it qualifies, else the padded width
+        self.Np = self.Pd if self.Pd % 4 == 0 else self.Pdp
+
+    def patchify(self, x, patches):
+        if self.native:
+            ops.patchify_bf16(x, patches, self.P)
+        else:
+            ops.patchify_ld_bf16(x, patches, self.P)
+
+    def proj_wgrad(self, dproj, patches, gw, ws: "Workspace"):
+        """gw f32 [D, Pd] += dproj^T @ patches[:, :Pd]"""
+        if self.native:
+            ops.gemm_tn(dproj, patches, gw)
+            return
+        tmp = ws.get("pad.proj_wgrad", (gw.shape[0], self.Pdp), F32, gw.device)
+        tmp.zero_()
+        ops.gemm_tn(dproj, patches, tmp)
+        ops.accumulate_ld_f32(gw, tmp)      # the column prefix of the padded result
+
+
 class Workspace:
     """Named device buffers reused across steps (no allocation in steady state)."""
 
@@ -113,6 +151,7 @@ class FlatStore:
         self._bf16_key = None
         self.generation = 0   # bumped whenever the flat buffer is rewritten behind torch's back
         self._cast_jobs: List[Tuple[str, Callable[[], torch.Tensor], bool, bool]] = []
+        self._cast_pad: Dict[str, Tuple[int, int]] = {}    # key -> padded (rows, cols) of its bf16 images
         self._fp8: Dict[str, torch.Tensor] = {}
         self._fp8_jobs: List[Tuple[str, Callable[[], torch.Tensor]]] = []
         self._fp8_plan = None
@@ -183,6 +222,13 @@ class FlatStore:
         `key + '.T'` (bf16 [K,N], the operand of the dgrad GEMM)."""
         self._cast_jobs.append((key, src, transposed_too and not self.forward_only, plain))
 
+    def register_padded_weight(self, key: str, src: Callable[[], torch.Tensor], rows: int, cols: int, transposed_too: bool = True):
+        """register_weight for a patch-facing weight [N,K] whose bf16 images are kept at the padded shape [rows, cols] /
+        [cols, rows] (rows >= N, cols >= K).  The images are allocated zeroed and the cast writes the source's image only
+        (one launch for the whole store, ops.CastPlanLd), so the pad rows and columns are zero after every refresh."""
+        self._cast_pad[key] = (int(rows), int(cols))
+        self.register_weight(key, src, transposed_too)
+
     def register_fp8_weight(self, key: str, src: Callable[[], torch.Tensor]):
         """Declare a 2-D GEMM weight [N,K] whose GEMM operands are e4m3 images with a per-tensor power-of-two
         scale: `w8(key)` returns (image [N,K], dequantisation factor as a 1-element device tensor), `w8t(key)`
@@ -198,20 +244,24 @@ class FlatStore:
         for wname, src, tr, plain in self._cast_jobs:     # (never `key`: that is the cache key stored below)
             w = src()
             R, Cn = w.shape
+            alloc = torch.empty
+            if wname in self._cast_pad:      # padded images: zeroed once, the cast never touches the pad
+                R, Cn = self._cast_pad[wname]
+                alloc = torch.zeros
             dst = self._bf16.get(wname) if plain else None
             if plain and (dst is None or dst.shape != (R, Cn)):
-                dst = torch.empty(R, Cn, dtype=BF16, device=self.device)
+                dst = alloc(R, Cn, dtype=BF16, device=self.device)
                 self._bf16[wname] = dst
             dst_t = None
             if tr:
                 dst_t = self._bf16.get(wname + ".T")
                 if dst_t is None or dst_t.shape != (Cn, R):
-                    dst_t = torch.empty(Cn, R, dtype=BF16, device=self.device)
+                    dst_t = alloc(Cn, R, dtype=BF16, device=self.device)
                     self._bf16[wname + ".T"] = dst_t
             jobs.append((w.contiguous(), dst, dst_t))
         if jobs:      # every weight of the store in one launch (was ~50 launches of ~12 us)
             if getattr(self, "_cast_plan", None) is None:
-                self._cast_plan = ops.CastPlan()
+                self._cast_plan = ops.CastPlanLd() if self._cast_pad else ops.CastPlan()
             self._cast_plan.run(jobs)
         if self._fp8_jobs:
             jobs8 = []

@@ -513,6 +513,98 @@ class CastPlan:
              self.njobs, self.total, _stream())
 
 
+# ---- the patch path for any patch side and channel count (include/vitssl_patch.h) ----
+def _chk_ld(t, dtype, name, rows, cols):
+    """A [rows, cols] matrix with unit column stride whose rows lie `ld` >= cols elements apart (a contiguous matrix or the
+    column prefix of a wider one) -> (pointer, ld)."""
+    if t is None:
+        raise L.VitsslError(f"{name}: tensor is None")
+    if not t.is_cuda or t.device.index != torch.cuda.current_device():
+        raise L.VitsslError(f"{name}: expected a tensor of the current CUDA (HIP) device, got {t.device}; there is no CPU fallback")
+    if t.dtype != dtype:
+        raise L.VitsslError(f"{name}: expected dtype {dtype}, got {t.dtype}")
+    if tuple(t.shape) != (rows, cols):
+        raise L.VitsslError(f"{name}: expected shape {(rows, cols)}, got {tuple(t.shape)}")
+    ld = t.stride(0) if rows > 1 else max(t.stride(0), cols)
+    if t.stride(1) != 1 or ld < cols:
+        raise L.VitsslError(f"{name}: expected unit column stride and a row stride >= {cols}, got strides {tuple(t.stride())}")
+    return C.c_void_p(t.data_ptr()), int(ld)
+
+
+def patchify_ld_bf16(img, patches, P):
+    """img f32 [B,C,H,W] -> patches bf16 [B*gh*gw, ld], ld >= C*P*P, any P; columns C*P*P .. ld-1 are written as zeros"""
+    B, Cc, H, W = img.shape
+    if P <= 0 or H % P != 0 or W % P != 0:
+        raise L.VitsslError(f"patchify_ld: image {H}x{W} not divisible by patch {P}")
+    rows = B * (H // P) * (W // P)
+    if patches is None or patches.dim() != 2 or patches.shape[1] < Cc * P * P:
+        raise L.VitsslError(f"patchify_ld: expected patches [{rows}, ld >= {Cc * P * P}], got {None if patches is None else tuple(patches.shape)}")
+    call("vitssl_patchify_ld_bf16", _chk(img, F32, "img"), _chk(patches, BF16, "patches", (rows, patches.shape[1])), B, Cc, H, W, P,
+         patches.shape[1], _stream())
+
+
+def gather_patches_any_f32(img, idx, out, P):
+    B, Cc, H, W = img.shape
+    n = idx.numel()
+    call("vitssl_gather_patches_any_f32", _chk(img, F32, "img"), _chk(idx, torch.int32, "idx"), _chk(out, F32, "out", (n, Cc * P * P)),
+         n, Cc, H, W, P, _stream())
+
+
+def l1_loss_ld(pred, target, loss_sum, dpred=None, gscale=0.0):
+    """L1 loss of pred / target f32 [rows, cols] (each contiguous or a column prefix of a wider matrix); dpred bf16 [rows, ld_d]
+    contiguous, ld_d >= cols: +-gscale / 0 in the first cols columns, zeros behind them."""
+    rows, cols = pred.shape
+    pp, ld_p = _chk_ld(pred, F32, "pred", rows, cols)
+    tp, ld_t = _chk_ld(target, F32, "target", rows, cols)
+    ld_d = 0
+    if dpred is not None:
+        if dpred.dim() != 2 or dpred.shape[0] != rows or dpred.shape[1] < cols:
+            raise L.VitsslError(f"l1_loss_ld: dpred must be [{rows}, ld_d >= {cols}], got {tuple(dpred.shape)}")
+        ld_d = dpred.shape[1]
+    call("vitssl_l1_loss_ld", pp, ld_p, tp, ld_t, _chk(loss_sum, F32, "loss_sum", (1,)), _opt(dpred, BF16, "dpred"), ld_d, float(gscale),
+         rows, cols, *_sum_ws(pred.device, rows * cols, 1), _stream())
+
+
+def accumulate_ld_f32(dst, src, cols=None):
+    """dst f32 [rows, cols] (contiguous) += src[:, :cols] of src f32 [rows, ld] (contiguous)"""
+    rows, c = dst.shape
+    if src is None or src.dim() != 2 or src.shape[0] != rows or src.shape[1] < c:
+        raise L.VitsslError(f"accumulate_ld: src must be [{rows}, ld >= {c}], got {None if src is None else tuple(src.shape)}")
+    call("vitssl_accumulate_ld_f32", _chk(dst, F32, "dst"), _chk(src, F32, "src"), rows, c, src.shape[1], _stream())
+
+
+class CastPlanLd(CastPlan):
+    """CastPlan whose destinations may be wider / taller than the source (`vitssl_cast_transpose_batch_ld`): dst bf16
+    [>= R, ld >= C], dst_t bf16 [>= C, ld >= R].  Only the image of the source is written; the destinations are allocated
+    zeroed, so their pad stays zero through every refresh."""
+
+    def run(self, jobs):
+        import numpy as np
+        key = tuple((s.data_ptr(), 0 if d is None else d.data_ptr(), 0 if t is None else t.data_ptr(), s.shape[0], s.shape[1],
+                     0 if d is None else d.shape[1], 0 if t is None else t.shape[1]) for s, d, t in jobs)
+        if key != self.key:
+            for s, d, t in jobs:
+                R, Cn = s.shape
+                _chk(s, F32, "src"); _opt(d, BF16, "dst"); _opt(t, BF16, "dst_t")
+                if d is not None and (d.dim() != 2 or d.shape[0] < R or d.shape[1] < Cn):
+                    raise L.VitsslError(f"cast plan: dst {tuple(d.shape)} does not hold the [{R}, {Cn}] source")
+                if t is not None and (t.dim() != 2 or t.shape[0] < Cn or t.shape[1] < R):
+                    raise L.VitsslError(f"cast plan: dst_t {tuple(t.shape)} does not hold the transposed [{R}, {Cn}] source")
+            dev = jobs[0][0].device
+            rec = np.zeros(len(jobs), dtype=np.dtype([("src", "<u8"), ("dst", "<u8"), ("dst_t", "<u8"), ("R", "<i4"), ("C", "<i4"),
+                                                      ("ld_dst", "<i4"), ("ld_dst_t", "<i4")]))
+            starts = np.zeros(len(jobs) + 1, dtype=np.int32)
+            for i, k in enumerate(key):
+                rec[i] = k
+                starts[i + 1] = starts[i] + ((k[3] + 63) // 64) * ((k[4] + 63) // 64)
+            self.jobs_dev = torch.from_numpy(rec.view(np.uint8).copy()).to(dev)
+            self.starts_dev = torch.from_numpy(starts).to(dev)
+            self.njobs, self.total, self.key = len(jobs), int(starts[-1]), key
+        self.keep = jobs        # the sources must outlive the launch
+        call("vitssl_cast_transpose_batch_ld", C.c_void_p(self.jobs_dev.data_ptr()), C.c_void_p(self.starts_dev.data_ptr()),
+             self.njobs, self.total, _stream())
+
+
 class Fp8WeightPlan:
     """Device-resident job table for `vitssl_fp8_quantize_weights` (per-tensor power-of-two scales computed on the
     device, no host synchronisation): `alpha` holds one dequantisation factor per job."""
