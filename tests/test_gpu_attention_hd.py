@@ -92,6 +92,20 @@ def test_dh64_against_the_dh64_kernels(ops, N):
     A.check_rows(got, case, f"hd family, dh=64 N={N} rev")
 
 
+@pytest.mark.parametrize("N", [257, 300])
+def test_dh64_run_time_and_folded_head_dim_are_bit_equal(ops, N):
+    """dh = 64 above 256 tokens: ops.attn_hd_* (dh and scale as launch arguments) and ops.attn_* (both folded at compile time)
+    are two instantiations of one template, with the same instruction order per accumulator and an exact scale of 1 / 8: every
+    output is the same bits.  257: one row in the third query tile, one key in the fifth streamed tile; 300: a ragged tail."""
+    q, k, v, dout, qkv = A.randn_inputs(B, N, H, 64, seed=6400 + N)
+    run_time, _ = run(ops.attn_hd_fwd, ops.attn_hd_bwd, qkv, dout, B, N, H, 64, probs=True)
+    folded, _ = run(ops.attn_fwd, ops.attn_bwd, qkv, dout, B, N, H, 64, probs=True)
+    for n in ("out", "lse", "probs", "dq", "dk", "dv"):
+        a, b = run_time[n].contiguous(), folded[n].contiguous()
+        bits = torch.int16 if a.dtype == torch.bfloat16 else torch.int32
+        assert a.dtype == b.dtype and torch.equal(a.view(bits), b.view(bits)), f"N={N}: {n} differs"
+
+
 def test_poisoned_buffers_and_determinism(ops):
     dh, N = A.POISON
     (q, k, v, dout, qkv), ref = A.randn_case(dh, N)

@@ -1,4 +1,4 @@
-"""Streaming attention for 257-2048 tokens (csrc/attention_long.hip) against the CPU oracle: op parity with the bars of
+"""Streaming attention for 257-2048 tokens (dh = 64: the <64, 64> instantiations of csrc/attention_hd.hip) against the CPU oracle: op parity with the bars of
 tests/test_gpu_ops.py::test_attention_fwd_bwd, multi-round grids, run-to-run determinism, large logits with a ragged tail,
 the limits (2048 tokens with bf16 operands, 256 with fp8 operands) and the module / model level at patch 8."""
 import math
@@ -12,7 +12,7 @@ from oracle import vit_oracle as O
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda:0")
-QUERY_TILE = 128      # queries per workgroup of the streaming forward (WG_ROWS in csrc/attention_long.hip)
+QUERY_TILE = 128      # queries per workgroup of the streaming forward (WG_ROWS in csrc/attention_hd.hip)
 
 
 @pytest.fixture(scope="module")

@@ -308,7 +308,7 @@ def run(seed=0, kinds="nt,nt,tn,attn,ln,nt8,tn8,tnb", budget_s=120.0, max_cases=
         elif kind == "attn":
             args = (rng.randint(1, 256),)
             fn = T.test_attention_fwd_bwd
-        elif kind == "attnlong":                             # the streaming kernels (csrc/attention_long.hip); not in the default kinds
+        elif kind == "attnlong":                             # the streaming kernels (csrc/attention_hd.hip at dh = 64, through ops.attn_fwd / attn_bwd); not in the default kinds
             args = (rng.randint(257, 1100),)
             fn = T.test_attention_fwd_bwd
         else:                                                # a quarter of the cases on the row-pair backward (384 columns, even row count)

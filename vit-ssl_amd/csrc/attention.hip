@@ -1,5 +1,5 @@
 // Fused multi-head self-attention for ViT-sized sequences (N <= 256, dh = 64), gfx950.
-// (257-2048 tokens: attention_long.hip, reached through the entry points at the end of this file.)
+// (257-2048 tokens: the streaming kernels of attention_hd.hip, reached through the entry points at the end of this file.)
 //
 // The reference materialises S = QK^T / sqrt(dk), softmax, P.V as four passes over a
 // [B,H,N,N] tensor (vit_core/attention.py:20-23).  Here one workgroup owns one

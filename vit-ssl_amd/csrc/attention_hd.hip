@@ -1,22 +1,29 @@
-// Streaming multi-head self-attention for head dims 8 .. 128 (dh % 8 == 0, 1 .. 2048 tokens, bf16 operands), gfx950.
-// C ABI: include/vitssl_attention_hd.h.
+// Streaming multi-head self-attention (bf16 operands), gfx950: the one implementation behind two entry points.
+//   * head dims 8 .. 128 (dh % 8 == 0), 1 .. 2048 tokens: vitssl_attn_hd_fwd / _bwd, C ABI in include/vitssl_attention_hd.h;
+//   * dh = 64 at 257 .. 2048 tokens: attn_long_fwd / _bwd (attention_tiles.h), reached from vitssl_attn_fwd / _bwd.  Below
+//     that, attention.hip keeps all keys and values of an (image, head) item in LDS, which ends at 256 tokens.
 //
-// The structure is that of attention_long.hip for every sequence length: a workgroup of four waves owns 128 rows of one
-// (image, head) item and the other side of the product streams through LDS in 64-row tiles, two buffers, the next tile
-// arriving by LDS-DMA while the current one is multiplied.  Forward (online softmax in fp32), a separate probs kernel
-// (`out` cannot depend on the probs pointer), and a backward of three launches without atomics: delta = rowsum(dO * O)
-// into the caller's workspace, dK / dV sweeping Q / dO tiles, dQ sweeping K / V tiles.
+// A workgroup of four waves owns 128 rows of one (image, head) item and the other side of the product streams through LDS in
+// 64-row tiles, two buffers, the next tile arriving by LDS-DMA while the current one is multiplied.  A wave owns 32 of the
+// rows as two 16-row MFMA tiles, so that every fragment read from LDS feeds two MFMAs.  Forward (online softmax in fp32: running
+// maximum and running sum, the output accumulators rescaled whenever the maximum moves), a separate probs kernel (`out`
+// cannot depend on the probs pointer), and a backward of three launches without atomics, every output element written once
+// by one workgroup in a fixed order: delta = rowsum(dO * O) into the caller's workspace, dK / dV sweeping Q / dO tiles, dQ
+// sweeping K / V tiles.  Both recompute P = exp(S - lse): 7 matrix products of N^2 x dh instead of the fused backward's 5.
+// Workgroups are numbered item-major and remapped so that one XCD gets a contiguous run: the tiles of an item, and the heads
+// of an image, re-read their streamed operands from one L2.
 //
-// What differs is the tile width.  The kernels are templated on DP, the head dim padded to a whole number of
-// v_mfma_f32_16x16x32_bf16 contraction steps: 32, 64, 96 or 128 columns, i.e. DP / 8 16-byte chunks per tile row.  They read
-// qkv in place: a head's slice of a row is dh / 8 chunks, and only those are fetched.
+// The kernels are templated on DP, the head dim padded to a whole number of v_mfma_f32_16x16x32_bf16 contraction steps: 32,
+// 64, 96 or 128 columns, i.e. DP / 8 16-byte chunks per tile row, and on DHC: 0 takes dh and the scale from the launch (the hd
+// entry points, dh = 64 included), 64 makes them constants (the <64, 64> instantiations behind attn_long_*).  They read qkv in
+// place: a head's slice of a row is dh / 8 chunks, and only those are fetched.
 //   * LDS tiles: the chunks >= dh / 8 of every row are zeroed ONCE, before the first tile is requested, and the LDS-DMA
 //     lanes that would land on them are switched off, so they stay zero for every tile of the sweep.  (A lane's LDS
 //     destination is fixed by its lane number, its source is free: the lane computes which logical chunk its slot holds and
 //     fetches that chunk, or nothing.)
 //   * register fragments read straight from global memory take zeros for those chunks, stores skip them.
-// The scale 1 / sqrt(dh) multiplies the fp32 score accumulators inside the exp2 argument, as the dh = 64 kernels fold 1 / 8.
-// Rounding points are theirs too: bf16 P into P.V, delta from the stored bf16 O, bf16 dS.
+// The scale 1 / sqrt(dh) multiplies the fp32 score accumulators inside the exp2 argument.  Rounding points: bf16 P into P.V,
+// delta from the stored bf16 O, bf16 dS.  At dh = 64 the two instantiations give the same bits.
 #include "common.h"
 #include "attention_tiles.h"
 #include "../../include/vitssl_attention_hd.h"
@@ -67,6 +74,20 @@ __device__ __forceinline__ Item item_of(const bf16_t* qkv, int item, int N, int 
   it.lse0 = (long long)item * N;
   it.h = h;
   return it;
+}
+
+// The head dim as a kernel sees it.  DHC == 0: dh and scale = 1 / sqrt(dh) are the launch's arguments.  DHC == 64: they are the
+// constants 64 and 1 / 8 whatever was passed, so chr = dh / 8 = TL<64>::CH, every test against it folds (no pad chunks, no
+// zeroing, no switched-off DMA lanes) and no register holds either.
+template <int DHC>
+__device__ __forceinline__ void fix_head_dim(int& dh) {
+  static_assert(DHC == 0 || DHC == 64, "run-time head dim, or dh = 64");
+  if constexpr (DHC == 64) dh = 64;
+}
+template <int DHC>
+__device__ __forceinline__ void fix_head_dim(int& dh, float& scale) {
+  fix_head_dim<DHC>(dh);
+  if constexpr (DHC == 64) scale = 0.125f;
 }
 
 // rows [row0, row0 + 64) of X[n][0 .. 8 chr) (n < N) into a streamed-tile buffer: CH wave instructions of 64 chunks each.  Slot
@@ -166,12 +187,13 @@ __device__ __forceinline__ void store_pair_hd(bool row_ok, bf16_t* row, int pr, 
 // tile in 16 registers: running maximum, running sum and the rescale factor are lane scalars, and the accumulators of S^T are
 // directly the B operand of O^T = V^T.P^T.  Keys >= N of the last tile start at -inf.  Rows >= N of the last query tile
 // compute on zeros and are not stored.
-template <int DP, int MINW>
+template <int DP, int DHC, int MINW>
 __global__ __launch_bounds__(64 * LW, MINW) void attn_hd_fwd_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
                                                                   float* __restrict__ lse, int N, int H, int dh, int nqt, float scale) {
   using T = TL<DP>;
   constexpr int KK = T::KK, DT = T::DT, STB = T::ST_BYTES;
   extern __shared__ __attribute__((aligned(16))) char smem[];
+  fix_head_dim<DHC>(dh, scale);
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int g = lane >> 4, li = lane & 15;
@@ -279,12 +301,13 @@ __global__ __launch_bounds__(64 * LW, MINW) void attn_hd_fwd_kernel(const bf16_t
 // ------------------------------------------------------------------ probs (return_attn)
 // grid = items x ceil(N / 128); K tiles stream.  S[q][key] = Q.K^T: the key sits on the lane, so one store instruction covers
 // 16 consecutive keys (64 bytes) of four query rows.  probs = exp(S / sqrt(dh) - lse) with the lse the forward wrote.
-template <int DP>
+template <int DP, int DHC>
 __global__ __launch_bounds__(64 * LW, 2) void attn_hd_probs_kernel(const bf16_t* __restrict__ qkv, const float* __restrict__ lse,
                                                                  float* __restrict__ probs, int N, int H, int dh, int nqt, float scale) {
   using T = TL<DP>;
   constexpr int KK = T::KK, STB = T::ST_BYTES;
   extern __shared__ __attribute__((aligned(16))) char smem[];
+  fix_head_dim<DHC>(dh, scale);
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int g = lane >> 4, li = lane & 15;
@@ -339,9 +362,11 @@ __global__ __launch_bounds__(64 * LW, 2) void attn_hd_probs_kernel(const bf16_t*
 }
 
 // ------------------------------------------------------------------ backward: delta = rowsum(dO * O)
-// eight lanes per (token, head) row of dh values (one or two 16-byte chunks each); delta f32 [B, H, N]
+// eight lanes per (token, head) row of dh values (one or two 16-byte chunks each, exactly one at DHC = 64); delta f32 [B, H, N]
+template <int DHC>
 __global__ __launch_bounds__(256) void attn_hd_delta_kernel(const bf16_t* __restrict__ outp, const bf16_t* __restrict__ dout,
                                                            float* __restrict__ delta, long long rows, int N, int H, int dh) {
+  fix_head_dim<DHC>(dh);
   const long long row = ((long long)blockIdx.x * 256 + threadIdx.x) >> 3;   // = token * H + head
   const int c = threadIdx.x & 7;
   float part = 0.f;
@@ -371,13 +396,14 @@ __global__ __launch_bounds__(256) void attn_hd_delta_kernel(const bf16_t* __rest
 // lse and delta values.  Per 32 queries: S = Q.K^T and dP = dO.V^T (key on the lane, queries in registers),
 // P = exp(S scale - lse), dS = P (dP - delta) scale, dV^T += dO^T.P, dK^T += Q^T.dS.  Queries >= N arrive as zero rows of Q and
 // dO (with lse = delta = 0: P = 1, dS = 0) and add nothing; keys >= N start S at -inf (P = dS = 0) and are not stored.
-template <int DP, int MINW>
+template <int DP, int DHC, int MINW>
 __global__ __launch_bounds__(64 * LW, MINW) void attn_hd_dkv_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dout,
                                                                   const float* __restrict__ lse, const float* __restrict__ delta,
                                                                   bf16_t* __restrict__ dqkv, int N, int H, int dh, int nkt_wg, float scale) {
   using T = TL<DP>;
   constexpr int KK = T::KK, DT = T::DT, STB = T::ST_BYTES;
   extern __shared__ __attribute__((aligned(16))) char smem[];
+  fix_head_dim<DHC>(dh, scale);
   float* scal = (float*)(smem + 4 * STB);       // [buffer][lse | delta][64]
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -497,13 +523,14 @@ __global__ __launch_bounds__(64 * LW, MINW) void attn_hd_dkv_kernel(const bf16_t
 // grid = items x ceil(N / 128); the forward's structure (K / V tiles stream, the query on the lane) with the Q and dO
 // fragments, lse and delta of the wave's 32 queries in registers: S^T = K.Q^T, dP^T = V.dO^T, dS^T = P^T (dP^T - delta) scale,
 // dQ^T[d][q] += K^T.dS^T.
-template <int DP, int MINW>
+template <int DP, int DHC, int MINW>
 __global__ __launch_bounds__(64 * LW, MINW) void attn_hd_dq_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dout,
                                                                  const float* __restrict__ lse, const float* __restrict__ delta,
                                                                  bf16_t* __restrict__ dqkv, int N, int H, int dh, int nqt, float scale) {
   using T = TL<DP>;
   constexpr int KK = T::KK, DT = T::DT, STB = T::ST_BYTES;
   extern __shared__ __attribute__((aligned(16))) char smem[];
+  fix_head_dim<DHC>(dh, scale);
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int g = lane >> 4, li = lane & 15;
@@ -609,7 +636,7 @@ constexpr int HD_LDS_LIMIT = 160 * 1024;
 template <int DP>
 constexpr int dkv_minw() { return DP > 96 ? 1 : 2; }
 
-template <int DP>
+template <int DP, int DHC>
 int launch_fwd_hd(const bf16_t* qkv, bf16_t* out, float* lse, float* probs, int B, int N, int H, int dh, float scale, hipStream_t s) {
   constexpr int lds_fwd = 4 * TL<DP>::ST_BYTES, lds_probs = 2 * TL<DP>::ST_BYTES;
   static_assert(lds_probs <= 48 * 1024, "the probs kernel stays within the default dynamic-LDS limit");
@@ -617,18 +644,18 @@ int launch_fwd_hd(const bf16_t* qkv, bf16_t* out, float* lse, float* probs, int 
   const int wgs = B * H * nqt;
   if constexpr (lds_fwd > 48 * 1024) {
     static VsOnce done{false};
-    if (int rc = ensure_lds(attn_hd_fwd_kernel<DP, 2>, HD_LDS_LIMIT, done, "attn_hd_fwd")) return rc;
+    if (int rc = ensure_lds(attn_hd_fwd_kernel<DP, DHC, 2>, HD_LDS_LIMIT, done, "attn_hd_fwd")) return rc;
   }
-  hipLaunchKernelGGL((attn_hd_fwd_kernel<DP, 2>), dim3(wgs), dim3(64 * LW), lds_fwd, s, qkv, out, lse, N, H, dh, nqt, scale);
+  hipLaunchKernelGGL((attn_hd_fwd_kernel<DP, DHC, 2>), dim3(wgs), dim3(64 * LW), lds_fwd, s, qkv, out, lse, N, H, dh, nqt, scale);
   VS_CHECK_LAUNCH("attn_hd_fwd");
   if (probs) {
-    hipLaunchKernelGGL((attn_hd_probs_kernel<DP>), dim3(wgs), dim3(64 * LW), lds_probs, s, qkv, (const float*)lse, probs, N, H, dh, nqt, scale);
+    hipLaunchKernelGGL((attn_hd_probs_kernel<DP, DHC>), dim3(wgs), dim3(64 * LW), lds_probs, s, qkv, (const float*)lse, probs, N, H, dh, nqt, scale);
     VS_CHECK_LAUNCH("attn_hd_probs");
   }
   return VITSSL_OK;
 }
 
-template <int DP>
+template <int DP, int DHC>
 int launch_bwd_hd(const bf16_t* qkv, const bf16_t* out, const bf16_t* dout, const float* lse, bf16_t* dqkv, float* delta_ws,
                   int B, int N, int H, int dh, float scale, hipStream_t s) {
   constexpr int lds_dq = 4 * TL<DP>::ST_BYTES, lds_dkv = lds_dq + 2 * 2 * 64 * 4;
@@ -638,18 +665,18 @@ int launch_bwd_hd(const bf16_t* qkv, const bf16_t* out, const bf16_t* dout, cons
   const long long rows = (long long)B * N * H;
   if constexpr (lds_dkv > 48 * 1024) {
     static VsOnce done_kv{false};
-    if (int rc = ensure_lds(attn_hd_dkv_kernel<DP, MW>, HD_LDS_LIMIT, done_kv, "attn_hd_dkv")) return rc;
+    if (int rc = ensure_lds(attn_hd_dkv_kernel<DP, DHC, MW>, HD_LDS_LIMIT, done_kv, "attn_hd_dkv")) return rc;
   }
   if constexpr (lds_dq > 48 * 1024) {
     static VsOnce done_q{false};
-    if (int rc = ensure_lds(attn_hd_dq_kernel<DP, 2>, HD_LDS_LIMIT, done_q, "attn_hd_dq")) return rc;
+    if (int rc = ensure_lds(attn_hd_dq_kernel<DP, DHC, 2>, HD_LDS_LIMIT, done_q, "attn_hd_dq")) return rc;
   }
-  hipLaunchKernelGGL(attn_hd_delta_kernel, dim3((unsigned)((rows * 8 + 255) / 256)), dim3(256), 0, s, out, dout, delta_ws, rows, N, H, dh);
+  hipLaunchKernelGGL(attn_hd_delta_kernel<DHC>, dim3((unsigned)((rows * 8 + 255) / 256)), dim3(256), 0, s, out, dout, delta_ws, rows, N, H, dh);
   VS_CHECK_LAUNCH("attn_hd_delta");
-  hipLaunchKernelGGL((attn_hd_dkv_kernel<DP, MW>), dim3(wgs), dim3(64 * LW), lds_dkv, s, qkv, dout, lse, (const float*)delta_ws, dqkv, N, H,
+  hipLaunchKernelGGL((attn_hd_dkv_kernel<DP, DHC, MW>), dim3(wgs), dim3(64 * LW), lds_dkv, s, qkv, dout, lse, (const float*)delta_ws, dqkv, N, H,
                      dh, nt, scale);
   VS_CHECK_LAUNCH("attn_hd_dkv");
-  hipLaunchKernelGGL((attn_hd_dq_kernel<DP, 2>), dim3(wgs), dim3(64 * LW), lds_dq, s, qkv, dout, lse, (const float*)delta_ws, dqkv, N, H, dh,
+  hipLaunchKernelGGL((attn_hd_dq_kernel<DP, DHC, 2>), dim3(wgs), dim3(64 * LW), lds_dq, s, qkv, dout, lse, (const float*)delta_ws, dqkv, N, H, dh,
                      nt, scale);
   VS_CHECK_LAUNCH("attn_hd_dq");
   return VITSSL_OK;
@@ -680,6 +707,22 @@ int check_hd_shape(const char* who, int B, int N, int H, int dh) {
 
 }  // namespace
 
+// dh = 64 at 257 .. ATTN_LONG_MAX_N tokens, for vitssl_attn_fwd / _bwd (attention.hip, which has checked the arguments): the
+// DP = 64 kernels with the head dim folded.  32 KiB (forward, dQ), 16 KiB (probs) and 33 KiB (dK / dV) of dynamic LDS.
+namespace vitssl_attn {
+
+int attn_long_fwd(const bf16_t* qkv, bf16_t* out, float* lse, float* probs, int B, int N, int H, hipStream_t s, int* grid) {
+  if (grid) *grid = B * H * ((N + WG_ROWS - 1) / WG_ROWS);
+  return launch_fwd_hd<64, 64>(qkv, out, lse, probs, B, N, H, 64, 0.125f, s);
+}
+
+int attn_long_bwd(const bf16_t* qkv, const bf16_t* out, const bf16_t* dout, const float* lse, bf16_t* dqkv, float* delta_ws,
+                  int B, int N, int H, hipStream_t s) {
+  return launch_bwd_hd<64, 64>(qkv, out, dout, lse, dqkv, delta_ws, B, N, H, 64, 0.125f, s);
+}
+
+}  // namespace vitssl_attn
+
 extern "C" int vitssl_attn_hd_fwd(const void* qkv, void* out, float* lse, float* probs, int B, int N, int H, int dh, void* stream) {
   VS_CHECK_ARG(qkv, "attn_hd_fwd: qkv is NULL");
   VS_CHECK_ARG(out, "attn_hd_fwd: out is NULL");
@@ -688,7 +731,7 @@ extern "C" int vitssl_attn_hd_fwd(const void* qkv, void* out, float* lse, float*
   VS_CHECK_ARG(aligned16(qkv), "attn_hd_fwd: qkv must be 16-byte aligned");
   VS_CHECK_ARG(aligned16(out), "attn_hd_fwd: out must be 16-byte aligned");
   const float scale = 1.0f / sqrtf((float)dh);
-#define VS_CALL(DP) launch_fwd_hd<DP>((const bf16_t*)qkv, (bf16_t*)out, lse, probs, B, N, H, dh, scale, (hipStream_t)stream)
+#define VS_CALL(DP) launch_fwd_hd<DP, 0>((const bf16_t*)qkv, (bf16_t*)out, lse, probs, B, N, H, dh, scale, (hipStream_t)stream)
   VS_DP_SWITCH(dh, VS_CALL)
 #undef VS_CALL
 }
@@ -708,7 +751,7 @@ extern "C" int vitssl_attn_hd_bwd(const void* qkv, const void* out, const void* 
   VS_CHECK_ARG(aligned16(dqkv), "attn_hd_bwd: dqkv must be 16-byte aligned");
   const float scale = 1.0f / sqrtf((float)dh);
 #define VS_CALL(DP)                                                                                                                   \
-  launch_bwd_hd<DP>((const bf16_t*)qkv, (const bf16_t*)out, (const bf16_t*)dout, lse, (bf16_t*)dqkv, delta_ws, B, N, H, dh, scale, \
+  launch_bwd_hd<DP, 0>((const bf16_t*)qkv, (const bf16_t*)out, (const bf16_t*)dout, lse, (bf16_t*)dqkv, delta_ws, B, N, H, dh, scale, \
                     (hipStream_t)stream)
   VS_DP_SWITCH(dh, VS_CALL)
 #undef VS_CALL

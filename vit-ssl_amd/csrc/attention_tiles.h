@@ -1,5 +1,6 @@
 // Tile layout, fragment reads and row stores shared by the attention kernels (attention.hip: up to 256 tokens, one
-// workgroup per (image, head); attention_long.hip: 257-2048 tokens, keys / values streamed through LDS).
+// workgroup per (image, head)), and the fragment packing, row stores and constants that the streaming kernels of
+// attention_hd.hip take from here too.
 #pragma once
 #include "common.h"
 
@@ -107,7 +108,7 @@ constexpr float LOG2E = 1.4426950408889634f;
 constexpr float SCALE = 0.125f;                  // 1/sqrt(64)
 constexpr float SCALE_LOG2E = SCALE * LOG2E;
 
-// attention_long.hip: launches for 257 .. ATTN_LONG_MAX_N tokens (bf16 operands)
+// attention_hd.hip: launches of the streaming kernels at dh = 64 for 257 .. ATTN_LONG_MAX_N tokens (bf16 operands)
 constexpr int ATTN_LONG_MAX_N = 2048;
 int attn_long_fwd(const bf16_t* qkv, bf16_t* out, float* lse, float* probs, int B, int N, int H, hipStream_t s, int* grid);
 int attn_long_bwd(const bf16_t* qkv, const bf16_t* out, const bf16_t* dout, const float* lse, bf16_t* dqkv, float* delta_ws,

@@ -27,7 +27,7 @@ BF16 = torch.bfloat16
 F32 = torch.float32
 FP8 = ops.FP8
 ALIGN = 64  # elements; keeps every parameter 256-byte aligned inside the flat buffer
-MAX_TOKENS = 2048       # attention: streaming kernels for 257-2048 tokens (bf16 operands), csrc/attention_long.hip
+MAX_TOKENS = 2048       # attention: streaming kernels for 257-2048 tokens (bf16 operands), csrc/attention_hd.hip with dh = 64 folded
 FP8_MAX_TOKENS = 256    # the fp8 attention entry points (e4m3 images of out / dqkv) end where the one-workgroup-per-head kernels do
 
 # Operand type of the FORWARD Linear products inside the encoder blocks: "bf16" (default, the reference's
