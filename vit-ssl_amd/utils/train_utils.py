@@ -5,10 +5,12 @@ Same entry points and config keys as the reference (utils/train_utils.py:12-51:
 `optimizer`, `lr_scheduler.{main,warmup}`, `warmup_*`), different machinery: every section is
 read through `_spec` into a (name, kwargs) pair, and an AdamW request over a model that exposes
 its flat parameter store is answered with the fused flat-buffer optimizer kernel instead of
-torch.optim.AdamW.  `get_transforms` returns callables with the reference's per-image semantics that also carry the
+torch.optim.AdamW; the optional keys `training.clip_grad_norm`, `training.no_weight_decay` and `training.layer_decay` reach that
+optimizer as its per-parameter settings (`_group_options`) and are refused with any other.  `get_transforms` returns callables with the reference's per-image semantics that also carry the
 GPU multi-crop recipe (`.view_spec`, see `data.ViewSpec.from_config`) or, for the crop / flip / ToTensor and Resize / ToTensor
 lists, the recipe of the fused transform kernel (`.transform_spec`, see `data.TransformSpec.from_config`).
 """
+import fnmatch
 import logging
 import os
 
@@ -21,6 +23,7 @@ from .schedulers import LinearWarmupScheduler
 
 logger = logging.getLogger(__name__)
 _FUSED_ADAMW_KEYS = {"lr", "betas", "eps", "weight_decay"}
+_GROUP_KEYS = ("clip_grad_norm", "no_weight_decay", "layer_decay")
 
 
 def _spec(config, *path):
@@ -152,12 +155,55 @@ def make_criterion(config):
     return getattr(nn, name)(**kwargs)
 
 
+def _group_options(config, store):
+    """The optional keys beside `training.optimizer` as FusedAdamW's keyword arguments ({} when none is present):
+    `clip_grad_norm` (> 0), `no_weight_decay` (true, or a list of fnmatch patterns over parameter names) and
+    `layer_decay` (0 < d <= 1: lr multiplier d ** (L + 1 - layer_id), see vitssl_hip.engine.layer_id).  `store` is the
+    FlatStore whose names they are keyed by, or None when only the presence of the keys is asked for."""
+    present = {key: cfg_get(config, "training", key) for key in _GROUP_KEYS}
+    present = {key: value for key, value in present.items() if value is not None and value is not False}
+    if not present or store is None:
+        return present
+    from vitssl_hip.engine import exempt_from_weight_decay, layer_id, num_layers
+    out = {}
+    if "clip_grad_norm" in present:
+        clip = float(present["clip_grad_norm"])
+        if not clip > 0.0:
+            raise ValueError(f"training.clip_grad_norm = {present['clip_grad_norm']!r} must be a positive number")
+        out["max_grad_norm"] = clip
+    if "no_weight_decay" in present:
+        rule = present["no_weight_decay"]
+        if rule is True:
+            ndim = {name: p.dim() for name, p in zip(store.names, store.params)}
+            exempt = {name for name in store.names if exempt_from_weight_decay(name, ndim[name])}
+        elif isinstance(rule, str) or not hasattr(rule, "__iter__"):
+            raise ValueError(f"training.no_weight_decay = {rule!r} must be true or a list of name patterns")
+        else:
+            patterns = [str(pattern) for pattern in rule]
+            exempt = {name for name in store.names if any(fnmatch.fnmatchcase(name, pattern) for pattern in patterns)}
+        _, kwargs = _spec(config, "training", "optimizer")
+        decay = float(kwargs.get("weight_decay", 1e-2))
+        out["weight_decay_of"] = lambda name: 0.0 if name in exempt else decay
+    if "layer_decay" in present:
+        d = float(present["layer_decay"])
+        if not 0.0 < d <= 1.0:
+            raise ValueError(f"training.layer_decay = {present['layer_decay']!r} must satisfy 0 < d <= 1")
+        layers = num_layers(store.names)
+        out["lr_scale"] = lambda name: d ** (layers + 1 - layer_id(name, layers))
+    return out
+
+
 def make_optimizer(config, model):
     name, kwargs = _spec(config, "training", "optimizer")
     if name == "AdamW" and hasattr(model, "flat_store") and set(kwargs) <= _FUSED_ADAMW_KEYS:
         from vitssl_hip.optim import FusedAdamW
         store = model.trainable_store() if hasattr(model, "trainable_store") else model.flat_store()
-        return FusedAdamW(store, **kwargs)
+        return FusedAdamW(store, **kwargs, **_group_options(config, store))
+    ignored = _group_options(config, None)
+    if ignored:
+        raise ValueError(f"training.{' / training.'.join(sorted(ignored))} need the fused AdamW (optimizer name AdamW with only "
+                         f"{sorted(_FUSED_ADAMW_KEYS)} under params, over a model with a flat store); the optimizer configured here "
+                         f"is {name} with params {sorted(kwargs)}")
     return getattr(optim, name)((p for p in model.parameters() if p.requires_grad), **kwargs)
 
 

@@ -69,6 +69,15 @@ class BaseTrainer(ABC):
         from vitssl_hip.optim import FusedAdamW
         return isinstance(self.optimizer, FusedAdamW) and hasattr(self.model, "train_step")
 
+    def _log_grad_norm(self, epoch, values):
+        """With `training.clip_grad_norm`: log the pre-clip gradient norm of the epoch's last step.  Called once per epoch where
+        the epoch's loss has just been read, so the one-float read adds no wait of its own.  Returns `values` unchanged."""
+        norm = getattr(self.optimizer, "grad_norm", None)
+        if norm is not None:
+            logger.info("epoch %d: grad_norm %.4g before clipping at %g", epoch, float(norm),
+                        self.optimizer.param_groups[0]["max_grad_norm"])
+        return values
+
     def _generic_reduce(self):
         """Reference-style path (loss.backward through autograd): average p.grad across ranks."""
         if self.world == 1:

@@ -122,8 +122,8 @@ class DINOTrainer(BaseTrainer):
             self._warmup_step(epoch)
             running = loss if running is None else running + loss
             total += 1
-        return {**self._last_batch_metrics(outputs), "Loss": float(running) / max(total, 1), "TeacherTemp": self.criterion.teacher_temp,
-                "Momentum": momentum}
+        return self._log_grad_norm(epoch, {**self._last_batch_metrics(outputs), "Loss": float(running) / max(total, 1),
+                                           "TeacherTemp": self.criterion.teacher_temp, "Momentum": momentum})
 
     def validate(self):
         self.model.eval()

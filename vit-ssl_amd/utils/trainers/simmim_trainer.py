@@ -55,7 +55,7 @@ class SimMIMTrainer(BaseTrainer):
             self._warmup_step(epoch)
             running = loss if running is None else running + loss
             total += 1
-        return {**self._metric_values(), "Loss": float(running) / max(total, 1)}
+        return self._log_grad_norm(epoch, {**self._metric_values(), "Loss": float(running) / max(total, 1)})
 
     def validate(self):
         self.model.eval()

@@ -89,7 +89,7 @@ class SupervisedTrainer(BaseTrainer):
             running = loss if running is None else running + loss
             self._fused_update_metrics(labels)
             total += 1
-        return self._epoch_values(running, total, counters)
+        return self._log_grad_norm(epoch, self._epoch_values(running, total, counters))
 
     def _validate_fused(self):
         c = self.criterion
@@ -158,7 +158,8 @@ class SupervisedTrainer(BaseTrainer):
             correct += int((logits.argmax(1) == labels).sum())
             seen += labels.numel()
             total += 1
-        return {**self._metric_values(), "Loss": float(running) / max(total, 1), "Accuracy": correct / max(seen, 1)}
+        return self._log_grad_norm(epoch, {**self._metric_values(), "Loss": float(running) / max(total, 1),
+                                           "Accuracy": correct / max(seen, 1)})
 
     def validate(self):
         self.model.eval()

@@ -13,6 +13,7 @@ METRICS_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include"
 CLASSIFY_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "vitssl_classify.h"))
 ATTENTION_HD_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "vitssl_attention_hd.h"))
 PATCH_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "vitssl_patch.h"))
+OPTIM_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "vitssl_optim.h"))
 
 
 class VitsslError(RuntimeError):
@@ -37,6 +38,11 @@ class Fp8TnJob(C.Structure):
     """vitssl_fp8_tn_job_t"""
     _fields_ = [("A8", C.c_void_p), ("B8", C.c_void_p), ("C", C.c_void_p), ("N1", C.c_int), ("N2", C.c_int),
                 ("alpha", C.c_void_p), ("alpha2", C.c_void_p)]
+
+
+class OptimSegment(C.Structure):
+    """vitssl_optim_segment_t"""
+    _fields_ = [("offset", C.c_int64), ("n", C.c_int64), ("lr_scale", C.c_float), ("weight_decay", C.c_float)]
 
 
 class Gemm(C.Structure):
@@ -146,6 +152,15 @@ PROTOTYPES_PATCH = {
     "vitssl_cast_transpose_batch_ld": [_vp, _vp, _i, _i, _vp],
 }
 
+# include/vitssl_optim.h (segmented AdamW: per-parameter lr / weight decay, global-norm clipping): the launching entry points
+# and the host-side table builder; the sizing functions vitssl_optim_table_bytes / vitssl_grad_sumsq_workspace_bytes (return a
+# count) are bound in lib() beside the other sizing functions.
+PROTOTYPES_OPTIM = {
+    "vitssl_optim_table_build": [C.POINTER(OptimSegment), _i, _i64, _vp, _i64],
+    "vitssl_grad_sumsq": [_vp, _vp, _i, _vp, _vp, _i64, _vp],
+    "vitssl_adamw_segments": [_vp, _vp, _vp, _vp, _vp, _i, _f, _f, _f, _f, _i, _f, _vp, _f, _vp],
+}
+
 _lib = None
 
 
@@ -187,6 +202,13 @@ def attention_hd_header_symbols():
 def patch_header_symbols():
     """Entry points declared in include/vitssl_patch.h."""
     with open(PATCH_HEADER_PATH) as f:
+        txt = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)        # the comments name functions of vitssl_hip.h
+    return sorted(set(re.findall(r"\b(vitssl_[a-z0-9_]+)\s*\(", txt)))
+
+
+def optim_header_symbols():
+    """Entry points and sizing functions declared in include/vitssl_optim.h."""
+    with open(OPTIM_HEADER_PATH) as f:
         txt = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)        # the comments name functions of vitssl_hip.h
     return sorted(set(re.findall(r"\b(vitssl_[a-z0-9_]+)\s*\(", txt)))
 
@@ -238,8 +260,12 @@ def lib():
     l.vitssl_dino_stats_workspace_floats.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
     l.vitssl_classify_loss_workspace_floats.restype = C.c_int64
     l.vitssl_classify_loss_workspace_floats.argtypes = [C.c_int, C.c_int]
+    for sizing in ("vitssl_optim_table_bytes", "vitssl_grad_sumsq_workspace_bytes"):
+        getattr(l, sizing).restype = C.c_int64
+        getattr(l, sizing).argtypes = [C.c_int]
     for name, args in (list(PROTOTYPES.items()) + list(PROTOTYPES_TRANSFORMS.items()) + list(PROTOTYPES_METRICS.items())
-                       + list(PROTOTYPES_CLASSIFY.items()) + list(PROTOTYPES_ATTENTION_HD.items()) + list(PROTOTYPES_PATCH.items())):
+                       + list(PROTOTYPES_CLASSIFY.items()) + list(PROTOTYPES_ATTENTION_HD.items()) + list(PROTOTYPES_PATCH.items())
+                       + list(PROTOTYPES_OPTIM.items())):
         fn = getattr(l, name)  # AttributeError if the symbol is missing
         fn.restype = C.c_int
         fn.argtypes = args

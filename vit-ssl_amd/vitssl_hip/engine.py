@@ -15,6 +15,7 @@ Design (MI355X-first, not a translation of the reference's eager module graph):
 """
 from __future__ import annotations
 
+import re
 from typing import Callable, Dict, List, Optional, Tuple
 
 import torch
@@ -110,6 +111,37 @@ class Workspace:
 
     def clear(self):
         self._bufs.clear()
+
+
+# ---- parameter names of the stores: what the optimizer's per-parameter settings are keyed by -------------------------------------
+# A store keeps the module tree's names: `encoder_blocks.<i>.` inside a backbone (ViT / SimMIMViT directly, DINOViT under
+# `student_backbone.` / `teacher_backbone.`), the embedding as `patch_embedding.*` (ViT, DINOViT) or `projection.*`,
+# `positional_embedding`, `mask_token` (SimMIMViT); everything else is a head.
+_BLOCK_NAME = re.compile(r"(?:^|\.)encoder_blocks\.(\d+)\.")
+_TOKEN_NAMES = ("cls_token", "positional_embedding", "mask_token")
+
+
+def num_layers(names) -> int:
+    """Number of encoder blocks among the parameter names of a store."""
+    ids = [int(m.group(1)) for m in map(_BLOCK_NAME.search, names) if m]
+    return max(ids) + 1 if ids else 0
+
+
+def layer_id(name: str, layers: int) -> int:
+    """Depth of a parameter for layer-wise lr decay: 0 for the patch embedding / projection, the tokens and the positional table,
+    i + 1 for `encoder_blocks.i`, layers + 1 for everything else (the heads)."""
+    m = _BLOCK_NAME.search(name)
+    if m:
+        return int(m.group(1)) + 1
+    parts = name.split(".")
+    if "patch_embedding" in parts or parts[0] == "projection" or parts[-1] in _TOKEN_NAMES:
+        return 0
+    return layers + 1
+
+
+def exempt_from_weight_decay(name: str, ndim: int) -> bool:
+    """The ViT recipes' rule: biases and norm parameters (ndim <= 1), the tokens and the positional table are not decayed."""
+    return ndim <= 1 or name.split(".")[-1] in _TOKEN_NAMES
 
 
 class FlatStore:

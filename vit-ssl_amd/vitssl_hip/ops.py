@@ -648,6 +648,53 @@ def adamw(p, g, m, v, lr, beta1, beta2, eps, wd, step, gscale=1.0):
     _prof_end(ev, "adamw", 0.0, 28 * n)                          # p, m, v read + written, g read
 
 
+class AdamWPlan:
+    """Device-resident segment table of `vitssl_adamw_segments` / `vitssl_grad_sumsq` (include/vitssl_optim.h) over a flat
+    store of `numel` floats, with the workspace of the norm and its one-float result slot.  `segments`: (offset, n, lr_scale,
+    weight_decay) per parameter that takes part, in ascending order; checked on the host by the library when the plan is
+    built (offsets multiples of 4 floats, no overlap, inside the store).  Built once and kept until the set of parameters changes."""
+
+    def __init__(self, segments, numel, device):
+        segments = [(int(o), int(n), float(s), float(w)) for o, n, s, w in segments]
+        l = L.lib()
+        self.nseg, self.numel = len(segments), int(numel)
+        nbytes = int(l.vitssl_optim_table_bytes(self.nseg))
+        host = torch.zeros(max(nbytes, 8), dtype=torch.uint8)
+        arr = (L.OptimSegment * max(self.nseg, 1))(*[L.OptimSegment(*s) for s in segments])
+        call("vitssl_optim_table_build", arr, self.nseg, self.numel, C.c_void_p(host.data_ptr()), nbytes)
+        self.elements = sum(s[1] for s in segments)
+        self.table = host.to(device)
+        self.workspace = torch.empty(int(l.vitssl_grad_sumsq_workspace_bytes(self.nseg)), dtype=torch.uint8, device=device)
+        self.sumsq = torch.zeros(1, dtype=F32, device=device)
+
+
+def _flat(t, name, plan):
+    if t.dim() != 1 or t.numel() != plan.numel:
+        raise L.VitsslError(f"{name}: expected the flat buffer of {plan.numel} floats the plan was built for, got {tuple(t.shape)}")
+    return _chk(t, F32, name)
+
+
+def grad_sumsq(g, plan, out=None, workspace=None):
+    """out[0] (default: plan.sumsq) = sum of g^2 over the plan's segments; deterministic, no host synchronisation."""
+    out = plan.sumsq if out is None else out
+    ws = plan.workspace if workspace is None else workspace
+    ev = _prof_begin()
+    call("vitssl_grad_sumsq", _flat(g, "g", plan), _chk(plan.table, torch.uint8, "table"), plan.nseg, _chk(out, F32, "out", (1,)),
+         _chk(ws, torch.uint8, "workspace"), ws.numel(), _stream())
+    _prof_end(ev, "grad_sumsq", 0.0, 4 * plan.elements)
+    return out
+
+
+def adamw_segments(p, g, m, v, plan, lr, beta1, beta2, eps, step, gscale=1.0, sumsq=None, max_norm=0.0):
+    """One launch of AdamW over the plan's segments (lr * lr_scale and the weight decay of each).  With `sumsq` (the result
+    of grad_sumsq) the gradient is scaled by min(1, max_norm / (gscale * sqrt(sumsq) + 1e-6)) on the device; g is not written."""
+    ev = _prof_begin()
+    call("vitssl_adamw_segments", _flat(p, "p", plan), _flat(g, "g", plan), _flat(m, "m", plan), _flat(v, "v", plan),
+         _chk(plan.table, torch.uint8, "table"), plan.nseg, float(lr), float(beta1), float(beta2), float(eps), int(step), float(gscale),
+         _opt(sumsq, F32, "sumsq", (1,)), float(max_norm), _stream())
+    _prof_end(ev, "adamw_segments", 0.0, 28 * plan.elements)
+
+
 def ema(teacher, student, m):
     ev = _prof_begin()
     call("vitssl_ema", _chk(teacher, F32, "teacher"), _chk(student, F32, "student", teacher.shape), teacher.numel(), float(m), _stream())

@@ -17,12 +17,34 @@ class FusedAdamW(torch.optim.Optimizer):
       tensors are first copied into the flat buffer; parameters whose .grad is None are
       skipped, as torch.optim.AdamW does.
     param_groups[0]['lr'] is honoured, so the reference's warm-up / cosine schedulers
-    (utils/schedulers.py, torch.optim.lr_scheduler) drive it unchanged."""
+    (utils/schedulers.py, torch.optim.lr_scheduler) drive it unchanged.
 
-    def __init__(self, store: FlatStore, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+    Opt-in, keyword only (with all three None every call is what it was):
+    * `max_grad_norm` -- clip the global norm of the averaged gradient (torch.nn.utils.clip_grad_norm_'s formula), computed
+      and applied on the device with no host read; `grad_norm` then holds the pre-clip norm of the last step as a 1-element
+      device tensor (reading it is the caller's synchronisation).  The flat gradient buffer keeps the UNCLIPPED gradient.
+    * `lr_scale(name)` -- multiplier of the group's lr for that parameter (layer-wise lr decay);
+    * `weight_decay_of(name)` -- that parameter's weight decay (default: the group's).
+    param_groups stays ONE group: the multipliers live in the device-resident segment table (ops.AdamWPlan), built once per
+    set of parameters that take part, and a step is grad_sumsq (only when clipping) + adamw_segments, also over a store with
+    frozen parameters."""
+
+    def __init__(self, store: FlatStore, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, *, max_grad_norm=None,
+                 lr_scale=None, weight_decay_of=None):
         params = [p for p in store.params if p.requires_grad]
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        if max_grad_norm is not None:
+            if not float(max_grad_norm) > 0.0:
+                raise ValueError(f"max_grad_norm = {max_grad_norm!r} must be positive")
+            defaults["max_grad_norm"] = float(max_grad_norm)
         super().__init__(params, defaults)
+        self.lr_scale, self.weight_decay_of = lr_scale, weight_decay_of
+        self._trainable_names = tuple(n for n, p in zip(store.names, store.params) if p.requires_grad)
+        self._index = {n: i for i, n in enumerate(store.names)}
+        self._last_plan = None
+        self._plans = {}            # (names that take part, group weight decay) -> ops.AdamWPlan
+        self._sumsq = None          # sum of squares of the last clipped step's gradient (device) and its gscale
+        self._norm_gscale = 1.0
         self.store = store
         self.exp_avg = torch.zeros_like(store.flat)
         self.exp_avg_sq = torch.zeros_like(store.flat)
@@ -33,8 +55,60 @@ class FusedAdamW(torch.optim.Optimizer):
         g = self.param_groups[0]
         return float(g["lr"]), g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"]
 
+    @property
+    def max_grad_norm(self):
+        """The clip's bound, or None: lives in the group dict, so it follows state_dict() / load_state_dict()."""
+        return self.param_groups[0].get("max_grad_norm")
+
+    @property
+    def _segmented(self):
+        """True when any per-parameter setting or the clip is on (read from the group: a loaded checkpoint may switch the clip on)."""
+        return self.lr_scale is not None or self.weight_decay_of is not None or self.max_grad_norm is not None
+
+    @property
+    def grad_norm(self):
+        """Pre-clip global norm of the averaged gradient of the last step: a 1-element device tensor (None before the first
+        step and without max_grad_norm)."""
+        return None if self._sumsq is None else self._sumsq.sqrt() * self._norm_gscale
+
+    def _plan(self, names):
+        wd = self.param_groups[0]["weight_decay"]
+        last = self._last_plan              # the usual step: the same tuple object and decay as the step before, no hashing
+        if last is not None and last[0] is names and last[1] == wd:
+            return last[2]
+        key = (names, float(wd))
+        plan = self._plans.get(key)
+        if plan is None:
+            st = self.store
+            scale = self.lr_scale or (lambda name: 1.0)
+            decay = self.weight_decay_of or (lambda name: wd)
+            plan = ops.AdamWPlan([(*st.offsets[n], scale(n), decay(n)) for n in names], st.numel, st.flat.device)
+            if len(self._plans) >= 8:          # the set changes when a backbone is unfrozen, not every step
+                self._plans.clear()
+            self._plans[key] = plan
+        self._last_plan = (names, wd, plan)
+        return plan
+
+    def _step_segments(self, names, gscale):
+        """grad_sumsq (when clipping) + adamw_segments over the parameters `names` of the store"""
+        lr, b1, b2, eps, _ = self._hyper()
+        self.step_count += 1
+        st = self.store
+        if names:
+            plan = self._plan(names)
+            sumsq, max_norm = None, 0.0
+            if self.max_grad_norm is not None:
+                max_norm = float(self.max_grad_norm)
+                sumsq = self._sumsq = ops.grad_sumsq(st.gflat, plan)
+                self._norm_gscale = float(gscale)
+            ops.adamw_segments(st.flat, st.gflat, self.exp_avg, self.exp_avg_sq, plan, lr, b1, b2, eps, self.step_count, gscale,
+                               sumsq, max_norm)
+        st.mark_dirty()
+
     @torch.no_grad()
     def step_flat(self, gscale: float = 1.0):
+        if self._segmented:
+            return self._step_segments(self._trainable_names, gscale)      # the optimizer's parameters: fixed when it was built
         if not self._all_trainable:
             # frozen parameters in the store: per-parameter launches over the trainable slices.
             # The fused step leaves its gradients in store.gflat only (p.grad stays None).
@@ -53,6 +127,22 @@ class FusedAdamW(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        if self._segmented:
+            st = self.store
+            names, missing = self._trainable_names, False
+            if not from_flat:
+                for name in names:
+                    p = st.params[self._index[name]]
+                    if p.grad is None:
+                        missing = True
+                        continue
+                    gslice = st.gview(name)
+                    if p.grad.data_ptr() != gslice.data_ptr():
+                        gslice.copy_(p.grad.reshape(-1))
+                if missing:             # a table of its own for the parameters that have a gradient
+                    names = tuple(n for n in names if st.params[self._index[n]].grad is not None)
+            self._step_segments(names, gscale)
+            return loss
         lr, b1, b2, eps, wd = self._hyper()
         self.step_count += 1
         st = self.store
