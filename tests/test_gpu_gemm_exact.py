@@ -268,7 +268,11 @@ def test_nt_exact_splitk(ops, L, M, N, K):
         assert _same_bits(outs[0], outs[1])
 
 
-# ----------------------------------------------------------------------------- TN, bf16 operands
+# ----------------------------------------------------------------------------- TN, bf16 and e4m3 operands
+def _scalar(v):
+    return None if v is None else torch.tensor([v], device=DEV)
+
+
 def _tn_twice(run, C0, prod, what):
     Cd = C0.to(DEV)
     run(Cd)
@@ -278,64 +282,104 @@ def _tn_twice(run, C0, prod, what):
     return Cd
 
 
-@pytest.mark.parametrize("M,N1,N2,G,mode", [
-    (1, 264, 8, None, "direct"), (63, 264, 8, None, "direct"), (64, 8, 264, None, "direct"),      # one chunk of 64 rows: one split
-    (65, 264, 8, None, "slab"),                                  # two chunks, the second of one row
-    (3000, 264, 520, None, "slab"),                              # 6 tiles, 47 chunks in 24 splits of 2: the last split and the last chunk ragged
-    (300, 520, 776, 8, "direct"),                                # 12 tiles on 8 CUs: one owner per tile walks all 5 chunks
-    (1000, 264, 8, 8, "slab"),                                   # 2 tiles on 8 CUs: 4 splits of 4 chunks
-], ids=lambda v: str(v))
-def test_tn_exact(ops, L, usable, M, N1, N2, G, mode):
-    A, B, C0 = X.operands_tn(M, N1, N2, seed=M + N1)
+def _tn_id(kind, rest):
+    """the bf16 cases keep the ids they had before the e4m3 cases joined them"""
+    return ("" if kind == "bf16" else kind + "-") + rest
+
+
+TN_CASES = [                                                     # kind, M, N1, N2, usable CUs, mode
+    ("bf16", 1, 264, 8, None, "direct"), ("bf16", 63, 264, 8, None, "direct"), ("bf16", 64, 8, 264, None, "direct"),      # one chunk of 64 rows: one split
+    ("bf16", 65, 264, 8, None, "slab"),                          # two chunks, the second of one row
+    ("bf16", 3000, 264, 520, None, "slab"),                      # 6 tiles, 47 chunks in 24 splits of 2: the last split and the last chunk ragged
+    ("bf16", 300, 520, 776, 8, "direct"),                        # 12 tiles on 8 CUs: one owner per tile walks all 5 chunks
+    ("bf16", 1000, 264, 8, 8, "slab"),                           # 2 tiles on 8 CUs: 4 splits of 4 chunks
+    # e4m3: chunks of 128 rows, widths multiples of 16
+    ("e4m3", 100, 272, 16, None, "direct"), ("e4m3", 127, 272, 16, None, "direct"), ("e4m3", 128, 16, 272, None, "direct"),    # one chunk
+    ("e4m3", 129, 272, 16, None, "slab"),                        # two splits, the second of one row
+    ("e4m3", 1000, 272, 16, None, "slab"),                       # 2 tiles, 8 splits of one chunk, the last ragged
+    ("e4m3", 3000, 272, 528, None, "slab"),                      # 6 tiles, 24 splits of one chunk
+    ("e4m3", 600, 528, 784, 8, "direct"),                        # 12 tiles on 8 CUs: one owner per tile walks all 5 chunks
+    ("e4m3", 2000, 272, 16, 8, "slab"),                          # 2 tiles on 8 CUs: 4 splits of 4 chunks
+]
+
+
+@pytest.mark.parametrize("kind,M,N1,N2,G,mode", TN_CASES, ids=[_tn_id(c[0], "-".join(str(v) for v in c[1:])) for c in TN_CASES])
+def test_tn_exact(ops, L, usable, kind, M, N1, N2, G, mode):
+    """first and second (accumulating) call, two independent runs with the same bits, and the atomic mode; e4m3 operands once with
+    alpha x alpha2 = 0.25 x 8 (the factor 2 is part of the exactness bound of operands_tn) and once without scalars"""
+    fp8 = kind == "e4m3"
+    A, B, C0 = X.operands_tn(M, N1, N2, seed=M + (N2 if fp8 else N1), scale=2.0 if fp8 else 1.0)
     prod = X.ref_tn(A, B)
-    Ad, Bd = A.to(DEV), B.to(DEV)
+    Ad, Bd = (X.to_fp8(A).to(DEV), X.to_fp8(B).to(DEV)) if fp8 else (A.to(DEV), B.to(DEV))
     G = usable(G)
-    _, splits, _ = X.tn_plan(M, N1, N2, G)
+    _, splits, _ = X.tn_plan(M, N1, N2, G, km=128 if fp8 else 64)
     assert (splits == 1) == (mode == "direct"), (splits, mode)
-    assert L.lib().vitssl_gemm_tn_workspace_floats(M, N1, N2) == splits * N1 * N2
-    c_a = _tn_twice(lambda Cd: ops.gemm_tn(Ad, Bd, Cd), C0, prod, f"gemm_tn {mode}")
-    c_b = _tn_twice(lambda Cd: ops.gemm_tn(Ad, Bd, Cd), C0, prod, f"gemm_tn {mode}, again")
-    assert _same_bits(c_a, c_b)
-    _tn_twice(lambda Cd: ops.gemm_tn(Ad, Bd, Cd, atomic=True), C0, prod, "gemm_tn atomic")
+    query = L.lib().vitssl_gemm_fp8_tn_workspace_floats if fp8 else L.lib().vitssl_gemm_tn_workspace_floats
+    assert query(M, N1, N2) == splits * N1 * N2
+    gemm, name = (ops.gemm_fp8_tn, "gemm_fp8_tn") if fp8 else (ops.gemm_tn, "gemm_tn")
+    variants = [(", alpha 0.25 x 8", 2.0, dict(alpha=_scalar(0.25), alpha2=_scalar(8.0))), (", no scalars", 1.0, {})] if fp8 else [("", 1.0, {})]
+    for tag, s, kw in variants:
+        c_a = _tn_twice(lambda Cd: gemm(Ad, Bd, Cd, **kw), C0, s * prod, f"{name} {mode}{tag}")
+        c_b = _tn_twice(lambda Cd: gemm(Ad, Bd, Cd, **kw), C0, s * prod, f"{name} {mode}{tag}, again")
+        assert _same_bits(c_a, c_b)
+        _tn_twice(lambda Cd: gemm(Ad, Bd, Cd, atomic=True, **kw), C0, s * prod, f"{name} atomic{tag}")
 
 
 JOBS8 = [(264, 520), (8, 264), (512, 264), (256, 8), (8, 8), (264, 8), (72, 136), (16, 520)]     # 6 + 2 + 4 + 1 | + 1 + 2 + 1 + 3 tiles
 JOBS11 = [(264, 520), (512, 264), (256, 8)]                                                        # 6 + 4 + 1 tiles
+_W16 = {264: 272, 8: 16, 520: 528, 72: 80, 136: 144}                                               # the same lists in multiples of 16 (e4m3)
+JOBS8_16 = [(_W16.get(a, a), _W16.get(b, b)) for a, b in JOBS8]
+JOBS11_16 = [(_W16.get(a, a), _W16.get(b, b)) for a, b in JOBS11]
+FP8_SCALES = [(0.25, 8.0), (None, None), (2.0, None), (None, 0.5)]                                 # (alpha, alpha2) of job j % 4: |product| <= 2
+
+TN_BATCH_CASES = [                                 # kind, M, dims, usable CUs, plan, id
+    ("bf16", 300, JOBS8[4:5], None, "splits", "1job"),                      # one job, one tile, 5 chunks in 5 splits
+    ("bf16", 1700, JOBS8[:4], None, "splits", "4jobs"),                     # four jobs, 13 tiles, ragged last chunk
+    ("bf16", 1700, JOBS8, None, "splits", "8jobs"),                         # eight jobs, 20 tiles
+    ("bf16", 1700, JOBS8[:4], 8, "owners", "4jobs-G8-owners"),              # 13 tiles on 8 CUs: single owners, two rounds, workspace requirement 0
+    ("bf16", 1700, JOBS8[:4], 24, "helpers", "4jobs-G24-helpers"),          # 13 tiles on 24 CUs: one split of 22 chunks, the last 5 chunks of every tile by 11 helpers
+    ("bf16", 3100, JOBS11, 32, "helpers", "3jobs-G32-helpers"),             # 11 tiles on 32 CUs: two splits of 22 chunks + 5 chunks by 10 helpers
+    # e4m3 (chunks of 128 rows): the same plans at twice the rows
+    ("e4m3", 600, JOBS8_16[4:5], None, "splits", "1job"),                   # 5 splits of one chunk
+    ("e4m3", 1700, JOBS8_16[:4], None, "splits", "4jobs-1700"),             # 14 chunks in 3 splits of 5, the last split and chunk ragged
+    ("e4m3", 3400, JOBS8_16[:4], None, "splits", "4jobs"),                  # 4 splits of 7 chunks
+    ("e4m3", 3400, JOBS8_16[:4], 8, "owners", "4jobs-G8-owners"),           # single owners of 27 chunks, workspace requirement 0
+    ("e4m3", 3400, JOBS8_16[:4], 24, "helpers", "4jobs-G24-helpers"),       # one split of 22 chunks + 5 chunks by helpers
+    ("e4m3", 6200, JOBS11_16, 32, "helpers", "3jobs-G32-helpers"),          # two splits of 22 chunks + 5 chunks by helpers
+]
 
 
-@pytest.mark.parametrize("M,dims,G,plan", [
-    (300, JOBS8[4:5], None, "splits"),        # one job, one tile, 5 chunks in 5 splits
-    (1700, JOBS8[:4], None, "splits"),        # four jobs, 13 tiles, ragged last chunk
-    (1700, JOBS8, None, "splits"),            # eight jobs, 20 tiles
-    (1700, JOBS8[:4], 8, "owners"),           # 13 tiles on 8 CUs: single owners, two rounds, workspace requirement 0
-    (1700, JOBS8[:4], 24, "helpers"),         # 13 tiles on 24 CUs: one split of 22 chunks, the last 5 chunks of every tile by 11 helpers
-    (3100, JOBS11, 32, "helpers"),            # 11 tiles on 32 CUs: two splits of 22 chunks + 5 chunks by 10 helpers
-], ids=["1job", "4jobs", "8jobs", "4jobs-G8-owners", "4jobs-G24-helpers", "3jobs-G32-helpers"])
-def test_tn_exact_batch(ops, L, usable, M, dims, G, plan):
+@pytest.mark.parametrize("kind,M,dims,G,plan", [c[:5] for c in TN_BATCH_CASES], ids=[_tn_id(c[0], c[5]) for c in TN_BATCH_CASES])
+def test_tn_exact_batch(ops, L, usable, kind, M, dims, G, plan):
+    fp8 = kind == "e4m3"
     G = usable(G)
-    ops_in = [X.operands_tn(M, N1, N2, seed=M + 7 * j) for j, (N1, N2) in enumerate(dims)]
-    prods = [X.ref_tn(A, B) for A, B, _ in ops_in]
+    ops_in = [X.operands_tn(M, N1, N2, seed=M + (5 if fp8 else 7) * j, scale=2.0 if fp8 else 1.0) for j, (N1, N2) in enumerate(dims)]
+    scales = [FP8_SCALES[j % 4] if fp8 else (None, None) for j in range(len(dims))]
+    prods = [(a or 1.0) * (a2 or 1.0) * X.ref_tn(A, B) for (A, B, _), (a, a2) in zip(ops_in, scales)]
     T = sum(math.ceil(N1 / 256) * math.ceil(N2 / 256) for N1, N2 in dims)
-    knobs = dict(forced=_knob("VITSSL_TN_BATCH_SPLITS"), use_rem=os.environ.get("VITSSL_TN_BATCH_REM", "1") != "0")
+    knobs = dict(forced=_knob("VITSSL_TN_BATCH_SPLITS"), use_rem=os.environ.get("VITSSL_TN_BATCH_REM", "1") != "0", km=128 if fp8 else 64)
     S, cps, rem = X.tn_batch_plan(M, T, G, **knobs)
     if not knobs["forced"] and knobs["use_rem"]:                 # the plan the case id names (the knob child forces another one)
         assert {"splits": S > 1 and rem == 0, "owners": S == 1 and rem == 0, "helpers": rem > 0}[plan], (S, cps, rem)
-    jobs = [(A.to(DEV), B.to(DEV), C0.to(DEV)) for A, B, C0 in ops_in]
-    arr = (L.TnJob * len(jobs))()
-    for j, (A, B, Cd) in enumerate(jobs):
-        arr[j].A, arr[j].B, arr[j].C, arr[j].N1, arr[j].N2 = A.data_ptr(), B.data_ptr(), Cd.data_ptr(), A.shape[1], B.shape[1]
-    assert L.lib().vitssl_gemm_tn_batch_workspace_floats(arr, len(jobs), M) == X.tn_batch_workspace(M, T, G, **knobs)
+    if fp8:
+        jobs = [(X.to_fp8(A).to(DEV), X.to_fp8(B).to(DEV), C0.to(DEV), _scalar(a), _scalar(a2)) for (A, B, C0), (a, a2) in zip(ops_in, scales)]
+        arr, batch, query = (L.Fp8TnJob * len(jobs))(), ops.gemm_fp8_tn_batch, L.lib().vitssl_gemm_fp8_tn_batch_workspace_floats
+    else:
+        jobs = [(A.to(DEV), B.to(DEV), C0.to(DEV)) for A, B, C0 in ops_in]
+        arr, batch, query = (L.TnJob * len(jobs))(), ops.gemm_tn_batch, L.lib().vitssl_gemm_tn_batch_workspace_floats
+    for j, job in enumerate(jobs):
+        A, B, Cd = job[:3]
+        ptrs = dict(A8=A.data_ptr(), B8=B.data_ptr()) if fp8 else dict(A=A.data_ptr(), B=B.data_ptr())
+        for field, v in dict(ptrs, C=Cd.data_ptr(), N1=A.shape[1], N2=B.shape[1]).items():
+            setattr(arr[j], field, v)
+    assert query(arr, len(jobs), M) == X.tn_batch_workspace(M, T, G, **knobs)
     for call in (1, 2):
-        ops.gemm_tn_batch(jobs)
-        for j, ((_, _, C0), prod, (_, _, Cd)) in enumerate(zip(ops_in, prods, jobs)):
-            X.check_exact(Cd, X.to_f32_exact(C0.double() + call * prod), f"gemm_tn_batch {plan}: job {j} {dims[j]}, call {call}")
+        batch(jobs)
+        for j, ((_, _, C0), prod, job) in enumerate(zip(ops_in, prods, jobs)):
+            X.check_exact(job[2], X.to_f32_exact(C0.double() + call * prod), f"{batch.__name__} {plan}: job {j} {dims[j]}, call {call}")
 
 
 # ----------------------------------------------------------------------------- fp8 operands (always the ping-pong kernel)
-def _scalar(v):
-    return torch.tensor([v], device=DEV)
-
-
 @pytest.mark.parametrize("regime,M,N,K", [("small", 300, 264, 128), ("round", 1000, 520, 256)], ids=["small-300x264x128", "round-1000x520x256"])
 def test_fp8_exact_nt(ops, L, regime, M, N, K):
     s = 2.0                                                      # alpha x alpha2
@@ -382,30 +426,6 @@ def test_fp8_exact_nt_dgelu_image(ops, L, regime, M, N, K):
         cs = cs0.to(DEV)
         ops.gemm_fp8_nt(X.to_fp8(A).to(DEV), X.to_fp8(B).to(DEV), out, L.EPI_DGELU, alpha=_scalar(2.0), alpha2=_scalar(0.25), aux=aux.to(DEV), colsum=cs)
         X.check_exact(cs, X.to_f32_exact(cs0.double() + want.double().sum(0)), "fp8 EPI_DGELU column sums")
-
-
-@pytest.mark.parametrize("M,N1,N2,mode", [(100, 272, 16, "direct"), (1000, 272, 16, "slab"), (3000, 272, 528, "slab")], ids=lambda v: str(v))
-def test_fp8_exact_tn(ops, L, cus, M, N1, N2, mode):
-    s = 2.0
-    A, B, C0 = X.operands_tn(M, N1, N2, seed=M + N2, scale=s)
-    _, splits, _ = X.tn_plan(M, N1, N2, cus - L.lib().vitssl_get_reserved_cus(), km=128)
-    assert (splits == 1) == (mode == "direct")
-    A8, B8 = X.to_fp8(A).to(DEV), X.to_fp8(B).to(DEV)
-    _tn_twice(lambda Cd: ops.gemm_fp8_tn(A8, B8, Cd, alpha=_scalar(0.25), alpha2=_scalar(8.0)), C0, s * X.ref_tn(A, B), f"gemm_fp8_tn {mode}")
-    _tn_twice(lambda Cd: ops.gemm_fp8_tn(A8, B8, Cd), C0, X.ref_tn(A, B), f"gemm_fp8_tn {mode}, no scalars")
-
-
-def test_fp8_exact_tn_batch(ops, L):
-    M, dims = 1700, [(272, 528), (16, 272), (512, 272), (256, 16)]
-    scales = [(0.25, 8.0), (None, None), (2.0, None), (None, 0.5)]
-    ops_in = [X.operands_tn(M, N1, N2, seed=M + 5 * j, scale=2.0) for j, (N1, N2) in enumerate(dims)]
-    jobs = [(X.to_fp8(A).to(DEV), X.to_fp8(B).to(DEV), C0.to(DEV), None if a is None else _scalar(a), None if a2 is None else _scalar(a2))
-            for (A, B, C0), (a, a2) in zip(ops_in, scales)]
-    for call in (1, 2):
-        ops.gemm_fp8_tn_batch(jobs)
-        for j, ((A, B, C0), (a, a2), job) in enumerate(zip(ops_in, scales, jobs)):
-            want = C0.double() + call * (a or 1.0) * (a2 or 1.0) * X.ref_tn(A, B)
-            X.check_exact(job[2], X.to_f32_exact(want), f"gemm_fp8_tn_batch: job {j} {dims[j]}, call {call}")
 
 
 # ----------------------------------------------------------------------------- deterministic sums beside the GEMMs

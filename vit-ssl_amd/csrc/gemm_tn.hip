@@ -16,6 +16,7 @@
 // rate; they remain as the fallback when no workspace is given).  Rows past M are
 // zero-filled by the buffer descriptor's bounds check, so ragged M needs no tail code.
 #include <stdlib.h>
+#include <type_traits>
 #include "common.h"
 
 #ifdef VITSSL_TN_STAMPS
@@ -28,21 +29,33 @@ extern "C" int vitssl_debug_set_tn_stamps(unsigned long long* p) {
 namespace {
 
 constexpr int TN_T = 256;          // output tile edge
-constexpr int TN_KM = 64;          // contraction rows per stage
+constexpr int TN_KM = 64;          // contraction rows per stage, bf16 operands
+constexpr int TN8_KM = 128;        // ... e4m3 operands (the same 32 KiB per operand tile)
 constexpr int TN_THREADS = 512;
 constexpr int TN_TILE_BYTES = TN_KM * TN_T * 2;   // 32 KiB
 constexpr int TN_LDS_BYTES = 4 * TN_TILE_BYTES;   // 128 KiB
 
+// Everything around the two K loops (tn_pp_unit: bf16, tn8_pp_unit: e4m3) is written once and takes the operand kind as a traits
+// type F (TnBf16 / TnFp8, below the loops): K-tile rows, element bytes, column multiple, entry names, the unit function, the
+// barrier between two units of a batch.
+// An operand pointer of either kind: each K loop reads it as its own element type.
+struct TnPtr {
+  const void* p;
+  __host__ __device__ operator const bf16_t*() const { return (const bf16_t*)p; }
+  __host__ __device__ operator const unsigned char*() const { return (const unsigned char*)p; }
+};
+
 struct TnParams {
-  const bf16_t* A;
-  const bf16_t* B;
+  TnPtr A, B;
   float* C;
   long long M;
   int N1, N2;
   int tiles1, tiles2, splits;
-  int chunks_per_split;   // in units of TN_KM rows
+  int chunks_per_split;   // in units of F::KM rows
   float* slabs;           // [splits][N1][N2] fp32 or nullptr (atomic mode, or direct mode)
   int direct;             // splits == 1: every C tile has exactly one owner, which adds its result into C itself (no slab, no reduce pass)
+  const float* alpha;     // e4m3 only: device scalars multiplied into the result (dequantisation of the two operands), or NULL
+  const float* alpha2;
 };
 
 __device__ __forceinline__ int tn_f(int row) { return (row & 3) | (((row >> 3) & 1) << 2); }
@@ -65,10 +78,9 @@ typedef __attribute__((ext_vector_type(8))) short tn_s16x8;
 // fragments into a second register set in the shadow of its own MFMAs (inline-asm MFMAs interleaved 1:1 with the 24 reads + DMA,
 // one barrier per phase, 230 VGPRs): correct, but 5-8 % SLOWER than this loop on the four ViT-B shapes -- with nothing else to run
 // at the phase's wait + barrier the matrix pipe drains twice per K-tile.
-// One unit of work of the ping-pong loop: the K-tiles [ch_begin, ch_begin + nk) of the output tile at (c1, c2).
+// One unit of work of a ping-pong loop: the K-tiles [ch_begin, ch_begin + nk) (of F::KM rows) of the output tile at (c1, c2).
 struct TnUnit {
-  const bf16_t* A;
-  const bf16_t* B;
+  TnPtr A, B;
   long long M;
   int N1, N2;
   int c1, c2;
@@ -76,7 +88,9 @@ struct TnUnit {
   int nk;
   float* dst;      // mode 0 / 1 / 2: the [N1, N2] matrix (a split's slab, or C); mode 3: a compact 256 x 256 slot
   int mode;        // 0 store into a slab, 1 add into C (sole owner of the tile), 2 atomic add into C, 3 store the whole tile into a slot
-  int stamp_wg;    // diagnostic build: workgroup index of the stamp record, or -1
+  const float* alpha;    // read by the e4m3 loop only
+  const float* alpha2;
+  int stamp_wg;    // read by the diagnostic bf16 build only: workgroup index of the stamp record, or -1
 };
 
 __device__ __forceinline__ void tn_pp_unit(const TnUnit& p, char* smem) {
@@ -291,35 +305,7 @@ __device__ __forceinline__ void tn_pp_unit(const TnUnit& p, char* smem) {
   }
 }
 
-__global__ __launch_bounds__(TN_THREADS, 2) void gemm_tn_pp_kernel(TnParams p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  // block -> (split, tile): the tiles of one split, which share the split's rows of both operands, are neighbours on one XCD
-  const int ntiles = p.tiles1 * p.tiles2;
-  const int bid = xcd_remap(blockIdx.x, ntiles * p.splits);
-  const int split = bid / ntiles;
-  const int tile = bid - split * ntiles;
-  const int t1 = tile / p.tiles2, t2 = tile - t1 * p.tiles2;
-  const long long total_chunks = (p.M + TN_KM - 1) / TN_KM;
-  const long long ch_begin = (long long)split * p.chunks_per_split;
-  long long ch_end = ch_begin + p.chunks_per_split;
-  if (ch_end > total_chunks) ch_end = total_chunks;
-  TnUnit u;
-  u.A = p.A;
-  u.B = p.B;
-  u.M = p.M;
-  u.N1 = p.N1;
-  u.N2 = p.N2;
-  u.c1 = t1 * TN_T;
-  u.c2 = t2 * TN_T;
-  u.ch_begin = ch_begin;
-  u.nk = ch_begin < ch_end ? (int)(ch_end - ch_begin) : 0;   // empty split: writes a zero slab
-  u.dst = p.slabs ? p.slabs + (long long)split * p.N1 * p.N2 : p.C;
-  u.mode = p.slabs ? 0 : (p.direct ? 1 : 2);
-  u.stamp_wg = (int)blockIdx.x;
-  tn_pp_unit(u, smem);
-}
-
-// ---- several weight gradients over the same rows in ONE launch (vitssl_gemm_bf16_tn_batch).
+// ---- several weight gradients over the same rows in ONE launch (vitssl_gemm_bf16_tn_batch, vitssl_gemm_fp8_tn_batch).
 // Why: a launch of the kernel above is one round of the CUs, splits = CUs / tiles, and writes CUs x 256 KiB of partial tiles that
 // tn_reduce_kernel reads back -- 66 MB each way whatever the shape, ~25 us per launch, for the four gradients of a transformer
 // block four times.  Here the tiles of all jobs form one list, unit u = split * T + tile (split-major: the workgroups running at the
@@ -327,8 +313,8 @@ __global__ __launch_bounds__(TN_THREADS, 2) void gemm_tn_pp_kernel(TnParams p) {
 // chosen for the whole list (tn_batch_plan), so fewer, longer units, one launch and one reduce.
 constexpr int TN_MAX_JOBS = 8;
 struct TnBatchParams {
-  const bf16_t* A[TN_MAX_JOBS];
-  const bf16_t* B[TN_MAX_JOBS];
+  const void* A[TN_MAX_JOBS];    // bf16 or e4m3 images
+  const void* B[TN_MAX_JOBS];
   float* C[TN_MAX_JOBS];
   int N1[TN_MAX_JOBS], N2[TN_MAX_JOBS];
   int tiles2[TN_MAX_JOBS];
@@ -347,7 +333,9 @@ struct TnBatchParams {
 struct TnBatchWalk {
   int first, step, end;          // unit indices first, first + step, ... < end
 };
-__device__ __forceinline__ TnBatchWalk tn_batch_walk(const TnBatchParams& p, int bid, int G) {
+__device__ __forceinline__ TnBatchWalk tn_batch_walk(const TnBatchParams& p) {
+  const int G = gridDim.x;
+  const int bid = xcd_remap(blockIdx.x, G);
   const int T = p.tile0[p.njobs];
   const int mainu = T * p.splits;
   TnBatchWalk w;
@@ -388,26 +376,21 @@ __device__ __forceinline__ void tn_batch_unit(const TnBatchParams& p, int un, in
   nk = ch_begin < ch_end ? (int)(ch_end - ch_begin) : 0;
 }
 
-__global__ __launch_bounds__(TN_THREADS, 2) void gemm_tn_batch_kernel(TnBatchParams p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int G = gridDim.x;
-  const int bid = xcd_remap(blockIdx.x, G);
-  const TnBatchWalk w = tn_batch_walk(p, bid, G);
-  for (int un = w.first; un < w.end; un += w.step) {
-    TnUnit u;
-    int j;
-    tn_batch_unit(p, un, TN_KM, j, u.c1, u.c2, u.ch_begin, u.nk);
-    u.A = p.A[j];
-    u.B = p.B[j];
-    u.M = p.M;
-    u.N1 = p.N1[j];
-    u.N2 = p.N2[j];
-    u.dst = p.slots ? p.slots + (long long)un * (TN_T * TN_T) : p.C[j];
-    u.mode = p.slots ? 3 : 1;
-    u.stamp_wg = -1;
-    tn_pp_unit(u, smem);
-    raw_barrier();                                      // every wave is done with the LDS before the next unit's first DMA
-  }
+// the e4m3 batch adds its per-job scalars (composed, so that the bf16 batch kernel's arguments stay as small as they are)
+struct Tn8BatchParams {
+  TnBatchParams b;               // A / B hold the e4m3 images
+  const float* alpha[TN_MAX_JOBS];
+  const float* alpha2[TN_MAX_JOBS];
+};
+template <class P>
+__host__ __device__ __forceinline__ auto& tn_base(P& pp) {       // the part both kinds share, of const or mutable parameters
+  if constexpr (std::is_same_v<std::remove_const_t<P>, Tn8BatchParams>) return pp.b;
+  else return pp;
+}
+__device__ __forceinline__ void tn_job_scalars(const TnBatchParams&, int, TnUnit& u) { u.alpha = u.alpha2 = nullptr; }
+__device__ __forceinline__ void tn_job_scalars(const Tn8BatchParams& p, int j, TnUnit& u) {
+  u.alpha = p.alpha[j];
+  u.alpha2 = p.alpha2[j];
 }
 
 // C_j[tile] += sum over splits of the tile's slots; one block = 32 rows of one tile
@@ -453,37 +436,7 @@ __global__ __launch_bounds__(256) void tn_batch_reduce_kernel(TnBatchParams p) {
 // reads: the two lane groups of a half-wave then touch 16 rows x 16 B in 16 distinct chunk positions (conflict-free).
 // (Round 3's form of the loop, plain double buffering with all 8 waves in step, was 19-21 % slower than the ping-pong loop
 // below and is gone; DESIGN.md section 10a keeps the numbers.)
-struct Tn8Params {
-  const unsigned char* A;
-  const unsigned char* B;
-  float* C;
-  long long M;
-  int N1, N2;
-  int tiles1, tiles2, splits;
-  int chunks_per_split;   // in units of TN8_KM rows
-  float* slabs;
-  int direct;             // as TnParams::direct
-  const float* alpha;     // device scalars multiplied into the result (dequantisation of the two operands), or NULL
-  const float* alpha2;
-};
-constexpr int TN8_KM = 128;
-
 __device__ __forceinline__ int tn8_f(int row) { return (row & 7) | (((row >> 5) & 1) << 3); }
-
-// One unit of work of the e4m3 weight-gradient loop (as TnUnit; K-tiles of TN8_KM rows)
-struct Tn8Unit {
-  const unsigned char* A;
-  const unsigned char* B;
-  long long M;
-  int N1, N2;
-  int c1, c2;
-  long long ch_begin;
-  int nk;
-  float* dst;
-  int mode;               // 0 slab, 1 add into C, 2 atomic add into C, 3 compact 256 x 256 slot
-  const float* alpha;
-  const float* alpha2;
-};
 
 // ---- ping-pong form of the e4m3 weight-gradient loop (round 4) ----------------------------------------------------------------
 // Same roles as tn_pp_unit: waves 4-7 (the n1 half w1 = 1 of the tile) run one barrier behind waves 0-3, so on every SIMD one wave is
@@ -505,7 +458,7 @@ struct Tn8Unit {
 // it after that barrier.  K-tiles past the unit's range get an empty buffer window (zero fill, no traffic), so counts stay uniform.
 __device__ __forceinline__ int tn8_fa(int row) { return ((row >> 1) & 3) | (((row >> 5) & 1) << 2); }
 
-__device__ __forceinline__ void tn8_pp_unit(const Tn8Unit& p, char* smem) {
+__device__ __forceinline__ void tn8_pp_unit(const TnUnit& p, char* smem) {
   constexpr int AG = TN8_KM * 128;                     // 16 KiB: one A_g region
   constexpr int BT = TN8_KM * 256;                     // 32 KiB: the B tile
   constexpr int B_BASE = 4 * AG;
@@ -673,19 +626,43 @@ __device__ __forceinline__ void tn8_pp_unit(const Tn8Unit& p, char* smem) {
   }
 }
 
-__global__ __launch_bounds__(TN_THREADS, 2) void gemm_tn_fp8_kernel(Tn8Params p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  // block -> (split, tile): the tiles of one split, which share the split's rows of both operands, are neighbours on one XCD
+// ====================================================================================
+// The two operand kinds.  What is not listed here is the same for both.
+struct TnBf16 {
+  using BatchParams = TnBatchParams;
+  static constexpr int KM = TN_KM, ESZ = 2, COLS = 8;                 // K-tile rows, element bytes, N1 / N2 are multiples of COLS
+  static constexpr const char *NAME = "gemm_tn", *REDUCE = "gemm_tn_reduce", *BATCH = "gemm_tn_batch", *BATCH_REDUCE = "gemm_tn_batch_reduce";
+  static __device__ __forceinline__ void unit(const TnUnit& u, char* smem) { tn_pp_unit(u, smem); }
+  // every wave is done with the LDS before the next unit's first DMA.  (The two kinds differ here by history; nobody has measured it.)
+  static __device__ __forceinline__ void hand_over() { raw_barrier(); }
+};
+struct TnFp8 {
+  using BatchParams = Tn8BatchParams;
+  static constexpr int KM = TN8_KM, ESZ = 1, COLS = 16;
+  static constexpr const char *NAME = "gemm_fp8_tn", *REDUCE = "gemm_fp8_tn_reduce", *BATCH = "gemm_fp8_tn_batch",
+                              *BATCH_REDUCE = "gemm_fp8_tn_batch_reduce";
+  static __device__ __forceinline__ void unit(const TnUnit& u, char* smem) { tn8_pp_unit(u, smem); }
+  static __device__ __forceinline__ void hand_over() { __syncthreads(); }
+};
+
+// The wrappers below are shaped by one constraint: the four kernels must compile to the instruction streams they had as two
+// hand-written copies each (profiles/tn_one_path_isa.txt).  hipcc keeps them only if the single-launch body takes its parameters
+// by value and the batch kernels keep their unit loop themselves; the shared tile store of an earlier draft moved registers in
+// all four K loops, so the store epilogues of tn_pp_unit and tn8_pp_unit stay two copies (they differ in `* al`).
+// single launch: block -> (split, tile) -> unit
+template <class F>
+__device__ __forceinline__ void tn_single_body(TnParams p, char* smem) {
+  // the tiles of one split, which share the split's rows of both operands, are neighbours on one XCD
   const int ntiles = p.tiles1 * p.tiles2;
   const int bid = xcd_remap(blockIdx.x, ntiles * p.splits);
   const int split = bid / ntiles;
   const int tile = bid - split * ntiles;
   const int t1 = tile / p.tiles2, t2 = tile - t1 * p.tiles2;
-  const long long total_chunks = (p.M + TN8_KM - 1) / TN8_KM;
+  const long long total_chunks = (p.M + F::KM - 1) / F::KM;
   const long long ch_begin = (long long)split * p.chunks_per_split;
   long long ch_end = ch_begin + p.chunks_per_split;
   if (ch_end > total_chunks) ch_end = total_chunks;
-  Tn8Unit u;
+  TnUnit u;
   u.A = p.A;
   u.B = p.B;
   u.M = p.M;
@@ -699,38 +676,47 @@ __global__ __launch_bounds__(TN_THREADS, 2) void gemm_tn_fp8_kernel(Tn8Params p)
   u.mode = p.slabs ? 0 : (p.direct ? 1 : 2);
   u.alpha = p.alpha;
   u.alpha2 = p.alpha2;
-  tn8_pp_unit(u, smem);
+  u.stamp_wg = (int)blockIdx.x;
+  F::unit(u, smem);
 }
 
-// several e4m3 weight gradients over the same rows in one launch (vitssl_gemm_fp8_tn_batch; see gemm_tn_batch_kernel)
-struct Tn8BatchParams {
-  TnBatchParams b;               // A / B hold the e4m3 images
-  const float* alpha[TN_MAX_JOBS];
-  const float* alpha2[TN_MAX_JOBS];
-};
+// batch: unit un of the list; then the LDS is handed to the next unit
+template <class F>
+__device__ __forceinline__ void tn_batch_step(const typename F::BatchParams& pp, int un, char* smem) {
+  const TnBatchParams& p = tn_base(pp);
+  TnUnit u;
+  int j;
+  tn_batch_unit(p, un, F::KM, j, u.c1, u.c2, u.ch_begin, u.nk);
+  u.A = {p.A[j]};
+  u.B = {p.B[j]};
+  u.M = p.M;
+  u.N1 = p.N1[j];
+  u.N2 = p.N2[j];
+  u.dst = p.slots ? p.slots + (long long)un * (TN_T * TN_T) : p.C[j];
+  u.mode = p.slots ? 3 : 1;
+  tn_job_scalars(pp, j, u);
+  u.stamp_wg = -1;
+  F::unit(u, smem);
+  F::hand_over();
+}
 
-__global__ __launch_bounds__(TN_THREADS, 2) void gemm_tn_fp8_batch_kernel(Tn8BatchParams pp) {
+__global__ __launch_bounds__(TN_THREADS, 2) void gemm_tn_pp_kernel(TnParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const TnBatchParams& p = pp.b;
-  const int G = gridDim.x;
-  const int bid = xcd_remap(blockIdx.x, G);
-  const TnBatchWalk w = tn_batch_walk(p, bid, G);
-  for (int un = w.first; un < w.end; un += w.step) {
-    Tn8Unit u;
-    int j;
-    tn_batch_unit(p, un, TN8_KM, j, u.c1, u.c2, u.ch_begin, u.nk);
-    u.A = (const unsigned char*)p.A[j];
-    u.B = (const unsigned char*)p.B[j];
-    u.M = p.M;
-    u.N1 = p.N1[j];
-    u.N2 = p.N2[j];
-    u.dst = p.slots ? p.slots + (long long)un * (TN_T * TN_T) : p.C[j];
-    u.mode = p.slots ? 3 : 1;
-    u.alpha = pp.alpha[j];
-    u.alpha2 = pp.alpha2[j];
-    tn8_pp_unit(u, smem);
-    __syncthreads();                                   // every wave is done with the LDS before the next unit's first DMA
-  }
+  tn_single_body<TnBf16>(p, smem);
+}
+__global__ __launch_bounds__(TN_THREADS, 2) void gemm_tn_fp8_kernel(TnParams p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  tn_single_body<TnFp8>(p, smem);
+}
+__global__ __launch_bounds__(TN_THREADS, 2) void gemm_tn_batch_kernel(TnBatchParams p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const TnBatchWalk w = tn_batch_walk(tn_base(p));
+  for (int un = w.first; un < w.end; un += w.step) tn_batch_step<TnBf16>(p, un, smem);
+}
+__global__ __launch_bounds__(TN_THREADS, 2) void gemm_tn_fp8_batch_kernel(Tn8BatchParams p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const TnBatchWalk w = tn_batch_walk(tn_base(p));
+  for (int un = w.first; un < w.end; un += w.step) tn_batch_step<TnFp8>(p, un, smem);
 }
 
 // C[e] += sum_s slabs[s][e]
@@ -764,49 +750,7 @@ void tn_plan(long long M, int N1, int N2, int* tiles1, int* tiles2, int* splits,
   *splits = (int)((total_chunks + *chunks_per_split - 1) / *chunks_per_split);
 }
 
-}  // namespace
-
-extern "C" int64_t vitssl_gemm_tn_workspace_floats(int64_t M, int N1, int N2) {
-  if (M <= 0 || N1 <= 0 || N2 <= 0) return 0;
-  int t1, t2, sp, cps;
-  tn_plan(M, N1, N2, &t1, &t2, &sp, &cps);
-  return (int64_t)sp * N1 * N2;
-}
-
-extern "C" int vitssl_gemm_bf16_tn(const void* A, const void* B, float* C, int64_t M, int N1, int N2, float* workspace,
-                                   int64_t workspace_floats, void* stream) {
-  VS_CHECK_ARG(A && B && C, "gemm_tn: null operand");
-  VS_CHECK_ARG(M > 0 && N1 > 0 && N2 > 0, "gemm_tn: empty problem");
-  VS_CHECK_ARG(N1 % 8 == 0 && N2 % 8 == 0, "gemm_tn: N1=%d N2=%d must be multiples of 8", N1, N2);
-  VS_CHECK_ARG((unsigned long long)M * N1 * 2ull < (1ull << 31) && (unsigned long long)M * N2 * 2ull < (1ull << 31),
-               "gemm_tn: operand larger than 2 GiB");
-  TnParams p;
-  p.A = (const bf16_t*)A;
-  p.B = (const bf16_t*)B;
-  p.C = C;
-  p.M = M;
-  p.N1 = N1;
-  p.N2 = N2;
-  tn_plan(M, N1, N2, &p.tiles1, &p.tiles2, &p.splits, &p.chunks_per_split);
-  const long long need = (long long)p.splits * N1 * N2;
-  p.slabs = (workspace && workspace_floats >= need) ? workspace : nullptr;
-  VS_CHECK_ARG(!workspace || p.slabs, "gemm_tn: workspace too small (%lld < %lld floats, vitssl_gemm_tn_workspace_floats)", (long long)workspace_floats,
-               need);
-  // One split (more C tiles than CUs: the DINO head's [65536, 768] weight gradient): the slab would be written, read back and
-  // added to C by a second kernel -- 3 x 201 MB for nothing, since every tile has a single owner (tn_reduce was 1.6 ms of a
-  // DINO step, 114 us per such call).  The owner adds into C itself.
-  p.direct = p.splits == 1;
-  if (p.direct) p.slabs = nullptr;
-  static VsOnce attr_done{false};
-  if (int rc = ensure_lds(gemm_tn_pp_kernel, TN_LDS_BYTES, attr_done, "gemm_tn")) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(gemm_tn_pp_kernel, dim3(p.tiles1 * p.tiles2 * p.splits), dim3(TN_THREADS), TN_LDS_BYTES, s, p);
-  VS_CHECK_LAUNCH("gemm_tn");
-  return p.slabs ? tn_reduce_slabs(C, p.slabs, N1, N2, p.splits, s, "gemm_tn_reduce") : VITSSL_OK;
-}
-
 // ---- batch of weight gradients over the same M rows
-namespace {
 // Split count for a list of T tiles: minimises (rounds of the CUs) x (K-tiles per unit x 1.46 us + 9 us per unit: pipeline fill,
 // hand-over, slot store) plus the partial-tile traffic (0.15 us per 256 KiB partial written and read back).  The two constants are
 // fitted to whole-step measurements with forced split counts (VITSSL_TN_BATCH_SPLITS): ViT-B (108 tiles) 2 splits 33.27 ms,
@@ -865,177 +809,161 @@ void tn_batch_plan(long long M, int T, int G, int* splits, int* chunks_per_split
     }
   }
 }
-int tn_batch_tiles(const vitssl_tn_job_t* jobs, int njobs, TnBatchParams* p) {
+long long tn_batch_need(int splits, int rem_chunks, int T) {   // floats of partial-tile slots (none when every tile has one owner)
+  return (splits > 1 || rem_chunks > 0) ? (long long)(splits + (rem_chunks > 0)) * T * TN_T * TN_T : 0;
+}
+
+// job list -> batch parameters, unused entries zeroed; returns the tile count T.  The two job structs differ in the names of
+// the operand pointers and in the scalars, which these overloads bridge (q == nullptr: an unused entry).
+void tn_fill_operands(TnBatchParams& p, int j, const vitssl_tn_job_t* q) {
+  p.A[j] = q ? q->A : nullptr;
+  p.B[j] = q ? q->B : nullptr;
+}
+void tn_fill_operands(Tn8BatchParams& p, int j, const vitssl_fp8_tn_job_t* q) {
+  p.b.A[j] = q ? q->A8 : nullptr;
+  p.b.B[j] = q ? q->B8 : nullptr;
+  p.alpha[j] = q ? q->alpha : nullptr;
+  p.alpha2[j] = q ? q->alpha2 : nullptr;
+}
+template <class Params, class Job>
+int tn_batch_fill(const Job* jobs, int njobs, Params* pp) {
+  TnBatchParams& p = tn_base(*pp);
   int t = 0;
-  for (int j = 0; j < njobs; ++j) {
-    p->tile0[j] = t;
-    p->tiles2[j] = (jobs[j].N2 + TN_T - 1) / TN_T;
-    t += ((jobs[j].N1 + TN_T - 1) / TN_T) * p->tiles2[j];
+  for (int j = 0; j < TN_MAX_JOBS; ++j) {
+    const Job* q = j < njobs ? jobs + j : nullptr;
+    tn_fill_operands(*pp, j, q);
+    p.C[j] = q ? q->C : nullptr;
+    p.N1[j] = q ? q->N1 : 0;
+    p.N2[j] = q ? q->N2 : 0;
+    p.tile0[j] = t;
+    p.tiles2[j] = q ? (q->N2 + TN_T - 1) / TN_T : 0;
+    if (q) t += ((q->N1 + TN_T - 1) / TN_T) * p.tiles2[j];
   }
-  p->tile0[njobs] = t;
+  p.tile0[TN_MAX_JOBS] = t;
+  p.njobs = njobs;
   return t;
 }
-}  // namespace
 
-extern "C" int64_t vitssl_gemm_tn_batch_workspace_floats(const vitssl_tn_job_t* jobs, int njobs, int64_t M) {
-  if (!jobs || njobs <= 0 || njobs > TN_MAX_JOBS || M <= 0) return 0;
-  TnBatchParams p;
-  const int T = tn_batch_tiles(jobs, njobs, &p);
-  int sp, cps, rem;
-  tn_batch_plan(M, T, vitssl_persistent_cus(), &sp, &cps, &rem);
-  return (sp > 1 || rem > 0) ? (int64_t)(sp + (rem > 0)) * T * TN_T * TN_T : 0;
-}
-
-extern "C" int vitssl_gemm_bf16_tn_batch(const vitssl_tn_job_t* jobs, int njobs, int64_t M, float* workspace, int64_t workspace_floats,
-                                         void* stream) {
-  VS_CHECK_ARG(jobs && njobs > 0 && njobs <= TN_MAX_JOBS, "gemm_tn_batch: 1..%d jobs", TN_MAX_JOBS);
-  VS_CHECK_ARG(M > 0, "gemm_tn_batch: empty problem");
-  TnBatchParams p;
-  for (int j = 0; j < njobs; ++j) {
-    const vitssl_tn_job_t& q = jobs[j];
-    VS_CHECK_ARG(q.A && q.B && q.C, "gemm_tn_batch: job %d: null operand", j);
-    VS_CHECK_ARG(q.N1 > 0 && q.N2 > 0 && q.N1 % 8 == 0 && q.N2 % 8 == 0, "gemm_tn_batch: job %d: N1=%d N2=%d must be positive multiples of 8", j,
-                 q.N1, q.N2);
-    VS_CHECK_ARG((unsigned long long)M * q.N1 * 2ull < (1ull << 31) && (unsigned long long)M * q.N2 * 2ull < (1ull << 31),
-                 "gemm_tn_batch: job %d: operand larger than 2 GiB", j);
-    p.A[j] = (const bf16_t*)q.A;
-    p.B[j] = (const bf16_t*)q.B;
-    p.C[j] = q.C;
-    p.N1[j] = q.N1;
-    p.N2[j] = q.N2;
-  }
-  for (int j = njobs; j < TN_MAX_JOBS; ++j) {
-    p.A[j] = p.B[j] = nullptr;
-    p.C[j] = nullptr;
-    p.N1[j] = p.N2[j] = p.tiles2[j] = 0;
-  }
-  const int T = tn_batch_tiles(jobs, njobs, &p);
-  for (int j = njobs + 1; j <= TN_MAX_JOBS; ++j) p.tile0[j] = T;
-  p.njobs = njobs;
-  p.M = M;
-  const long long cus = vitssl_persistent_cus();               // once per launch: plan, workspace check and grid use this value
-  tn_batch_plan(M, T, (int)cus, &p.splits, &p.chunks_per_split, &p.rem_chunks);
-  const long long need = (p.splits > 1 || p.rem_chunks > 0) ? (long long)(p.splits + (p.rem_chunks > 0)) * T * TN_T * TN_T : 0;
-  VS_CHECK_ARG(need == 0 || (workspace && workspace_floats >= need), "gemm_tn_batch: workspace of %lld floats needed with %lld CUs available (vitssl_gemm_tn_batch_workspace_floats; the answer\n"
-               "changes with vitssl_set_reserved_cus: query again after changing the reserve)", need, cus);
-  p.slots = need ? workspace : nullptr;
-  static VsOnce attr_done{false};
-  if (int rc = ensure_lds(gemm_tn_batch_kernel, TN_LDS_BYTES, attr_done, "gemm_tn_batch")) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  const long long units = (long long)T * p.splits;
-  const unsigned grid = (unsigned)((units < cus && p.rem_chunks == 0) ? units : cus);      // (with a remainder range every CU has work)
-  hipLaunchKernelGGL(gemm_tn_batch_kernel, dim3(grid), dim3(TN_THREADS), TN_LDS_BYTES, s, p);
-  VS_CHECK_LAUNCH("gemm_tn_batch");
-  if (p.slots) {
-    hipLaunchKernelGGL(tn_batch_reduce_kernel, dim3((unsigned)T * 8u), dim3(256), 0, s, p);
-    VS_CHECK_LAUNCH("gemm_tn_batch_reduce");
-  }
+// the operands of a single launch (job < 0) or of job `job` of a batch, whose entry has checked M
+template <class F>
+int tn_check_operands(const void* A, const void* B, const float* C, long long M, int N1, int N2, int job) {
+  char who[48];
+  if (job < 0) snprintf(who, sizeof who, "%s", F::NAME);
+  else snprintf(who, sizeof who, "%s: job %d", F::BATCH, job);
+  VS_CHECK_ARG(A && B && C, "%s: null operand", who);
+  VS_CHECK_ARG(job >= 0 || (M > 0 && N1 > 0 && N2 > 0), "%s: empty problem", who);
+  VS_CHECK_ARG(N1 > 0 && N2 > 0 && N1 % F::COLS == 0 && N2 % F::COLS == 0, "%s: N1=%d N2=%d must be %smultiples of %d", who, N1, N2,
+               job < 0 ? "" : "positive ", F::COLS);
+  VS_CHECK_ARG((unsigned long long)M * N1 * F::ESZ < (1ull << 31) && (unsigned long long)M * N2 * F::ESZ < (1ull << 31),
+               "%s: operand larger than 2 GiB", who);
   return VITSSL_OK;
 }
 
-extern "C" int64_t vitssl_gemm_fp8_tn_workspace_floats(int64_t M, int N1, int N2) {
+template <class F>
+int64_t tn_single_workspace(int64_t M, int N1, int N2) {
   if (M <= 0 || N1 <= 0 || N2 <= 0) return 0;
   int t1, t2, sp, cps;
-  tn_plan(M, N1, N2, &t1, &t2, &sp, &cps, TN8_KM);
+  tn_plan(M, N1, N2, &t1, &t2, &sp, &cps, F::KM);
   return (int64_t)sp * N1 * N2;
 }
 
-extern "C" int vitssl_gemm_fp8_tn(const void* A8, const void* B8, float* C, int64_t M, int N1, int N2, const float* alpha,
-                                  const float* alpha2, float* workspace, int64_t workspace_floats, void* stream) {
-  VS_CHECK_ARG(A8 && B8 && C, "gemm_fp8_tn: null operand");
-  VS_CHECK_ARG(M > 0 && N1 > 0 && N2 > 0, "gemm_fp8_tn: empty problem");
-  VS_CHECK_ARG(N1 % 16 == 0 && N2 % 16 == 0, "gemm_fp8_tn: N1=%d N2=%d must be multiples of 16", N1, N2);
-  VS_CHECK_ARG((unsigned long long)M * N1 < (1ull << 31) && (unsigned long long)M * N2 < (1ull << 31),
-               "gemm_fp8_tn: operand larger than 2 GiB");
-  Tn8Params p;
-  p.A = (const unsigned char*)A8;
-  p.B = (const unsigned char*)B8;
+template <class F, void (*KERNEL)(TnParams)>
+int tn_launch_single(const void* A, const void* B, float* C, int64_t M, int N1, int N2, const float* alpha, const float* alpha2,
+                     float* workspace, int64_t workspace_floats, void* stream) {
+  if (int rc = tn_check_operands<F>(A, B, C, M, N1, N2, -1)) return rc;
+  TnParams p;
+  p.A = {A};
+  p.B = {B};
   p.C = C;
   p.M = M;
   p.N1 = N1;
   p.N2 = N2;
   p.alpha = alpha;
   p.alpha2 = alpha2;
-  tn_plan(M, N1, N2, &p.tiles1, &p.tiles2, &p.splits, &p.chunks_per_split, TN8_KM);
+  tn_plan(M, N1, N2, &p.tiles1, &p.tiles2, &p.splits, &p.chunks_per_split, F::KM);
   const long long need = (long long)p.splits * N1 * N2;
   p.slabs = (workspace && workspace_floats >= need) ? workspace : nullptr;
-  VS_CHECK_ARG(!workspace || p.slabs, "gemm_fp8_tn: workspace too small (%lld < %lld floats, vitssl_gemm_fp8_tn_workspace_floats)",
-               (long long)workspace_floats, need);
+  VS_CHECK_ARG(!workspace || p.slabs, "%s: workspace too small (%lld < %lld floats, vitssl_%s_workspace_floats)", F::NAME,
+               (long long)workspace_floats, need, F::NAME);
+  // One split (more C tiles than CUs: the DINO head's [65536, 768] weight gradient): the slab would be written, read back and
+  // added to C by a second kernel -- 3 x 201 MB for nothing, since every tile has a single owner (tn_reduce was 1.6 ms of a
+  // DINO step, 114 us per such call).  The owner adds into C itself.
   p.direct = p.splits == 1;
   if (p.direct) p.slabs = nullptr;
   static VsOnce attr_done{false};
-  if (int rc = ensure_lds(gemm_tn_fp8_kernel, TN_LDS_BYTES, attr_done, "gemm_fp8_tn")) return rc;
+  if (int rc = ensure_lds(KERNEL, TN_LDS_BYTES, attr_done, F::NAME)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(gemm_tn_fp8_kernel, dim3(p.tiles1 * p.tiles2 * p.splits), dim3(TN_THREADS), TN_LDS_BYTES, s, p);
-  VS_CHECK_LAUNCH("gemm_fp8_tn");
-  return p.slabs ? tn_reduce_slabs(C, p.slabs, N1, N2, p.splits, s, "gemm_fp8_tn_reduce") : VITSSL_OK;
+  hipLaunchKernelGGL(KERNEL, dim3(p.tiles1 * p.tiles2 * p.splits), dim3(TN_THREADS), TN_LDS_BYTES, s, p);
+  VS_CHECK_LAUNCH(F::NAME);
+  return p.slabs ? tn_reduce_slabs(C, p.slabs, N1, N2, p.splits, s, F::REDUCE) : VITSSL_OK;
 }
 
-namespace {
-int tn8_batch_fill(const vitssl_fp8_tn_job_t* jobs, int njobs, Tn8BatchParams* pp) {
-  TnBatchParams& p = pp->b;
-  int t = 0;
-  for (int j = 0; j < TN_MAX_JOBS; ++j) {
-    const bool live = j < njobs;
-    p.A[j] = live ? (const bf16_t*)jobs[j].A8 : nullptr;
-    p.B[j] = live ? (const bf16_t*)jobs[j].B8 : nullptr;
-    p.C[j] = live ? jobs[j].C : nullptr;
-    p.N1[j] = live ? jobs[j].N1 : 0;
-    p.N2[j] = live ? jobs[j].N2 : 0;
-    pp->alpha[j] = live ? jobs[j].alpha : nullptr;
-    pp->alpha2[j] = live ? jobs[j].alpha2 : nullptr;
-    p.tile0[j] = t;
-    p.tiles2[j] = live ? (jobs[j].N2 + TN_T - 1) / TN_T : 0;
-    if (live) t += ((jobs[j].N1 + TN_T - 1) / TN_T) * p.tiles2[j];
-  }
-  p.tile0[TN_MAX_JOBS] = t;
-  for (int j = njobs; j <= TN_MAX_JOBS; ++j) p.tile0[j] = t;
-  p.njobs = njobs;
-  return t;
-}
-}  // namespace
-
-extern "C" int64_t vitssl_gemm_fp8_tn_batch_workspace_floats(const vitssl_fp8_tn_job_t* jobs, int njobs, int64_t M) {
+template <class F, class Job>
+int64_t tn_batch_workspace(const Job* jobs, int njobs, int64_t M) {
   if (!jobs || njobs <= 0 || njobs > TN_MAX_JOBS || M <= 0) return 0;
-  Tn8BatchParams pp;
-  const int T = tn8_batch_fill(jobs, njobs, &pp);
+  typename F::BatchParams pp;
+  const int T = tn_batch_fill(jobs, njobs, &pp);
   int sp, cps, rem;
-  tn_batch_plan(M, T, vitssl_persistent_cus(), &sp, &cps, &rem, TN8_KM);
-  return (sp > 1 || rem > 0) ? (int64_t)(sp + (rem > 0)) * T * TN_T * TN_T : 0;
+  tn_batch_plan(M, T, vitssl_persistent_cus(), &sp, &cps, &rem, F::KM);
+  return tn_batch_need(sp, rem, T);
 }
 
-extern "C" int vitssl_gemm_fp8_tn_batch(const vitssl_fp8_tn_job_t* jobs, int njobs, int64_t M, float* workspace, int64_t workspace_floats,
-                                        void* stream) {
-  VS_CHECK_ARG(jobs && njobs > 0 && njobs <= TN_MAX_JOBS, "gemm_fp8_tn_batch: 1..%d jobs", TN_MAX_JOBS);
-  VS_CHECK_ARG(M > 0, "gemm_fp8_tn_batch: empty problem");
-  for (int j = 0; j < njobs; ++j) {
-    const vitssl_fp8_tn_job_t& q = jobs[j];
-    VS_CHECK_ARG(q.A8 && q.B8 && q.C, "gemm_fp8_tn_batch: job %d: null operand", j);
-    VS_CHECK_ARG(q.N1 > 0 && q.N2 > 0 && q.N1 % 16 == 0 && q.N2 % 16 == 0, "gemm_fp8_tn_batch: job %d: N1=%d N2=%d must be positive multiples of 16",
-                 j, q.N1, q.N2);
-    VS_CHECK_ARG((unsigned long long)M * q.N1 < (1ull << 31) && (unsigned long long)M * q.N2 < (1ull << 31),
-                 "gemm_fp8_tn_batch: job %d: operand larger than 2 GiB", j);
-  }
-  Tn8BatchParams pp;
-  TnBatchParams& p = pp.b;
-  const int T = tn8_batch_fill(jobs, njobs, &pp);
+template <class F, void (*KERNEL)(typename F::BatchParams), class Job>
+int tn_launch_batch(const Job* jobs, int njobs, int64_t M, float* workspace, int64_t workspace_floats, void* stream) {
+  VS_CHECK_ARG(jobs && njobs > 0 && njobs <= TN_MAX_JOBS, "%s: 1..%d jobs", F::BATCH, TN_MAX_JOBS);
+  VS_CHECK_ARG(M > 0, "%s: empty problem", F::BATCH);
+  typename F::BatchParams pp;
+  TnBatchParams& p = tn_base(pp);
+  const int T = tn_batch_fill(jobs, njobs, &pp);
+  for (int j = 0; j < njobs; ++j)
+    if (int rc = tn_check_operands<F>(p.A[j], p.B[j], p.C[j], M, p.N1[j], p.N2[j], j)) return rc;
   p.M = M;
   const long long cus = vitssl_persistent_cus();               // once per launch: plan, workspace check and grid use this value
-  tn_batch_plan(M, T, (int)cus, &p.splits, &p.chunks_per_split, &p.rem_chunks, TN8_KM);
-  const long long need = (p.splits > 1 || p.rem_chunks > 0) ? (long long)(p.splits + (p.rem_chunks > 0)) * T * TN_T * TN_T : 0;
-  VS_CHECK_ARG(need == 0 || (workspace && workspace_floats >= need),
-               "gemm_fp8_tn_batch: workspace of %lld floats needed (vitssl_gemm_fp8_tn_batch_workspace_floats)", need);
+  tn_batch_plan(M, T, (int)cus, &p.splits, &p.chunks_per_split, &p.rem_chunks, F::KM);
+  const long long need = tn_batch_need(p.splits, p.rem_chunks, T);
+  VS_CHECK_ARG(need == 0 || (workspace && workspace_floats >= need), "%s: workspace of %lld floats needed with %lld CUs available (vitssl_%s_workspace_floats; the answer\n"
+               "changes with vitssl_set_reserved_cus: query again after changing the reserve)", F::BATCH, need, cus, F::BATCH);
   p.slots = need ? workspace : nullptr;
   static VsOnce attr_done{false};
-  if (int rc = ensure_lds(gemm_tn_fp8_batch_kernel, TN_LDS_BYTES, attr_done, "gemm_fp8_tn_batch")) return rc;
+  if (int rc = ensure_lds(KERNEL, TN_LDS_BYTES, attr_done, F::BATCH)) return rc;
   hipStream_t s = (hipStream_t)stream;
   const long long units = (long long)T * p.splits;
-  const unsigned grid = (unsigned)((units < cus && p.rem_chunks == 0) ? units : cus);
-  hipLaunchKernelGGL(gemm_tn_fp8_batch_kernel, dim3(grid), dim3(TN_THREADS), TN_LDS_BYTES, s, pp);
-  VS_CHECK_LAUNCH("gemm_fp8_tn_batch");
+  const unsigned grid = (unsigned)((units < cus && p.rem_chunks == 0) ? units : cus);      // (with a remainder range every CU has work)
+  hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(TN_THREADS), TN_LDS_BYTES, s, pp);
+  VS_CHECK_LAUNCH(F::BATCH);
   if (p.slots) {
     hipLaunchKernelGGL(tn_batch_reduce_kernel, dim3((unsigned)T * 8u), dim3(256), 0, s, p);
-    VS_CHECK_LAUNCH("gemm_fp8_tn_batch_reduce");
+    VS_CHECK_LAUNCH(F::BATCH_REDUCE);
   }
   return VITSSL_OK;
+}
+
+}  // namespace
+
+extern "C" int64_t vitssl_gemm_tn_workspace_floats(int64_t M, int N1, int N2) { return tn_single_workspace<TnBf16>(M, N1, N2); }
+extern "C" int64_t vitssl_gemm_fp8_tn_workspace_floats(int64_t M, int N1, int N2) { return tn_single_workspace<TnFp8>(M, N1, N2); }
+
+extern "C" int vitssl_gemm_bf16_tn(const void* A, const void* B, float* C, int64_t M, int N1, int N2, float* workspace,
+                                   int64_t workspace_floats, void* stream) {
+  return tn_launch_single<TnBf16, gemm_tn_pp_kernel>(A, B, C, M, N1, N2, nullptr, nullptr, workspace, workspace_floats, stream);
+}
+extern "C" int vitssl_gemm_fp8_tn(const void* A8, const void* B8, float* C, int64_t M, int N1, int N2, const float* alpha,
+                                  const float* alpha2, float* workspace, int64_t workspace_floats, void* stream) {
+  return tn_launch_single<TnFp8, gemm_tn_fp8_kernel>(A8, B8, C, M, N1, N2, alpha, alpha2, workspace, workspace_floats, stream);
+}
+
+extern "C" int64_t vitssl_gemm_tn_batch_workspace_floats(const vitssl_tn_job_t* jobs, int njobs, int64_t M) {
+  return tn_batch_workspace<TnBf16>(jobs, njobs, M);
+}
+extern "C" int64_t vitssl_gemm_fp8_tn_batch_workspace_floats(const vitssl_fp8_tn_job_t* jobs, int njobs, int64_t M) {
+  return tn_batch_workspace<TnFp8>(jobs, njobs, M);
+}
+
+extern "C" int vitssl_gemm_bf16_tn_batch(const vitssl_tn_job_t* jobs, int njobs, int64_t M, float* workspace, int64_t workspace_floats,
+                                         void* stream) {
+  return tn_launch_batch<TnBf16, gemm_tn_batch_kernel>(jobs, njobs, M, workspace, workspace_floats, stream);
+}
+extern "C" int vitssl_gemm_fp8_tn_batch(const vitssl_fp8_tn_job_t* jobs, int njobs, int64_t M, float* workspace, int64_t workspace_floats,
+                                        void* stream) {
+  return tn_launch_batch<TnFp8, gemm_tn_fp8_batch_kernel>(jobs, njobs, M, workspace, workspace_floats, stream);
 }

@@ -1,6 +1,7 @@
 """Tensor-level wrappers over the C ABI: validate device/dtype/shape/contiguity on the
 host (a wrong shape must never reach a hand-written kernel), then enqueue on torch's
 current stream.  No computation happens in Python and there is no fallback path."""
+import collections
 import ctypes as C
 import operator
 
@@ -100,29 +101,6 @@ def _scalar(t, name):
     if t.numel() != 1:
         raise L.VitsslError(f"{name}: expected a 1-element fp32 device tensor")
     return _chk(t, F32, name)
-
-
-def gemm_fp8_tn_batch(jobs):
-    """For every (A8, B8, Cacc, alpha, alpha2) of `jobs` (at most 8, same row count M): Cacc += alpha * alpha2 * A8^T @ B8 on e4m3
-    operands, in one launch (vitssl_gemm_fp8_tn_batch)."""
-    if not jobs:
-        return
-    M = jobs[0][0].shape[0]
-    arr = (L.Fp8TnJob * len(jobs))()
-    flops = 0.0
-    for j, (A8, B8, Cacc, alpha, alpha2) in enumerate(jobs):
-        if A8.shape[0] != M or B8.shape[0] != M:
-            raise L.VitsslError(f"gemm_fp8_tn_batch: job {j}: row counts {A8.shape[0]} / {B8.shape[0]} differ from {M}")
-        N1, N2 = A8.shape[1], B8.shape[1]
-        a, b, c = _chk(A8, FP8, "A8"), _chk(B8, FP8, "B8"), _chk(Cacc, F32, "C", (N1, N2))
-        arr[j].A8, arr[j].B8, arr[j].C, arr[j].N1, arr[j].N2 = a.value, b.value, c.value, N1, N2
-        arr[j].alpha, arr[j].alpha2 = _scalar(alpha, "alpha").value, _scalar(alpha2, "alpha2").value
-        flops += 2.0 * M * N1 * N2
-    wsn = int(L.lib().vitssl_gemm_fp8_tn_batch_workspace_floats(arr, len(jobs), M))
-    ws = _tn_workspace(jobs[0][0].device, wsn)
-    ev = _prof_begin()
-    call("vitssl_gemm_fp8_tn_batch", arr, len(jobs), M, C.c_void_p(ws.data_ptr()), ws.numel(), _stream())
-    _prof_end(ev, f"gemm_fp8_tn batch{len(jobs)}x{M}", flops)
 
 
 def quantize_fp8(x, y8, scale=None, amax=None):
@@ -278,59 +256,76 @@ def _sum_ws(device, rows, cols):
     return C.c_void_p(ws.data_ptr()), ws.numel()
 
 
-def gemm_tn(A, B, Cacc, atomic=False):
-    """Cacc[N1,N2] (fp32) += A[M,N1]^T @ B[M,N2]."""
+# The weight-gradient GEMM has one launch path for its two operand kinds (csrc/gemm_tn.hip); what differs is listed here.
+_TnKind = collections.namedtuple("_TnKind", "label dtype sfx scalars entry query batch_entry batch_query Job")
+_TN_BF16 = _TnKind("gemm_tn", BF16, "", (), "vitssl_gemm_bf16_tn", "vitssl_gemm_tn_workspace_floats",
+                   "vitssl_gemm_bf16_tn_batch", "vitssl_gemm_tn_batch_workspace_floats", L.TnJob)
+_TN_FP8 = _TnKind("gemm_fp8_tn", FP8, "8", ("alpha", "alpha2"), "vitssl_gemm_fp8_tn", "vitssl_gemm_fp8_tn_workspace_floats",
+                  "vitssl_gemm_fp8_tn_batch", "vitssl_gemm_fp8_tn_batch_workspace_floats", L.Fp8TnJob)
+
+
+def _tn_single(k, A, B, Cacc, scalars, atomic):
     M, N1 = A.shape
     M2, N2 = B.shape
     if M != M2:
-        raise L.VitsslError(f"gemm_tn: M mismatch {M} vs {M2}")
-    a, b, c = _chk(A, BF16, "A"), _chk(B, BF16, "B"), _chk(Cacc, F32, "C", (N1, N2))
-    if atomic:
+        raise L.VitsslError(f"{k.label}: M mismatch {M} vs {M2}")
+    a, b, c = _chk(A, k.dtype, "A" + k.sfx), _chk(B, k.dtype, "B" + k.sfx), _chk(Cacc, F32, "C", (N1, N2))
+    if atomic:                    # NULL workspace: the partial tiles are added into C with atomics
         wsp, wsn = C.c_void_p(0), 0
     else:
-        wsn = int(L.lib().vitssl_gemm_tn_workspace_floats(M, N1, N2))
-        ws = _tn_workspace(A.device, wsn)
+        ws = _tn_workspace(A.device, int(getattr(L.lib(), k.query)(M, N1, N2)))
         wsp, wsn = C.c_void_p(ws.data_ptr()), ws.numel()
     ev = _prof_begin()
-    call("vitssl_gemm_bf16_tn", a, b, c, M, N1, N2, wsp, wsn, _stream())
-    _prof_end(ev, f"gemm_tn {N1}x{N2}x{M}", 2.0 * M * N1 * N2)
+    call(k.entry, a, b, c, M, N1, N2, *scalars, wsp, wsn, _stream())
+    _prof_end(ev, f"{k.label} {N1}x{N2}x{M}", 2.0 * M * N1 * N2)
+
+
+def _tn_batch(k, jobs):
+    if not jobs:
+        return
+    M = jobs[0][0].shape[0]
+    arr = (k.Job * len(jobs))()
+    flops = 0.0
+    for j, (A, B, Cacc, *scalars) in enumerate(jobs):
+        if len(scalars) != len(k.scalars):
+            raise L.VitsslError(f"{k.label}_batch: job {j}: expected (A, B, C{''.join(', ' + n for n in k.scalars)})")
+        if A.shape[0] != M or B.shape[0] != M:
+            raise L.VitsslError(f"{k.label}_batch: job {j}: row counts {A.shape[0]} / {B.shape[0]} differ from {M}")
+        N1, N2 = A.shape[1], B.shape[1]
+        q = arr[j]
+        setattr(q, "A" + k.sfx, _chk(A, k.dtype, "A" + k.sfx).value)
+        setattr(q, "B" + k.sfx, _chk(B, k.dtype, "B" + k.sfx).value)
+        q.C, q.N1, q.N2 = _chk(Cacc, F32, "C", (N1, N2)).value, N1, N2
+        for name, t in zip(k.scalars, scalars):
+            setattr(q, name, _scalar(t, name).value)
+        flops += 2.0 * M * N1 * N2
+    ws = _tn_workspace(jobs[0][0].device, int(getattr(L.lib(), k.batch_query)(arr, len(jobs), M)))
+    ev = _prof_begin()
+    call(k.batch_entry, arr, len(jobs), M, C.c_void_p(ws.data_ptr()), ws.numel(), _stream())
+    _prof_end(ev, f"{k.label} batch{len(jobs)}x{M}", flops)
+
+
+def gemm_tn(A, B, Cacc, atomic=False):
+    """Cacc[N1,N2] (fp32) += A[M,N1]^T @ B[M,N2].  `atomic`: no slab workspace, the partial tiles are added into Cacc with atomics."""
+    _tn_single(_TN_BF16, A, B, Cacc, (), atomic)
+
+
+def gemm_fp8_tn(A8, B8, Cacc, alpha=None, alpha2=None, atomic=False):
+    """Cacc[N1,N2] (fp32) += alpha * alpha2 * A8[M,N1]^T @ B8[M,N2] on e4m3 operands (weight gradient of the fp8 path);
+    `atomic` as in gemm_tn."""
+    _tn_single(_TN_FP8, A8, B8, Cacc, (_scalar(alpha, "alpha"), _scalar(alpha2, "alpha2")), atomic)
 
 
 def gemm_tn_batch(jobs):
     """For every (A, B, Cacc) of `jobs` (at most 8, all with the same row count M): Cacc[N1,N2] (fp32) += A[M,N1]^T @ B[M,N2], in
     one launch with one shared split count and one reduce pass (vitssl_gemm_bf16_tn_batch)."""
-    if not jobs:
-        return
-    M = jobs[0][0].shape[0]
-    arr = (L.TnJob * len(jobs))()
-    flops = 0.0
-    for j, (A, B, Cacc) in enumerate(jobs):
-        if A.shape[0] != M or B.shape[0] != M:
-            raise L.VitsslError(f"gemm_tn_batch: job {j}: row counts {A.shape[0]} / {B.shape[0]} differ from {M}")
-        N1, N2 = A.shape[1], B.shape[1]
-        a, b, c = _chk(A, BF16, "A"), _chk(B, BF16, "B"), _chk(Cacc, F32, "C", (N1, N2))
-        arr[j].A, arr[j].B, arr[j].C, arr[j].N1, arr[j].N2 = a.value, b.value, c.value, N1, N2
-        flops += 2.0 * M * N1 * N2
-    wsn = int(L.lib().vitssl_gemm_tn_batch_workspace_floats(arr, len(jobs), M))
-    ws = _tn_workspace(jobs[0][0].device, wsn)
-    ev = _prof_begin()
-    call("vitssl_gemm_bf16_tn_batch", arr, len(jobs), M, C.c_void_p(ws.data_ptr()), ws.numel(), _stream())
-    _prof_end(ev, f"gemm_tn batch{len(jobs)}x{M}", flops)
+    _tn_batch(_TN_BF16, jobs)
 
 
-def gemm_fp8_tn(A8, B8, Cacc, alpha=None, alpha2=None):
-    """Cacc[N1,N2] (fp32) += alpha * alpha2 * A8[M,N1]^T @ B8[M,N2] on e4m3 operands (weight gradient of the fp8 path)."""
-    M, N1 = A8.shape
-    M2, N2 = B8.shape
-    if M != M2:
-        raise L.VitsslError(f"gemm_fp8_tn: M mismatch {M} vs {M2}")
-    a, b, c = _chk(A8, FP8, "A8"), _chk(B8, FP8, "B8"), _chk(Cacc, F32, "C", (N1, N2))
-    wsn = int(L.lib().vitssl_gemm_fp8_tn_workspace_floats(M, N1, N2))
-    ws = _tn_workspace(A8.device, wsn)
-    ev = _prof_begin()
-    call("vitssl_gemm_fp8_tn", a, b, c, M, N1, N2, _scalar(alpha, "alpha"), _scalar(alpha2, "alpha2"), C.c_void_p(ws.data_ptr()),
-         ws.numel(), _stream())
-    _prof_end(ev, f"gemm_fp8_tn {N1}x{N2}x{M}", 2.0 * M * N1 * N2)
+def gemm_fp8_tn_batch(jobs):
+    """For every (A8, B8, Cacc, alpha, alpha2) of `jobs` (at most 8, same row count M): Cacc += alpha * alpha2 * A8^T @ B8 on e4m3
+    operands, in one launch (vitssl_gemm_fp8_tn_batch)."""
+    _tn_batch(_TN_FP8, jobs)
 
 
 def attn_fwd(qkv, out, lse, B, N, H, dh, probs=None, out_fp8=None):
