@@ -8,7 +8,12 @@
 // it): the bf16 gradient is then the rounded image of the fp64 value and does not flip at rounding boundaries.
 // Sums over rows follow the library's rule (common.h, "deterministic sums"): a row stores its loss and its fp32 gradient in
 // its own slot of the caller's workspace; classify_finish_kernel and vs_reduce_parts add the slots in a fixed order.
+//
+// MIX (include/vitssl_mixup.h, vitssl_classify_loss_mix): the same kernels against the two-label target of a mixed image.  A
+// row whose two labels coincide, or whose weight is 0 or 1, runs the one-label statements below unchanged; a genuine
+// two-label row keeps the second label's term apart as well.  The one-label instantiation contains none of it.
 #include "../../include/vitssl_classify.h"
+#include "../../include/vitssl_mixup.h"
 #include "common.h"
 #include <math.h>
 
@@ -43,6 +48,8 @@ __device__ __forceinline__ bool arg_better(float v, int i, float bv, int bi) {
 struct ClArgs {
   const float* logits;
   const long long* labels;
+  const int* partner;        // MIX: [B]
+  const float* lam;          // MIX: [B]
   double* row_loss;          // workspace: [B]
   float* parts;              // workspace: [B, cp] fp32 gradient rows (read by the bias-gradient sum), or nullptr
   bf16_t* dlogits;           // or nullptr
@@ -54,8 +61,29 @@ struct ClArgs {
 
 __device__ __forceinline__ bool label_valid(long long l, long long ignore_index, int C) { return l != ignore_index && l >= 0 && l < C; }
 
+// what a row contributes: ROW_VALID, ROW_IGNORED (nothing), ROW_BAD (nothing, and counted in bad_labels).  MIX: la / lb / lm
+// are the row's two labels and its weight; nothing is read through a partner outside [0, B)
+enum { ROW_VALID = 0, ROW_IGNORED = 1, ROW_BAD = 2 };
+template <bool MIX>
+__device__ __forceinline__ int row_state(const long long* labels, const int* partner, const float* lam, int i, int B, int C,
+                                         long long ignore_index, long long& la, long long& lb, float& lm) {
+  la = lb = labels[i];
+  lm = 1.f;
+  if constexpr (!MIX) {
+    return label_valid(la, ignore_index, C) ? ROW_VALID : la == ignore_index ? ROW_IGNORED : ROW_BAD;
+  } else {
+    const int p = partner[i];
+    lm = lam[i];
+    const bool pok = p >= 0 && p < B;
+    if (pok) lb = labels[p];
+    const bool bad = !pok || !(lm >= 0.f && lm <= 1.f) || (la != ignore_index && (la < 0 || la >= C)) ||
+                     (lb != ignore_index && (lb < 0 || lb >= C));
+    return bad ? ROW_BAD : (la == ignore_index || lb == ignore_index) ? ROW_IGNORED : ROW_VALID;
+  }
+}
+
 // REG: the row's chunks (C <= CL_NV * CL_CHUNK) stay in registers between the passes; otherwise every pass re-reads the row
-template <bool REG>
+template <bool REG, bool MIX>
 __global__ __launch_bounds__(CL_THREADS) void classify_rows_kernel(ClArgs a) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * CL_WAVES + (threadIdx.x >> 6);
@@ -64,11 +92,29 @@ __global__ __launch_bounds__(CL_THREADS) void classify_rows_kernel(ClArgs a) {
   // n_valid: every wave counts the B labels itself (B / 64 coalesced reads), so the gradient's 1 / n_valid needs neither a
   // launch of its own nor a host read
   int nv = 0;
-  for (int i = lane; i < a.B; i += 64) nv += label_valid(a.labels[i], a.ignore_index, C) ? 1 : 0;
-  nv = wave_sum_i(nv);
-  const long long lab = a.labels[row];
-  const bool valid = label_valid(lab, a.ignore_index, C);
-  const int y = valid ? (int)lab : -1;                           // -1 matches no column: nothing is indexed by a bad label
+  bool valid;
+  int y, y2 = -1;                                                // y2: the second label of a two-label row (MIX), else no column
+  double wa = 1.0, wb = 0.0;                                     // their weights
+  if constexpr (!MIX) {
+    for (int i = lane; i < a.B; i += 64) nv += label_valid(a.labels[i], a.ignore_index, C) ? 1 : 0;
+    nv = wave_sum_i(nv);
+    const long long lab = a.labels[row];
+    valid = label_valid(lab, a.ignore_index, C);
+    y = valid ? (int)lab : -1;                                   // -1 matches no column: nothing is indexed by a bad label
+  } else {
+    long long la, lb;
+    float lm;
+    for (int i = lane; i < a.B; i += 64) nv += row_state<true>(a.labels, a.partner, a.lam, i, a.B, C, a.ignore_index, la, lb, lm) == ROW_VALID ? 1 : 0;
+    nv = wave_sum_i(nv);
+    valid = row_state<true>(a.labels, a.partner, a.lam, row, a.B, C, a.ignore_index, la, lb, lm) == ROW_VALID;
+    y = -1;
+    if (valid) {
+      if (la == lb || lm == 1.f) y = (int)la;                    // one-label rows: the statements of the one-label kernel
+      else if (lm == 0.f) y = (int)lb;
+      else y = (int)la, y2 = (int)lb, wa = (double)lm, wb = 1.0 - (double)lm;
+    }
+  }
+  const bool two = MIX && y2 >= 0;                               // wave-uniform
   const float* zr = a.logits + (long long)row * a.ld;
   const int nk = (C + CL_CHUNK - 1) / CL_CHUNK;
 
@@ -118,7 +164,7 @@ __global__ __launch_bounds__(CL_THREADS) void classify_rows_kernel(ClArgs a) {
 
   // pass 2: exp(z - max); the label's term apart, so that 1 - p[y] is a sum and not a difference
   const double md = (double)m;
-  double so = 0.0, ey = 0.0, zy = 0.0;
+  double so = 0.0, ey = 0.0, zy = 0.0, e2 = 0.0, z2 = 0.0;
   chunks([&](auto k) {
     f32x4 v;
     if constexpr (REG) v = zc[(int)k]; else v = load(k);
@@ -128,7 +174,11 @@ __global__ __launch_bounds__(CL_THREADS) void classify_rows_kernel(ClArgs a) {
       double x = 0.0;
       if (col + e < C) {
         x = exp((double)v[e] - md);
-        if (col + e == y) ey = x, zy = (double)v[e]; else so += x;
+        if constexpr (MIX) {
+          if (col + e == y) ey = x, zy = (double)v[e]; else if (col + e == y2) e2 = x, z2 = (double)v[e]; else so += x;
+        } else {
+          if (col + e == y) ey = x, zy = (double)v[e]; else so += x;
+        }
       }
       if constexpr (REG) ec[(int)k][e] = x;
     }
@@ -136,10 +186,19 @@ __global__ __launch_bounds__(CL_THREADS) void classify_rows_kernel(ClArgs a) {
   so = wave_sum_d(so);
   ey = wave_sum_d(ey);
   zy = wave_sum_d(zy);
-  const double s = so + ey;
+  double s = so + ey;
+  if (two) {
+    e2 = wave_sum_d(e2);
+    z2 = wave_sum_d(z2);
+    s += e2;
+  }
   if (lane == 0) {
     double loss = 0.0;
-    if (valid) {
+    if (two) {
+      const double ls = log(s);
+      loss = (1.0 - a.eps) * (wa * ((md - zy) + ls) + wb * ((md - z2) + ls));
+      if (a.eps > 0.0) loss += a.eps * ((md + ls) - zs / (double)C);
+    } else if (valid) {
       const double ls = ey == 1.0 ? log1p(so) : log(s);         // the label is the row's maximum: s = 1 + so
       loss = (1.0 - a.eps) * ((md - zy) + ls);
       if (a.eps > 0.0) loss += a.eps * ((md + log(s)) - zs / (double)C);
@@ -151,7 +210,12 @@ __global__ __launch_bounds__(CL_THREADS) void classify_rows_kernel(ClArgs a) {
 
   // pass 3: the gradient, to the bf16 operand (every column below ld_out) and to the row's slot of the bias-gradient sum
   const double scale = a.upstream / (double)nv, inv_s = 1.0 / s, sm = a.eps / (double)C;
-  const double gy = (a.eps * (1.0 - 1.0 / (double)C) - so * inv_s) * scale;       // p[y] - (1 - eps) - eps / C
+  double gy = (a.eps * (1.0 - 1.0 / (double)C) - so * inv_s) * scale;             // p[y] - (1 - eps) - eps / C
+  double gy2 = 0.0;
+  if (two) {                                                     // p[a] - wa (1 - eps) - eps / C, and the same for b
+    gy = ((wb * (1.0 - a.eps) + a.eps * (1.0 - 1.0 / (double)C)) - (so + e2) * inv_s) * scale;
+    gy2 = ((wa * (1.0 - a.eps) + a.eps * (1.0 - 1.0 / (double)C)) - (so + ey) * inv_s) * scale;
+  }
   bf16_t* dr = a.dlogits ? a.dlogits + (long long)row * a.ld_out : nullptr;
   float* pr = a.parts ? a.parts + (long long)row * a.cp : nullptr;
   chunks([&](auto k) {
@@ -166,7 +230,10 @@ __global__ __launch_bounds__(CL_THREADS) void classify_rows_kernel(ClArgs a) {
         if (col + e < C) {
           double x;
           if constexpr (REG) x = ec[(int)k][e]; else x = exp((double)v[e] - md);
-          g[e] = (float)(col + e == y ? gy : (x * inv_s - sm) * scale);
+          if constexpr (MIX)
+            g[e] = (float)(col + e == y ? gy : col + e == y2 ? gy2 : (x * inv_s - sm) * scale);
+          else
+            g[e] = (float)(col + e == y ? gy : (x * inv_s - sm) * scale);
         }
     }
     if (dr) {                                                    // col < C <= ld_out and ld_out % 4 == 0
@@ -182,7 +249,9 @@ __global__ __launch_bounds__(CL_THREADS) void classify_rows_kernel(ClArgs a) {
 }
 
 // one workgroup: loss_out = {sum of the row losses in a fixed order, n_valid}; counters and bad_labels accumulated
+template <bool MIX>
 __global__ __launch_bounds__(CL_THREADS) void classify_finish_kernel(const double* __restrict__ row_loss, const long long* __restrict__ labels,
+                                                                     const int* __restrict__ partner, const float* __restrict__ lam,
                                                                      const long long* __restrict__ pred, long long ignore_index, int B, int C,
                                                                      float* __restrict__ loss_out, long long* __restrict__ counters,
                                                                      int* __restrict__ bad_labels) {
@@ -192,12 +261,14 @@ __global__ __launch_bounds__(CL_THREADS) void classify_finish_kernel(const doubl
   double sum = 0.0;
   int nvalid = 0, ncorrect = 0, nbad = 0;
   for (int i = tid; i < B; i += CL_THREADS) {
-    const long long l = labels[i];
-    if (label_valid(l, ignore_index, C)) {
+    long long l, lb;
+    float lm;
+    const int st = row_state<MIX>(labels, partner, lam, i, B, C, ignore_index, l, lb, lm);
+    if (st == ROW_VALID) {
       sum += row_loss[i];
       ++nvalid;
-      ncorrect += pred[i] == l ? 1 : 0;
-    } else if (l != ignore_index) {
+      ncorrect += pred[i] == l ? 1 : 0;                          // MIX: the row's own label
+    } else if (st == ROW_BAD) {
       ++nbad;
     }
   }
@@ -232,28 +303,30 @@ extern "C" int64_t vitssl_classify_loss_workspace_floats(int B, int C) {
   return cl_loss_floats(B) + (long long)B * cl_cp(C);
 }
 
-extern "C" int vitssl_classify_loss(const float* logits, const int64_t* labels, int B, int C, int ld, double label_smoothing,
-                                    int64_t ignore_index, float upstream, float* loss_out, void* dlogits_bf16, int ld_out,
-                                    float* dbias, int64_t* pred, int64_t* counters, int32_t* bad_labels, float* workspace,
-                                    int64_t workspace_floats, void* stream) {
-  VS_CHECK_ARG(logits && labels && loss_out && pred && counters && bad_labels, "classify_loss: null pointer");
-  VS_CHECK_ARG(B >= 1 && B <= CL_MAX_B, "classify_loss: B = %d rows is outside 1 <= B <= 2^22", B);
-  VS_CHECK_ARG(C >= 2 && C <= CL_MAX_C, "classify_loss: C = %d classes is outside 2 <= C <= 65536", C);
-  VS_CHECK_ARG(ld >= C && ld % 4 == 0, "classify_loss: C = %d classes need a row length ld >= C that is a multiple of 4, got ld = %d", C, ld);
-  VS_CHECK_ARG(label_smoothing >= 0.0 && label_smoothing <= 1.0, "classify_loss: label_smoothing = %g is outside 0 <= eps <= 1",
-               label_smoothing);
+// both entry points: `who` names the caller in the messages; partner == nullptr is the one-label loss
+static int classify_launch(const char* who, const char* sizing, const float* logits, const int64_t* labels, const int32_t* partner, const float* lam,
+                           int B, int C, int ld, double label_smoothing, int64_t ignore_index, float upstream, float* loss_out,
+                           void* dlogits_bf16, int ld_out, float* dbias, int64_t* pred, int64_t* counters, int32_t* bad_labels,
+                           float* workspace, int64_t workspace_floats, void* stream) {
+  VS_CHECK_ARG(logits && labels && loss_out && pred && counters && bad_labels, "%s: null pointer", who);
+  VS_CHECK_ARG(B >= 1 && B <= CL_MAX_B, "%s: B = %d rows is outside 1 <= B <= 2^22", who, B);
+  VS_CHECK_ARG(C >= 2 && C <= CL_MAX_C, "%s: C = %d classes is outside 2 <= C <= 65536", who, C);
+  VS_CHECK_ARG(ld >= C && ld % 4 == 0, "%s: C = %d classes need a row length ld >= C that is a multiple of 4, got ld = %d", who, C, ld);
+  VS_CHECK_ARG(label_smoothing >= 0.0 && label_smoothing <= 1.0, "%s: label_smoothing = %g is outside 0 <= eps <= 1", who, label_smoothing);
   if (dlogits_bf16)
-    VS_CHECK_ARG(ld_out >= C && ld_out % 64 == 0, "classify_loss: dlogits needs a row length ld_out >= C = %d that is a multiple of 64, got ld_out = %d",
+    VS_CHECK_ARG(ld_out >= C && ld_out % 64 == 0, "%s: dlogits needs a row length ld_out >= C = %d that is a multiple of 64, got ld_out = %d", who,
                  C, ld_out);
   VS_CHECK_ARG((((uintptr_t)logits | (uintptr_t)dlogits_bf16 | (uintptr_t)workspace) & 15) == 0,
-               "classify_loss: logits, dlogits and workspace must be 16-byte aligned");
-  VS_CHECK_ARG((((uintptr_t)labels | (uintptr_t)pred | (uintptr_t)counters) & 7) == 0, "classify_loss: labels, pred and counters must be 8-byte aligned");
-  if (!vs_parts(workspace, workspace_floats, vitssl_classify_loss_workspace_floats(B, C), "classify_loss", "vitssl_classify_loss_workspace_floats"))
-    return VITSSL_ERR_ARG;
+               "%s: logits, dlogits and workspace must be 16-byte aligned", who);
+  VS_CHECK_ARG((((uintptr_t)labels | (uintptr_t)pred | (uintptr_t)counters) & 7) == 0, "%s: labels, pred and counters must be 8-byte aligned", who);
+  VS_CHECK_ARG((((uintptr_t)partner | (uintptr_t)lam) & 3) == 0, "%s: partner and lam must be 4-byte aligned", who);
+  if (!vs_parts(workspace, workspace_floats, vitssl_classify_loss_workspace_floats(B, C), who, sizing)) return VITSSL_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
   ClArgs a;
   a.logits = logits;
   a.labels = (const long long*)labels;
+  a.partner = partner;
+  a.lam = lam;
   a.row_loss = (double*)workspace;
   a.parts = dbias ? workspace + cl_loss_floats(B) : nullptr;
   a.dlogits = (bf16_t*)dlogits_bf16;
@@ -263,14 +336,47 @@ extern "C" int vitssl_classify_loss(const float* logits, const int64_t* labels, 
   a.upstream = (double)upstream;
   a.B = B, a.C = C, a.ld = ld, a.ld_out = ld_out, a.cp = (int)cl_cp(C);
   const dim3 grid((unsigned)((B + CL_WAVES - 1) / CL_WAVES)), block(CL_THREADS);
-  if (C <= CL_NV * CL_CHUNK)
-    hipLaunchKernelGGL(classify_rows_kernel<true>, grid, block, 0, s, a);
+  const bool reg = C <= CL_NV * CL_CHUNK;
+  if (!partner) {
+    if (reg)
+      hipLaunchKernelGGL((classify_rows_kernel<true, false>), grid, block, 0, s, a);
+    else
+      hipLaunchKernelGGL((classify_rows_kernel<false, false>), grid, block, 0, s, a);
+  } else {
+    if (reg)
+      hipLaunchKernelGGL((classify_rows_kernel<true, true>), grid, block, 0, s, a);
+    else
+      hipLaunchKernelGGL((classify_rows_kernel<false, true>), grid, block, 0, s, a);
+  }
+  VS_CHECK_LAUNCH(who);
+  if (!partner)
+    hipLaunchKernelGGL(classify_finish_kernel<false>, dim3(1), block, 0, s, (const double*)a.row_loss, a.labels, a.partner, a.lam,
+                       (const long long*)a.pred, (long long)ignore_index, B, C, loss_out, (long long*)counters, bad_labels);
   else
-    hipLaunchKernelGGL(classify_rows_kernel<false>, grid, block, 0, s, a);
-  VS_CHECK_LAUNCH("classify_loss");
-  hipLaunchKernelGGL(classify_finish_kernel, dim3(1), block, 0, s, (const double*)a.row_loss, a.labels, (const long long*)a.pred, (long long)ignore_index,
-                     B, C, loss_out, (long long*)counters, bad_labels);
-  VS_CHECK_LAUNCH("classify_loss (finish)");
+    hipLaunchKernelGGL(classify_finish_kernel<true>, dim3(1), block, 0, s, (const double*)a.row_loss, a.labels, a.partner, a.lam,
+                       (const long long*)a.pred, (long long)ignore_index, B, C, loss_out, (long long*)counters, bad_labels);
+  VS_CHECK_LAUNCH(who);
   if (dbias) return vs_reduce_parts(dbias, a.parts, B, C, a.cp, s);
   return VITSSL_OK;
+}
+
+extern "C" int vitssl_classify_loss(const float* logits, const int64_t* labels, int B, int C, int ld, double label_smoothing,
+                                    int64_t ignore_index, float upstream, float* loss_out, void* dlogits_bf16, int ld_out,
+                                    float* dbias, int64_t* pred, int64_t* counters, int32_t* bad_labels, float* workspace,
+                                    int64_t workspace_floats, void* stream) {
+  return classify_launch("classify_loss", "vitssl_classify_loss_workspace_floats", logits, labels, nullptr, nullptr, B, C, ld, label_smoothing,
+                         ignore_index, upstream, loss_out, dlogits_bf16, ld_out, dbias, pred, counters, bad_labels, workspace, workspace_floats,
+                         stream);
+}
+
+extern "C" int64_t vitssl_classify_loss_mix_workspace_floats(int B, int C) { return vitssl_classify_loss_workspace_floats(B, C); }
+
+extern "C" int vitssl_classify_loss_mix(const float* logits, const int64_t* labels, const int32_t* partner, const float* lam, int B, int C,
+                                        int ld, double label_smoothing, int64_t ignore_index, float upstream, float* loss_out,
+                                        void* dlogits_bf16, int ld_out, float* dbias, int64_t* pred, int64_t* counters,
+                                        int32_t* bad_labels, float* workspace, int64_t workspace_floats, void* stream) {
+  VS_CHECK_ARG(partner && lam, "classify_loss_mix: null pointer");
+  return classify_launch("classify_loss_mix", "vitssl_classify_loss_mix_workspace_floats", logits, labels, partner, lam, B, C, ld,
+                         label_smoothing, ignore_index, upstream, loss_out, dlogits_bf16, ld_out, dbias, pred, counters, bad_labels, workspace,
+                         workspace_floats, stream);
 }

@@ -7,3 +7,4 @@ __path__ = extend_path(__path__, __name__)
 
 from .multicrop import GPUMultiCrop, ViewSpec, params_as_list, sample_batch_params, sample_view_params  # noqa: F401
 from .transforms import GPUTransform, TransformSpec, sample_transform_params  # noqa: F401
+from .mixup import GPUMixup, MixParams, MixSpec, sample_mix_params  # noqa: F401

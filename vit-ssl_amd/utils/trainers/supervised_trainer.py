@@ -4,6 +4,8 @@ through the HIP engine; with `training.fused_step: true` (and the fused AdamW, a
 nn.CrossEntropyLoss(weight=None, reduction="mean")) every step is `ViT.train_step` / `ViT.eval_step`: loss, backward,
 all-reduce and AdamW as one engine schedule that does only the work the model's frozen state needs, with one host read
 per epoch.  Anything else falls back to the autograd path and says so once.
+`training.mixup: {mixup_alpha, cutmix_alpha, prob, switch_prob, mode}` (fused path only, else a ValueError at construction): the
+training batches are mixed on the GPU (data.GPUMixup, timm's Mixup semantics) and the loss is taken against the two-label targets.
 Batches are (images, labels); uint8 [B,H,W,3] images are rendered on the GPU (`BaseTrainer._batch`).
 The names of the config's `metrics` (Accuracy, F1Score, Recall, Precision) come from a confusion matrix accumulated on the
 device per batch (utils/gpu_metrics.py); with `Accuracy` listed the best checkpoint is the one with the highest validation
@@ -19,7 +21,7 @@ import math
 import torch
 from torch import nn
 
-from .._config import cfg_get
+from .._config import cfg_get, to_plain
 from ..train_utils import make_optimizer
 from .base_trainer import BaseTrainer
 
@@ -30,6 +32,7 @@ class SupervisedTrainer(BaseTrainer):
     def __init__(self, *args, **kwargs):
         super().__init__(*args, **kwargs)
         self._read_schedule_keys()
+        self._read_mixup()
         if self.reducer is not None and self._fused_path():
             self._rebuild_reducer()
 
@@ -42,6 +45,24 @@ class SupervisedTrainer(BaseTrainer):
         self.fused_step = bool(cfg_get(self.config, "training", "fused_step", default=False))
         self._fallback_logged = False
         self._step_counters = None
+
+    def _read_mixup(self):
+        """`training.mixup: {mixup_alpha, cutmix_alpha, prob, switch_prob, mode}` (timm's Mixup; data.MixSpec): the training
+        batches of the fused step are mixed on the GPU and the loss is taken against the two-label targets.  Validation
+        never mixes."""
+        node = cfg_get(self.config, "training", "mixup")
+        self.mixup = None
+        if node is None or node is False:
+            return
+        from data import GPUMixup, MixSpec
+        spec = MixSpec.from_config({} if node is True else to_plain(node))
+        if not self._fused_path():
+            c = self.criterion
+            raise ValueError("training.mixup needs the fused supervised step (training.fused_step: true, with the fused AdamW over a "
+                             "model with train_step and nn.CrossEntropyLoss(weight=None, reduction='mean')): only its loss kernel "
+                             f"takes two-label targets; configured here are training.fused_step = {getattr(self, 'fused_step', False)!r}, "
+                             f"optimizer {type(self.optimizer).__name__}, criterion {type(c).__name__}")
+        self.mixup = GPUMixup(spec)
 
     # ---- fused path --------------------------------------------------------------
     def _fused_path(self) -> bool:
@@ -83,8 +104,11 @@ class SupervisedTrainer(BaseTrainer):
         total, running, counters = 0, None, self._counters()
         for batch in self.train_loader:
             inputs, labels = self._labelled(batch, "train")
+            kw = {}
+            if getattr(self, "mixup", None) is not None:
+                kw["mix"] = self.mixup.draw(inputs.shape[0], inputs.shape[2], inputs.shape[3], self.transform_generator, inputs.device)
             loss = self.model.train_step(inputs, labels, self.optimizer, self.reducer, label_smoothing=c.label_smoothing,
-                                         ignore_index=c.ignore_index, counters=counters)
+                                         ignore_index=c.ignore_index, counters=counters, **kw)
             self._warmup_step(epoch)
             running = loss if running is None else running + loss
             self._fused_update_metrics(labels)

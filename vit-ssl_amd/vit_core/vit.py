@@ -114,15 +114,21 @@ class _ViTRuntime:
             self.rec = dict(feats=feats, h=h, mean=mean, rstd=rstd, wt=wt, Nk=Nk, B=B)
         return logits, probs
 
-    def loss(self, logits, labels, tag, label_smoothing, ignore_index, counters, dlogits=None, dbias=None):
-        """csrc/classify.hip on the padded logits -> (loss as a device scalar, pred i64 [B])."""
+    def loss(self, logits, labels, tag, label_smoothing, ignore_index, counters, dlogits=None, dbias=None, mix=None):
+        """csrc/classify.hip on the padded logits -> (loss as a device scalar, pred i64 [B]).  `mix` (data.MixParams): against
+        the two-label targets of a mixed batch."""
         B, dev = logits.shape[0], logits.device
         if labels.dtype != torch.int64 or not labels.is_contiguous():
             labels = labels.to(torch.int64).contiguous()
         loss_out = self.ws.get(tag + "loss_out", (2,), F32, dev)
         pred = self.ws.get(tag + "pred", (B,), torch.int64, dev)
-        ops.classify_loss(logits, labels, self.ncls, loss_out, pred, self.counters if counters is None else counters, self.bad_labels,
-                          dlogits=dlogits, dbias=dbias, label_smoothing=label_smoothing, ignore_index=ignore_index)
+        counters = self.counters if counters is None else counters
+        if mix is None:
+            ops.classify_loss(logits, labels, self.ncls, loss_out, pred, counters, self.bad_labels,
+                              dlogits=dlogits, dbias=dbias, label_smoothing=label_smoothing, ignore_index=ignore_index)
+        else:
+            ops.classify_loss_mix(logits, labels, mix.partner, mix.lam, self.ncls, loss_out, pred, counters, self.bad_labels,
+                                  dlogits=dlogits, dbias=dbias, label_smoothing=label_smoothing, ignore_index=ignore_index)
         return loss_out[0] / loss_out[1], pred         # 0 / 0 = nan when every row is ignored, as torch gives
 
     def backward(self, dlb, sched, reducer=None):
@@ -231,12 +237,16 @@ class ViT(nn.Module):
             raise L.VitsslError(f"ViT: {n} label(s) outside [0, {self.num_classes}) reached train_step / eval_step; their rows were ignored")
 
     def train_step(self, x: torch.Tensor, labels: torch.Tensor, optimizer, reducer=None, label_smoothing: float = 0.0,
-                   ignore_index: int = -100, counters=None) -> torch.Tensor:
+                   ignore_index: int = -100, counters=None, mix=None) -> torch.Tensor:
         """One full optimisation step (zero_grad -> forward -> CrossEntropyLoss(mean, label_smoothing, ignore_index) ->
         backward -> gradient all-reduce -> AdamW) with no autograd graph; returns the loss as a device scalar (no host sync).
         Equivalent to utils/trainers/supervised_trainer.py:33-40 of the reference.  Leaves `last_logits` ([B, C] view of the
         padded GEMM output) and `last_pred` (i64 [B]) on the model; `counters` (i64 [2] on the device, default: the
-        runtime's own) accumulates (correct, valid) rows."""
+        runtime's own) accumulates (correct, valid) rows.
+        `mix` (data.MixParams, from data.GPUMixup.draw): Mixup / CutMix.  The batch is mixed into a workspace buffer
+        (vitssl_mix_batch) and the loss is taken against the two-label targets lam s(y[i]) + (1 - lam) s(y[partner])
+        (vitssl_classify_loss_mix); a row of an invalid table counts as a bad label (`check_labels`).  The counters then
+        compare the prediction with the row's own label.  Without `mix` nothing of this is launched."""
         R.require_gpu(x, "ViT.train_step")
         rt = self.runtime(x.device)
         st = rt.store
@@ -244,10 +254,14 @@ class ViT(nn.Module):
             sched = rt.schedule()
             if sched == "head":                        # nothing below the head trains: no activations are kept
                 rt.bb.forget("a")
+            if mix is not None:
+                mixed = rt.ws.get("mix.x", tuple(x.shape), F32, x.device)
+                ops.mix_batch(R.as_f32(x), mixed, mix.iparams, mix.lam)
+                x = mixed
             logits, _ = rt.forward(x, True, save=True, save_backbone=sched != "head")
             dlb = rt.ws.get("head.dlogits", tuple(logits.shape), BF16, x.device)
             loss, pred = rt.loss(logits, labels, "head.", label_smoothing, ignore_index, counters, dlogits=dlb,
-                                 dbias=st.gview("classification_head.linear.bias"))
+                                 dbias=st.gview("classification_head.linear.bias"), mix=mix)
             rt.backward(dlb, sched, reducer)
             apply()
             self.last_logits, self.last_pred = logits[:, :self.num_classes], pred

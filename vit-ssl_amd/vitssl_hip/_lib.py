@@ -14,6 +14,7 @@ CLASSIFY_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include
 ATTENTION_HD_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "vitssl_attention_hd.h"))
 PATCH_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "vitssl_patch.h"))
 OPTIM_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "vitssl_optim.h"))
+MIXUP_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "vitssl_mixup.h"))
 
 
 class VitsslError(RuntimeError):
@@ -161,6 +162,14 @@ PROTOTYPES_OPTIM = {
     "vitssl_adamw_segments": [_vp, _vp, _vp, _vp, _vp, _i, _f, _f, _f, _f, _i, _f, _vp, _f, _vp],
 }
 
+# include/vitssl_mixup.h (Mixup / CutMix: the mix kernel and the classification loss against two-label targets): the launching
+# entry points; the sizing function vitssl_classify_loss_mix_workspace_floats (returns a count) is bound in lib() beside the
+# other sizing functions.
+PROTOTYPES_MIXUP = {
+    "vitssl_mix_batch": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    "vitssl_classify_loss_mix": [_vp, _vp, _vp, _vp, _i, _i, _i, C.c_double, _i64, _f, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
+}
+
 _lib = None
 
 
@@ -213,6 +222,13 @@ def optim_header_symbols():
     return sorted(set(re.findall(r"\b(vitssl_[a-z0-9_]+)\s*\(", txt)))
 
 
+def mixup_header_symbols():
+    """Entry points and sizing functions declared in include/vitssl_mixup.h."""
+    with open(MIXUP_HEADER_PATH) as f:
+        txt = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)        # the comments name functions of vitssl_classify.h
+    return sorted(set(re.findall(r"\b(vitssl_[a-z0-9_]+)\s*\(", txt)))
+
+
 def lib():
     global _lib
     if _lib is not None:
@@ -260,12 +276,14 @@ def lib():
     l.vitssl_dino_stats_workspace_floats.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
     l.vitssl_classify_loss_workspace_floats.restype = C.c_int64
     l.vitssl_classify_loss_workspace_floats.argtypes = [C.c_int, C.c_int]
+    l.vitssl_classify_loss_mix_workspace_floats.restype = C.c_int64
+    l.vitssl_classify_loss_mix_workspace_floats.argtypes = [C.c_int, C.c_int]
     for sizing in ("vitssl_optim_table_bytes", "vitssl_grad_sumsq_workspace_bytes"):
         getattr(l, sizing).restype = C.c_int64
         getattr(l, sizing).argtypes = [C.c_int]
     for name, args in (list(PROTOTYPES.items()) + list(PROTOTYPES_TRANSFORMS.items()) + list(PROTOTYPES_METRICS.items())
                        + list(PROTOTYPES_CLASSIFY.items()) + list(PROTOTYPES_ATTENTION_HD.items()) + list(PROTOTYPES_PATCH.items())
-                       + list(PROTOTYPES_OPTIM.items())):
+                       + list(PROTOTYPES_OPTIM.items()) + list(PROTOTYPES_MIXUP.items())):
         fn = getattr(l, name)  # AttributeError if the symbol is missing
         fn.restype = C.c_int
         fn.argtypes = args

@@ -853,6 +853,31 @@ def dino_stats(teacher, student, center, out):
 I64, I32 = torch.int64, torch.int32
 
 
+def _classify(who, entry, sizing, between, logits, labels, C, loss_out, pred, counters, bad_labels, dlogits, dbias, label_smoothing,
+              ignore_index, upstream, workspace):
+    """the checks and the call shared by classify_loss and classify_loss_mix; `between`: the (tensor, dtype, name) arguments the
+    entry point takes between `labels` and `B`"""
+    if logits is None or logits.dim() != 2 or not 2 <= int(C) <= logits.shape[1]:
+        raise L.VitsslError(f"{who}: expected logits [B, ld] with 2 <= C = {C} <= ld, got {None if logits is None else tuple(logits.shape)}")
+    B, ld = logits.shape
+    ld_out = 0
+    if dlogits is not None:
+        if dlogits.dim() != 2 or dlogits.shape[0] != B or dlogits.shape[1] % 64 != 0 or dlogits.shape[1] < C:
+            raise L.VitsslError(f"{who}: dlogits must be [{B}, ld_out] with ld_out % 64 == 0 and ld_out >= {C}, got {tuple(dlogits.shape)}")
+        ld_out = dlogits.shape[1]
+    z, y = _chk(logits, F32, "logits"), _chk(labels, I64, "labels", (B,))
+    extra = [_chk(t, dtype, name, (B,)) for t, dtype, name in between]
+    lo, pr = _chk(loss_out, F32, "loss_out", (2,)), _chk(pred, I64, "pred", (B,))
+    ct, bl = _chk(counters, I64, "counters", (2,)), _chk(bad_labels, I32, "bad_labels", (1,))
+    dl, db = _opt(dlogits, BF16, "dlogits"), _opt(dbias, F32, "dbias", (C,))
+    need = int(getattr(L.lib(), sizing)(B, C))
+    ws = _tn_workspace(logits.device, need) if workspace is None else workspace      # shared scratch: launches on one stream are ordered
+    if workspace is not None:
+        _chk(ws, F32, "workspace")
+    call(entry, z, y, *extra, B, int(C), ld, float(label_smoothing), int(ignore_index), float(upstream), lo, dl, ld_out, db,
+         pr, ct, bl, _vp(ws), ws.numel(), _stream())
+
+
 def classify_loss(logits, labels, C, loss_out, pred, counters, bad_labels, dlogits=None, dbias=None, label_smoothing=0.0,
                   ignore_index=-100, upstream=1.0, workspace=None):
     """nn.CrossEntropyLoss(mean, ignore_index, label_smoothing) on the first C columns of logits f32 [B, ld] (the padded
@@ -860,21 +885,32 @@ def classify_loss(logits, labels, C, loss_out, pred, counters, bad_labels, dlogi
     counters i64 [2] += (correct, valid); bad_labels i32 [1] += labels outside [0, C) that are not ignore_index.  With
     dlogits bf16 [B, ld_out] (ld_out % 64 == 0): the zero-padded gradient scaled by upstream / n_valid; dbias f32 [C] += its
     column sums.  `workspace`: f32, at least vitssl_classify_loss_workspace_floats(B, C) (default: the shared scratch)."""
-    if logits is None or logits.dim() != 2 or not 2 <= int(C) <= logits.shape[1]:
-        raise L.VitsslError(f"classify_loss: expected logits [B, ld] with 2 <= C = {C} <= ld, got {None if logits is None else tuple(logits.shape)}")
-    B, ld = logits.shape
-    ld_out = 0
-    if dlogits is not None:
-        if dlogits.dim() != 2 or dlogits.shape[0] != B or dlogits.shape[1] % 64 != 0 or dlogits.shape[1] < C:
-            raise L.VitsslError(f"classify_loss: dlogits must be [{B}, ld_out] with ld_out % 64 == 0 and ld_out >= {C}, got {tuple(dlogits.shape)}")
-        ld_out = dlogits.shape[1]
-    z, y = _chk(logits, F32, "logits"), _chk(labels, I64, "labels", (B,))
-    lo, pr = _chk(loss_out, F32, "loss_out", (2,)), _chk(pred, I64, "pred", (B,))
-    ct, bl = _chk(counters, I64, "counters", (2,)), _chk(bad_labels, I32, "bad_labels", (1,))
-    dl, db = _opt(dlogits, BF16, "dlogits"), _opt(dbias, F32, "dbias", (C,))
-    need = int(L.lib().vitssl_classify_loss_workspace_floats(B, C))
-    ws = _tn_workspace(logits.device, need) if workspace is None else workspace      # shared scratch: launches on one stream are ordered
-    if workspace is not None:
-        _chk(ws, F32, "workspace")
-    call("vitssl_classify_loss", z, y, B, int(C), ld, float(label_smoothing), int(ignore_index), float(upstream), lo, dl, ld_out, db,
-         pr, ct, bl, _vp(ws), ws.numel(), _stream())
+    _classify("classify_loss", "vitssl_classify_loss", "vitssl_classify_loss_workspace_floats", (), logits, labels, C, loss_out, pred,
+              counters, bad_labels, dlogits, dbias, label_smoothing, ignore_index, upstream, workspace)
+
+
+# ---- Mixup / CutMix (include/vitssl_mixup.h) ----
+MIX_IP = 6
+MIX_COPY, MIX_BLEND, MIX_PASTE = 0, 1, 2
+
+
+def mix_batch(x, out, iparams, lam):
+    """out f32 [B,C,H,W] (another buffer than x) = x mixed row by row: iparams int32 [B,6] = (kind, partner, y0, y1, x0, x1),
+    lam f32 [B].  kind 0: out[i] = x[i]; 1: fmaf(lam, x[i], (1 - lam) * x[partner]); 2: x[partner] inside the box, x[i]
+    elsewhere.  A partner outside the batch is the row itself, a box is clamped to the image, any other kind copies."""
+    if x is None or x.dim() != 4:
+        raise L.VitsslError(f"mix_batch: expected x [B,C,H,W], got {None if x is None else tuple(x.shape)}")
+    B, Cn, H, W = x.shape
+    call("vitssl_mix_batch", _chk(x, F32, "x"), _chk(out, F32, "out", (B, Cn, H, W)), _chk(iparams, I32, "iparams", (B, MIX_IP)),
+         _chk(lam, F32, "lam", (B,)), B, Cn, H, W, _stream())
+
+
+def classify_loss_mix(logits, labels, partner, lam, C, loss_out, pred, counters, bad_labels, dlogits=None, dbias=None,
+                      label_smoothing=0.0, ignore_index=-100, upstream=1.0, workspace=None):
+    """`classify_loss` against the target lam[i] s(labels[i]) + (1 - lam[i]) s(labels[partner[i]]) of a mixed batch (s: the
+    label-smoothed one-hot row): partner int32 [B], lam f32 [B], everything else as there.  A row is ignored when either
+    label is ignore_index; it is ignored and counted in bad_labels when its partner is outside [0, B), a label is otherwise
+    outside [0, C) or lam is outside [0, 1].  counters[0] counts pred == labels[i], the row's own label."""
+    _classify("classify_loss_mix", "vitssl_classify_loss_mix", "vitssl_classify_loss_mix_workspace_floats",
+              ((partner, I32, "partner"), (lam, F32, "lam")), logits, labels, C, loss_out, pred, counters, bad_labels, dlogits, dbias,
+              label_smoothing, ignore_index, upstream, workspace)
