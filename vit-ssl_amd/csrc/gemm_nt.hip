@@ -32,6 +32,7 @@
 // peeling the under-filled last round into a SMALL-tile launch.
 #include <stdlib.h>
 #include <atomic>
+#include "../../include/vitssl_droppath.h"
 #include "common.h"
 
 namespace {
@@ -82,6 +83,8 @@ struct NtParams {
   const float* alpha2;  // second device scalar multiplied into the accumulators (1 / scale of a scaled gradient operand), or NULL
   const float* qscale;  // device scalar the values are multiplied by before they are quantised into out2 (NULL = 1)
   float* qamax;         // device slot that receives max |value| written to out2, before scaling (atomic max; NULL = none)
+  const float* rowscale;   // EPI_RESID_ROWS: the branch of row m is multiplied by rowscale[m / rows_per_group] (include/vitssl_droppath.h)
+  unsigned rows_per_group;
 #ifdef VITSSL_NT_STAMPS
   unsigned long long* stamps;   // diagnostic build only (tools/nt_stamps.py): [2: 100 MHz ticks, shader clocks][wg][2 wave groups][16 rounds][4]
 #endif
@@ -90,6 +93,10 @@ struct NtParams {
 // internal epilogue: fp32 output accumulated with atomics by the split-K slices (out0 is
 // zeroed by the launcher; slice 0 adds the bias)
 constexpr int EPI_F32_SPLITK = 100;
+// internal epilogue: VITSSL_EPI_RESID with a per-row scale of the branch (drop path, vitssl_gemm_bf16_nt_rows).  An epilogue id
+// of its own, so that the kernels of the plain residual launch are the instantiations they were.
+constexpr int EPI_RESID_ROWS = 101;
+constexpr bool epi_is_resid(int epi) { return epi == VITSSL_EPI_RESID || epi == EPI_RESID_ROWS; }
 
 // XOR applied to the 16-byte chunk index of tile row r (source side for the DMA, and on
 // the fragment reads): BK=64 (128-B rows) chunk ^ ((r>>1)&7); BK=32 (64-B rows)
@@ -294,7 +301,7 @@ __device__ __forceinline__ void nt_epilogue(const NtParams& p, f32x4 (&acc)[4][C
   };
   // one pair (32 columns) of a row tile of an fp32 image.  Residual-stream stores (read next by a different kernel) are
   // non-temporal (aux 2): interleaved A/B on MI355X, out-projection shape M = 50176, N = K = 768: 116 -> 97 us; neutral at K = 3072
-  constexpr int F32_AUX = EPI == VITSSL_EPI_RESID ? 2 : 0;
+  constexpr int F32_AUX = epi_is_resid(EPI) ? 2 : 0;
   auto store_f32_pair = [&](__amdgpu_buffer_rsrc_t rs, int i, int jp, const f32x4& v0, const f32x4& v1, const int (&nnp)[2]) {
     if (tls) {
       *(f32x4*)(xs + tw32) = v0;
@@ -314,9 +321,9 @@ __device__ __forceinline__ void nt_epilogue(const NtParams& p, f32x4 (&acc)[4][C
   const float qs = (Q8EPI && p.qscale) ? *p.qscale : 1.0f;
   float qmax = 0.f;                               // running max |value| of this lane's share of the e4m3 image
   if constexpr (EPI == VITSSL_EPI_BF16 || EPI == VITSSL_EPI_GELU || EPI == VITSSL_EPI_DGELU) rsOut0 = window(p.out0, 2);
-  if constexpr (EPI == VITSSL_EPI_F32 || EPI == VITSSL_EPI_RESID) rsOut0 = window(p.out0, 4);
+  if constexpr (EPI == VITSSL_EPI_F32 || epi_is_resid(EPI)) rsOut0 = window(p.out0, 4);
   if constexpr (EPI == VITSSL_EPI_GELU) rsOut1 = window(p.out1, 2);
-  if constexpr (EPI == VITSSL_EPI_RESID) rsAux = window(p.aux, 4);
+  if constexpr (epi_is_resid(EPI)) rsAux = window(p.aux, 4);
   if constexpr (EPI == VITSSL_EPI_DGELU) rsAux = window(p.aux, 2);
 
   // Column bookkeeping of this wave's 64 columns: pair jp covers tiles (2jp, 2jp+1), half h
@@ -326,7 +333,7 @@ __device__ __forceinline__ void nt_epilogue(const NtParams& p, f32x4 (&acc)[4][C
   f32x4 bias4[2][2];
   // dropout stream (common.h): the state word of group g = row * N/4 + col/4 is g * C0 + k0 = (row term) + (column term);
   // the row term advances by a launch constant per 16-row tile, the column terms are four lane constants
-  constexpr bool DROPS = EPI == VITSSL_EPI_GELU || EPI == VITSSL_EPI_RESID;
+  constexpr bool DROPS = EPI == VITSSL_EPI_GELU || epi_is_resid(EPI);
   unsigned a0col[2][2];
   const unsigned a0rowstep = 16u * (unsigned)(p.N >> 2) * DROP_C0;
   unsigned a0row = 0;
@@ -359,17 +366,27 @@ __device__ __forceinline__ void nt_epilogue(const NtParams& p, f32x4 (&acc)[4][C
   // is computed and stored.  The vector-memory counter retires in issue order, so in the plain order (loads of g+1 behind the
   // stores of g) the wait for a group's operands also waited for the previous group's stores to be acknowledged by the L2 --
   // one load round trip plus one store round trip per group, 7 times per tile for the 224-row residual epilogue.
-  constexpr bool PREF = TLS && (EPI == VITSSL_EPI_RESID || EPI == VITSSL_EPI_DGELU);
+  constexpr bool PREF = TLS && (epi_is_resid(EPI) || EPI == VITSSL_EPI_DGELU);
   // (with the prefetch two groups of operands are alive at once: 1 row per group for the residual lines, 2 for g')
-  constexpr int RG = EPI == VITSSL_EPI_RESID ? (PREF ? 1 : (MI % 2 == 0 ? 2 : 1))
+  constexpr int RG = epi_is_resid(EPI) ? (PREF ? 1 : (MI % 2 == 0 ? 2 : 1))
                      : EPI == VITSSL_EPI_DGELU ? (PREF ? 2 : (MI % 4 == 0 ? 4 : 2))
                                                : 4;
   constexpr int NB = PREF ? 2 : 1;
   f32x4 res[NB][RG][2][2];   // RESID: residual stream (line layout until used)
   u32x4 raw[NB][RG][2];      // DGELU, 16-byte form: g' as loaded
+  float rsc[NB][RG];         // RESID_ROWS: the scale of this lane's accumulator row (row tile ig + ii), requested with the group's residual
   auto load_group = [&](const int ig, const int b) {
     const int cnt = MI - ig < RG ? MI - ig : RG;
-    if constexpr (EPI == VITSSL_EPI_RESID) {
+    if constexpr (EPI == EPI_RESID_ROWS) {
+#pragma unroll
+      for (int ii = 0; ii < RG; ++ii) {
+        if (ii >= cnt) continue;
+        // rows past M read entry 0 (their stores are dropped); m < M < 2^31 / K, and groups * rows_per_group == M keeps the index inside the table
+        const long long mr = m0 + wm * CFG::WROWS + (ig + ii) * 16 + (lane & 15);
+        rsc[b][ii] = p.rowscale[mr < p.M ? (unsigned)mr / p.rows_per_group : 0u];
+      }
+    }
+    if constexpr (epi_is_resid(EPI)) {
 #pragma unroll
       for (int ii = 0; ii < RG; ++ii)
 #pragma unroll
@@ -556,13 +573,29 @@ __device__ __forceinline__ void nt_epilogue(const NtParams& p, f32x4 (&acc)[4][C
           }
         } else if constexpr (EPI == VITSSL_EPI_F32) {
           store_f32_pair(rsOut0, i, jp, v[0], v[1], nn[jp]);
-        } else if constexpr (EPI == VITSSL_EPI_RESID) {
+        } else if constexpr (epi_is_resid(EPI)) {
           if (tls) {                              // the pair's residual lines -> accumulator layout (inverse of store_f32_pair's path)
             *(f32x4*)(xs + tr32a) = res[gb][ii][jp][0];
             *(f32x4*)(xs + tr32a + 1024) = res[gb][ii][jp][1];
             res[gb][ii][jp][0] = *(const f32x4*)(xs + tw32);
             res[gb][ii][jp][1] = *(const f32x4*)(xs + (tw32 ^ 64u));
           }
+          if constexpr (EPI == EPI_RESID_ROWS) {
+            // the row's scale times the dropout scale (1 when dropout is off: a table of ones gives the plain launch's bits); a
+            // dropped row (scale 0) stores the residual itself, whatever the accumulator holds
+            const float rs = rsc[gb][ii];
+            const float cs = p.drop_on ? rs * p.dk.scale : rs;
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+              bool keep[4] = {true, true, true, true};
+              if (p.drop_on) drop_keep4(p.dk, drop_words_a0(p.dk, a0row + (unsigned)i * a0rowstep + a0col[jp][h]), keep);
+#pragma unroll
+              for (int r = 0; r < 4; ++r) {
+                const float t = fmaf(keep[r] ? v[h][r] : 0.f, cs, res[gb][ii][jp][h][r]);
+                v[h][r] = rs == 0.f ? res[gb][ii][jp][h][r] : t;
+              }
+            }
+          } else {
 #pragma unroll
           for (int h = 0; h < 2; ++h) {
             if (p.drop_on) {
@@ -573,6 +606,7 @@ __device__ __forceinline__ void nt_epilogue(const NtParams& p, f32x4 (&acc)[4][C
             } else {
               v[h] += res[gb][ii][jp][h];
             }
+          }
           }
           store_f32_pair(rsOut0, i, jp, v[0], v[1], nn[jp]);
         } else {   // VITSSL_EPI_EMBED (one launch per step: plain addressing)
@@ -876,7 +910,7 @@ constexpr int nt_epi_vmem_ops() {
   return EPI == VITSSL_EPI_BF16 ? 2 * MI
          : (EPI == VITSSL_EPI_GELU || EPI == VITSSL_EPI_DGELU) ? (F8 ? 3 * MI : 4 * MI)
          : EPI == VITSSL_EPI_F32 ? 4 * MI
-         : EPI == VITSSL_EPI_RESID ? 8 * MI
+         : epi_is_resid(EPI) ? 8 * MI
          : 0;
 }
 
@@ -1246,9 +1280,10 @@ int launch_pp(NtParams p, hipStream_t s) {
   static VsEnvInt stagger_mask_knob;
   const int stagger_mask = stagger_mask_knob.get("VITSSL_NT_STAGGER_EPIS", STAGGER_EPIS);
   const float epi_us = EPI == VITSSL_EPI_BF16 ? 2.f : EPI == VITSSL_EPI_GELU ? 7.f : EPI == VITSSL_EPI_DGELU ? 5.f
-                       : EPI == VITSSL_EPI_RESID ? 8.f : 4.f;
+                       : epi_is_resid(EPI) ? 8.f : 4.f;
   const float tile_us = (float)(p.K * p.esz / 128) * 1.45f * (float)CFG::MI / 8.f + epi_us;
-  p.stagger = ((stagger_mask >> EPI) & 1) ? (int)(stagger_scale * tile_us * 100.f) : 0;
+  constexpr int MASK_BIT = EPI == EPI_RESID_ROWS ? VITSSL_EPI_RESID : EPI;      // the rows form staggers as the residual epilogue does
+  p.stagger = ((stagger_mask >> MASK_BIT) & 1) ? (int)(stagger_scale * tile_us * 100.f) : 0;
   nt_note_grid((int)grid);
   hipLaunchKernelGGL((gemm_nt_pp_kernel<EPI, CFG, F8>), dim3((unsigned)grid), dim3(CFG::THREADS), LDS, s, p);
   VS_CHECK_LAUNCH("gemm_nt_pp");
@@ -1457,8 +1492,8 @@ static unsigned long long* g_nt_stamps = nullptr;
 extern "C" void vitssl_debug_nt_stamps(void* buf) { g_nt_stamps = (unsigned long long*)buf; }
 #endif
 
-static int gemm_nt_entry(const vitssl_gemm_t* g, int esz, const vitssl_fp8_gemm_t* q, void* stream) {
-  const char* who = esz == 1 ? "gemm_fp8_nt" : "gemm_nt";
+static int gemm_nt_entry(const vitssl_gemm_t* g, int esz, const vitssl_fp8_gemm_t* q, void* stream, const vitssl_rowscale_t* rows = nullptr) {
+  const char* who = rows ? "gemm_nt_rows" : esz == 1 ? "gemm_fp8_nt" : "gemm_nt";
   VS_CHECK_ARG(g && g->A && g->B && (g->out0 || (esz == 1 && g->epilogue == VITSSL_EPI_DGELU && q && q->out_fp8)), "%s: null operand", who);
   VS_CHECK_ARG(g->M > 0 && g->N > 0 && g->K > 0, "%s: empty problem M=%lld N=%d K=%d", who, (long long)g->M, g->N, g->K);
   VS_CHECK_ARG(g->K % (128 / esz) == 0, "%s: K=%d must be a multiple of %d", who, g->K, 128 / esz);
@@ -1491,6 +1526,8 @@ static int gemm_nt_entry(const vitssl_gemm_t* g, int esz, const vitssl_fp8_gemm_
   p.out2 = q ? q->out_fp8 : nullptr;
   p.qscale = q ? q->out_scale : nullptr;
   p.qamax = q ? q->out_amax : nullptr;
+  p.rowscale = nullptr;
+  p.rows_per_group = 1;
 #ifdef VITSSL_NT_STAMPS
   p.stamps = g_nt_stamps;
 #endif
@@ -1499,6 +1536,16 @@ static int gemm_nt_entry(const vitssl_gemm_t* g, int esz, const vitssl_fp8_gemm_
                "%s: column sums are built for the BF16 / F32 / DGELU epilogues only", who);
   VS_CHECK_ARG(!p.drop_on || (unsigned long long)g->M * (unsigned long long)g->N < (1ull << 34),
                "%s: dropout over %lld x %d elements: the stream's group counter is 32 bits (M * N < 2^34)", who, (long long)g->M, g->N);
+  if (rows) {      // vitssl_gemm_bf16_nt_rows: the residual epilogue with a per-row scale of the branch
+    VS_CHECK_ARG(g->epilogue == VITSSL_EPI_RESID, "%s: row scales are built for VITSSL_EPI_RESID only, got epilogue %d", who, g->epilogue);
+    VS_CHECK_ARG(g->aux, "%s: EPI_RESID needs aux (residual)", who);
+    VS_CHECK_ARG(rows->scale && rows->groups > 0 && rows->rows_per_group > 0, "%s: row scales need scale, groups > 0 and rows_per_group > 0", who);
+    VS_CHECK_ARG(rows->groups * (int64_t)rows->rows_per_group == g->M, "%s: groups (%lld) * rows_per_group (%d) must equal M (%lld)", who,
+                 (long long)rows->groups, rows->rows_per_group, (long long)g->M);
+    p.rowscale = rows->scale;
+    p.rows_per_group = (unsigned)rows->rows_per_group;
+    return launch_nt<EPI_RESID_ROWS>(p, s);
+  }
   switch (g->epilogue) {
     case VITSSL_EPI_BF16: return launch_nt<VITSSL_EPI_BF16>(p, s);
     case VITSSL_EPI_F32: return launch_nt<VITSSL_EPI_F32>(p, s);
@@ -1523,6 +1570,11 @@ static int gemm_nt_entry(const vitssl_gemm_t* g, int esz, const vitssl_fp8_gemm_
 }
 
 extern "C" int vitssl_gemm_bf16_nt(const vitssl_gemm_t* g, void* stream) { return gemm_nt_entry(g, 2, nullptr, stream); }
+
+extern "C" int vitssl_gemm_bf16_nt_rows(const vitssl_gemm_t* g, const vitssl_rowscale_t* rows, void* stream) {
+  VS_CHECK_ARG(rows, "gemm_nt_rows: null row scales (vitssl_gemm_bf16_nt is the launch without them)");
+  return gemm_nt_entry(g, 2, nullptr, stream, rows);
+}
 
 extern "C" int vitssl_gemm_fp8_nt(const vitssl_gemm_t* g, const vitssl_fp8_gemm_t* q, void* stream) {
   VS_CHECK_ARG(g && (g->epilogue == VITSSL_EPI_BF16 || g->epilogue == VITSSL_EPI_F32 || g->epilogue == VITSSL_EPI_GELU ||

@@ -10,6 +10,7 @@
 // column sum are accumulated in registers across the rows a wave visits, reduced
 // across the block's 4 waves in LDS and added to global with one atomic per column
 // per block.
+#include "../../include/vitssl_droppath.h"
 #include "common.h"
 
 namespace {
@@ -105,21 +106,26 @@ constexpr int ln_bwd_blocks(int V, bool has_ln, bool has_cs) {
 // 28.9 us at M = 25088; interleaved A/B, MI355X).  The caller passes rows = row pairs and cols = 2 x the row length; a slot
 // (lane, v) belongs to the pair's second row where lane + 64 v >= cols / 8, and the row statistics are reduced per row.  (The
 // same form of the FORWARD kernel was 17 % slower than one row per wave, 24.5 against 21.0 us, and is not built.)
-template <int V, bool HAS_LN, bool HAS_CS, bool Q8 = false, bool PAIR = false>
-__global__ __launch_bounds__(LN_THREADS, ln_bwd_blocks(V, HAS_LN, HAS_CS)) void ln_bwd_kernel(const bf16_t* __restrict__ dy, const float* __restrict__ x,
+// ROWS (drop path, include/vitssl_droppath.h): the bf16 operand of row r is multiplied once more, by rowscale[r / rows_per_group];
+// g_out, dgamma and dbeta are not.  An instantiation of its own: the plain kernels are what they were.  (The row-pair form without
+// column sums spills at 3 workgroups per CU once it also holds the pair's two scales: it takes the budget of the form with them.)
+template <int V, bool HAS_LN, bool HAS_CS, bool Q8 = false, bool PAIR = false, bool ROWS = false>
+__global__ __launch_bounds__(LN_THREADS, ln_bwd_blocks(V, HAS_LN, HAS_CS || (ROWS && PAIR))) void ln_bwd_kernel(const bf16_t* __restrict__ dy, const float* __restrict__ x,
                                                             const float* __restrict__ mean, const float* __restrict__ rstd,
                                                             const float* __restrict__ gamma, const float* g_res,
                                                             float* g_out, bf16_t* __restrict__ gm, float* __restrict__ dgamma,
                                                             float* __restrict__ dbeta, float* __restrict__ gm_colsum,
                                                             DropKey dk, int drop_on, long long rows, int cols,
                                                             unsigned char* __restrict__ gm8 = nullptr,
-                                                            const float* __restrict__ qscale = nullptr, float* qamax = nullptr) {
+                                                            const float* __restrict__ qscale = nullptr, float* qamax = nullptr,
+                                                            const float* __restrict__ rowscale = nullptr, unsigned rows_per_group = 1) {
   __shared__ __attribute__((aligned(16))) float red[4][V * 256];   // [wave][col]
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   const int c4n = cols >> 2;
   const int c4h = PAIR ? c4n >> 1 : c4n;            // float4 per row
   static_assert(!PAIR || (HAS_LN && !Q8), "row pairs are built for the LayerNorm form with a bf16 image");
+  static_assert(!ROWS || !Q8, "row scales are built for the bf16 image");
   f32x4 g[V], acc_dg[V], acc_db[V], acc_cs[V];
   bool hi[V];                                       // PAIR: the slot holds columns of the pair's second row
 #pragma unroll
@@ -138,8 +144,13 @@ __global__ __launch_bounds__(LN_THREADS, ln_bwd_blocks(V, HAS_LN, HAS_CS)) void 
   f32x4 nx[V], ngr[V];
   u32x2 ndy[V];
   float nmu = 0.f, nrs = 0.f, nmuB = 0.f, nrsB = 0.f;
+  float nsc = 1.f, nscB = 1.f;                      // ROWS: scale of the row (PAIR: of the pair's two rows); rows < 2^31
   auto fetch = [&](long long row) {
     if (!HAS_LN || row >= rows) return;
+    if constexpr (ROWS) {
+      nsc = rowscale[(PAIR ? 2u * (unsigned)row : (unsigned)row) / rows_per_group];
+      if constexpr (PAIR) nscB = rowscale[(2u * (unsigned)row + 1u) / rows_per_group];
+    }
     if constexpr (PAIR) {
       nmu = mean[2 * row];
       nrs = rstd[2 * row];
@@ -163,6 +174,15 @@ __global__ __launch_bounds__(LN_THREADS, ln_bwd_blocks(V, HAS_LN, HAS_CS)) void 
   fetch((long long)blockIdx.x * 4 + wave);
   for (long long row = (long long)blockIdx.x * 4 + wave; row < rows; row += row_step) {
     f32x4 dx[V];
+    float sc = 1.f, scB = 1.f;
+    // (mask + cast form: no prefetch to ride on.  A row belongs to one wave, so the index is made wave-uniform and the scale comes
+    // through the scalar cache: as a vector load at the loop head it made every row wait for the previous row's stores first,
+    // +16 us at 50432 x 768)
+    if constexpr (ROWS && !HAS_LN) sc = rowscale[__builtin_amdgcn_readfirstlane((unsigned)row / rows_per_group)];
+    if constexpr (ROWS && HAS_LN) {
+      sc = nsc;
+      scB = nscB;
+    }
     if constexpr (HAS_LN) {
       const float mu = nmu, rs = nrs, muB = nmuB, rsB = nrsB;
       f32x4 xh[V], gr[V];
@@ -229,6 +249,7 @@ __global__ __launch_bounds__(LN_THREADS, ln_bwd_blocks(V, HAS_LN, HAS_CS)) void 
 #pragma unroll
             for (int r = 0; r < 4; ++r) o[r] = keep[r] ? o[r] * dk.scale : 0.f;
           }
+          if constexpr (ROWS) o *= hi[v] ? scB : sc;
           if (gm) {                              // fp8 path: the bf16 image is optional
             u32x2 w = {pack_bf2(o[0], o[1]), pack_bf2(o[2], o[3])};
             *(u32x2*)(gm + row * cols + 4 * c4) = w;
@@ -294,15 +315,55 @@ inline int ln_grid(long long rows, bool fwd = false, int cols = 1024) {
   return (int)g;
 }
 
+// The launches of launch_ln_bwd_parts below for the ROWS instantiations: the same column-count paths, the 384-column row pairs
+// included, the same grids (so the slot rows of the sums are laid out as launch_ln_bwd expects).
+template <bool HAS_LN>
+int launch_ln_bwd_rows(const void* dy, const float* x, const float* mean, const float* rstd, const float* gamma, const float* g_res,
+                       float* g_out, void* gm, float* dgamma, float* dbeta, float* gm_colsum, DropKey dk, int on, int64_t rows, int cols,
+                       hipStream_t s, vitssl_rowscale_t rsc) {
+  const unsigned rpg = (unsigned)rsc.rows_per_group;
+#define VS_LNR(V, CS, PAIR, GRID, ROWS_, COLS_)                                                                                     \
+  hipLaunchKernelGGL((ln_bwd_kernel<V, HAS_LN, CS, false, PAIR, true>), dim3(GRID), dim3(LN_THREADS), 0, s, (const bf16_t*)dy, x, mean, \
+                     rstd, gamma, g_res, g_out, (bf16_t*)gm, dgamma, dbeta, gm_colsum, dk, on, (long long)(ROWS_), COLS_,             \
+                     (unsigned char*)nullptr, (const float*)nullptr, (float*)nullptr, rsc.scale, rpg)
+  if constexpr (HAS_LN) {
+    if (cols == 384 && (rows & 1) == 0) {            // two rows per wave (PAIR)
+      const int pgrid = ln_grid(rows / 2, false, 768);
+      if (gm_colsum) VS_LNR(3, true, true, pgrid, rows / 2, 768);
+      else VS_LNR(3, false, true, pgrid, rows / 2, 768);
+      VS_CHECK_LAUNCH("layernorm_bwd_rows");
+      return VITSSL_OK;
+    }
+  }
+  const int grid = ln_grid(rows, false, cols);
+#define VS_LNRV(V)                                          \
+  do {                                                      \
+    if (gm_colsum) VS_LNR(V, true, false, grid, rows, cols); \
+    else VS_LNR(V, false, false, grid, rows, cols);          \
+  } while (0)
+  if (cols <= 256) VS_LNRV(1);
+  else if (cols <= 512) VS_LNRV(2);
+  else if (cols <= 768) VS_LNRV(3);
+  else if (cols <= 1024) VS_LNRV(4);
+  else VS_LNRV(8);
+#undef VS_LNRV
+#undef VS_LNR
+  VS_CHECK_LAUNCH("layernorm_bwd_rows");
+  return VITSSL_OK;
+}
+
 template <bool HAS_LN, bool Q8 = false>
 int launch_ln_bwd_parts(const void* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
                   const float* g_res, float* g_out, void* gm, float* dgamma, float* dbeta, float* gm_colsum,
                   vitssl_dropout_t drop, int64_t rows, int cols, hipStream_t s, void* gm8 = nullptr,
-                  const float* qscale = nullptr, float* qamax = nullptr) {
+                  const float* qscale = nullptr, float* qamax = nullptr, const vitssl_rowscale_t* rsc = nullptr) {
   DropKey dk = make_drop_key(drop);
   const int on = dk.thr != 0;
   VS_CHECK_ARG(!on || (unsigned long long)rows * (unsigned long long)cols < (1ull << 34),
                "layernorm_bwd / grad_mask_cast: the dropout stream's group counter is 32 bits (rows * cols < 2^34)");
+  if constexpr (!Q8) {
+    if (rsc) return launch_ln_bwd_rows<HAS_LN>(dy, x, mean, rstd, gamma, g_res, g_out, gm, dgamma, dbeta, gm_colsum, dk, on, rows, cols, s, *rsc);
+  }
   if constexpr (HAS_LN && !Q8) {
     if (cols == 384 && (rows & 1) == 0) {            // two rows per wave (PAIR)
       const int pgrid = ln_grid(rows / 2, false, 768);
@@ -346,20 +407,20 @@ template <bool HAS_LN, bool Q8 = false>
 int launch_ln_bwd(const void* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
                   const float* g_res, float* g_out, void* gm, float* dgamma, float* dbeta, float* gm_colsum,
                   vitssl_dropout_t drop, int64_t rows, int cols, float* workspace, int64_t workspace_floats, hipStream_t s,
-                  void* gm8 = nullptr, const float* qscale = nullptr, float* qamax = nullptr) {
+                  void* gm8 = nullptr, const float* qscale = nullptr, float* qamax = nullptr, const vitssl_rowscale_t* rsc = nullptr) {
   const bool pair = HAS_LN && !Q8 && cols == 384 && (rows & 1) == 0;
   const int grid = pair ? ln_grid(rows / 2, false, 768) : ln_grid(rows, false, cols);
   const long long slab = (long long)grid * cols;
   if (!((HAS_LN && (dgamma || dbeta)) || gm_colsum))
     return launch_ln_bwd_parts<HAS_LN, Q8>(dy, x, mean, rstd, gamma, g_res, g_out, gm, nullptr, nullptr, nullptr, drop, rows, cols, s, gm8,
-                                           qscale, qamax);
+                                           qscale, qamax, rsc);
   float* parts = vs_sum_parts(workspace, workspace_floats, 3 * slab, rows, cols, "layernorm_bwd / grad_mask_cast");
   if (!parts) return VITSSL_ERR_ARG;
   float* pg = HAS_LN && dgamma ? parts : nullptr;
   float* pb = HAS_LN && dbeta ? parts + slab : nullptr;
   float* pc = gm_colsum ? parts + 2 * slab : nullptr;
   const int rc = launch_ln_bwd_parts<HAS_LN, Q8>(dy, x, mean, rstd, gamma, g_res, g_out, gm, pg, pb, pc, drop, rows, cols, s, gm8,
-                                                 qscale, qamax);
+                                                 qscale, qamax, rsc);
   if (rc != VITSSL_OK) return rc;
   return vs_reduce_parts(VsSums{{pg ? dgamma : nullptr, pb ? dbeta : nullptr, pc ? gm_colsum : nullptr}, {pg, pb, pc}}, grid, cols,
                          cols, s);
@@ -440,4 +501,34 @@ extern "C" int vitssl_grad_mask_cast(const float* g, void* gm_bf16, float* gm_co
   VS_CHECK_ARG(rows > 0 && cols > 0 && cols % 4 == 0 && cols <= 2048, "grad_mask_cast: cols=%d must be a multiple of 4 and <= 2048", cols);
   return launch_ln_bwd<false>(nullptr, nullptr, nullptr, nullptr, nullptr, g, nullptr, gm_bf16, nullptr, nullptr,
                               gm_colsum, drop, rows, cols, workspace, workspace_floats, (hipStream_t)stream);
+}
+
+// ---- drop path: the same two contracts with the bf16 operand scaled per row (include/vitssl_droppath.h) ----------------------
+static int check_rowscale(const char* who, const vitssl_rowscale_t* r, int64_t rows) {
+  VS_CHECK_ARG(r && r->scale && r->groups > 0 && r->rows_per_group > 0, "%s: row scales need scale, groups > 0 and rows_per_group > 0", who);
+  VS_CHECK_ARG(rows < (1ll << 31), "%s: rows = %lld outside rows < 2^31", who, (long long)rows);
+  VS_CHECK_ARG(r->groups * (int64_t)r->rows_per_group == rows, "%s: groups (%lld) * rows_per_group (%d) must equal rows (%lld)", who,
+               (long long)r->groups, r->rows_per_group, (long long)rows);
+  return VITSSL_OK;
+}
+
+extern "C" int vitssl_layernorm_bwd_rows(const void* dy_bf16, const float* x, const float* mean, const float* rstd,
+                                         const float* gamma, const float* g_res, float* g_out, void* gm_bf16, float* dgamma,
+                                         float* dbeta, float* gm_colsum, vitssl_dropout_t drop, const vitssl_rowscale_t* rowscale,
+                                         int64_t rows, int cols, float* workspace, int64_t workspace_floats, void* stream) {
+  VS_CHECK_ARG(dy_bf16 && x && mean && rstd && gamma && g_out && dgamma && dbeta && gm_bf16, "layernorm_bwd_rows: null pointer");
+  VS_CHECK_ARG(rows > 0 && cols > 0 && cols % 4 == 0 && cols <= 2048, "layernorm_bwd_rows: cols=%d must be a multiple of 4 and <= 2048", cols);
+  if (int rc = check_rowscale("layernorm_bwd_rows", rowscale, rows)) return rc;
+  return launch_ln_bwd<true>(dy_bf16, x, mean, rstd, gamma, g_res, g_out, gm_bf16, dgamma, dbeta, gm_colsum, drop, rows, cols,
+                             workspace, workspace_floats, (hipStream_t)stream, nullptr, nullptr, nullptr, rowscale);
+}
+
+extern "C" int vitssl_grad_mask_cast_rows(const float* g, void* gm_bf16, float* gm_colsum, vitssl_dropout_t drop,
+                                          const vitssl_rowscale_t* rowscale, int64_t rows, int cols, float* workspace,
+                                          int64_t workspace_floats, void* stream) {
+  VS_CHECK_ARG(g && gm_bf16, "grad_mask_cast_rows: null pointer");
+  VS_CHECK_ARG(rows > 0 && cols > 0 && cols % 4 == 0 && cols <= 2048, "grad_mask_cast_rows: cols=%d must be a multiple of 4 and <= 2048", cols);
+  if (int rc = check_rowscale("grad_mask_cast_rows", rowscale, rows)) return rc;
+  return launch_ln_bwd<false>(nullptr, nullptr, nullptr, nullptr, nullptr, g, nullptr, gm_bf16, nullptr, nullptr, gm_colsum, drop,
+                              rows, cols, workspace, workspace_floats, (hipStream_t)stream, nullptr, nullptr, nullptr, rowscale);
 }

@@ -100,6 +100,9 @@ def build_model(config):
     side = cfg_get(config, "data", "img_size")
     backbone = dict(input_shape=(m("in_channels"), side, side), patch_size=m("patch_size"), embed_dim=m("embed_dim"),
                     num_blocks=m("num_blocks"), num_heads=m("num_heads"), mlp_dim=m("mlp_dim"), dropout=m("dropout"))
+    rate = cfg_get(config, "model", "drop_path_rate")      # optional: stochastic depth (absent or 0: the models as they always were)
+    if rate:
+        backbone["drop_path_rate"] = float(rate)
     makers = {
         "supervised": lambda: ViT(num_classes=m("num_classes"), **backbone),
         "simmim": lambda: SimMIMViT(mask_ratio=m("mask_ratio"), **backbone),

@@ -365,7 +365,7 @@ class _StackFn(Function):
         runner.stack.check_tokens(T)
         st = runner.store
         st.refresh_weights()
-        seed = R.next_seed() if (training and runner.stack.p > 0) else 0
+        seed = R.next_seed() if runner.stack.needs_seed(training) else 0
         slot = runner.next_slot() if need else "nograd"
         y, probs = runner.stack.forward(R.as_f32(x).reshape(Bn * T, D), Bn, T, training, seed, save=need, slot=slot,
                                         return_attn=return_attn)
@@ -394,10 +394,10 @@ class _StackFn(Function):
 class StackRunner:
     """A private FlatStore + EncoderStack for a module that owns encoder blocks."""
 
-    def __init__(self, module, block_prefixes, D, H, Fd, p, device):
+    def __init__(self, module, block_prefixes, D, H, Fd, p, device, drop_path=None):
         self.module = module
         self.store = R.FlatStore(module, device)
-        self.stack = R.EncoderStack(self.store, block_prefixes, D, H, Fd, p)
+        self.stack = R.EncoderStack(self.store, block_prefixes, D, H, Fd, p, drop_path=drop_path)
         self.device = device
         self._slots = 0
         self._gen = 0

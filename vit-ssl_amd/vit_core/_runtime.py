@@ -12,7 +12,7 @@ if _PKG not in sys.path:
 
 from vitssl_hip import _lib as L  # noqa: E402
 from vitssl_hip import ops  # noqa: E402
-from vitssl_hip.engine import EncoderStack, FlatStore, GradReducer, PatchGeometry, Workspace, _round_up  # noqa: E402,F401
+from vitssl_hip.engine import EncoderStack, FlatStore, GradReducer, PatchGeometry, Workspace, _round_up, drop_path_rates  # noqa: E402,F401
 
 BF16 = torch.bfloat16
 F32 = torch.float32

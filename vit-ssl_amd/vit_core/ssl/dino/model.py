@@ -28,9 +28,12 @@ class ViTBackbone(nn.Module):
     (reference: ssl/dino/model.py:12-45).  Parameter container inside DINOViT; usable on its
     own through the modules' stand-alone paths."""
 
-    def __init__(self, num_blocks, input_shape, embed_dim, patch_size, num_heads=8, mlp_dim=3072, dropout=0.1):
+    def __init__(self, num_blocks, input_shape, embed_dim, patch_size, num_heads=8, mlp_dim=3072, dropout=0.1,
+                 drop_path_rate: float = 0.0):
         super().__init__()
-        self.encoder_blocks = nn.ModuleList([EncoderBlock(embed_dim, num_heads, mlp_dim, dropout) for _ in range(num_blocks)])
+        self.drop_path_rate = float(drop_path_rate)      # read by the owning runtime (DINOViT: the student's only); not a parameter
+        rates = R.drop_path_rates(self.drop_path_rate, num_blocks)      # (the blocks run one by one when the backbone is called on its own)
+        self.encoder_blocks = nn.ModuleList([EncoderBlock(embed_dim, num_heads, mlp_dim, dropout, drop_path=r) for r in rates])
         self.patch_embedding = DynamicPatchEmbedding(input_shape, embed_dim, patch_size)
 
     def forward(self, x: torch.Tensor, return_attn=False):
@@ -57,7 +60,8 @@ class _DINORuntime:
                          cls=pre + "patch_embedding.cls_token", pos=pre + "patch_embedding.positional_embedding")
             self.stores[who] = st
             self.bb[who] = BackboneRuntime(st, pre, names, model.num_blocks, C, P, grid, D, model.num_heads, model.mlp_dim,
-                                           model.dropout_p)
+                                           model.dropout_p,
+                                           drop_path=R.drop_path_rates(model.drop_path_rate, model.num_blocks) if who == "student" else None)
             self.head[who] = HeadRuntime(st, f"{who}_head.", D, K)
         if self.stores["teacher"].numel != self.stores["student"].numel:
             raise L.VitsslError("DINOViT: teacher and student parameter layouts differ")
@@ -77,7 +81,7 @@ class _DINORuntime:
         dev = views[0].device
         glob = torch.cat([R.as_f32(v) for v in views[:G]], dim=0)
         loc = torch.cat([R.as_f32(v) for v in views[G:]], dim=0) if V > G else None
-        seed = R.next_seed() if (training and m.dropout_p > 0) else 0
+        seed = R.next_seed() if self.bb["student"].stack.needs_seed(training) else 0
         student = torch.empty(V * B, self.K, dtype=F32, device=dev)
         fg, _ = self.bb["student"].forward(glob, training, seed, save=save, slot="g", dynamic=True)
         self.head["student"].forward(fg, student[:G * B], save=save, slot="g")
@@ -156,6 +160,7 @@ class DINOViT(nn.Module):
         dropout: float = 0.1,
         output_dim: int = 65536,
         center_momentum: float = 0.9,
+        drop_path_rate: float = 0.0,
     ):
         super().__init__()
         self.center_momentum = center_momentum
@@ -172,6 +177,9 @@ class DINOViT(nn.Module):
         self.input_shape = tuple(input_shape)
         self.num_blocks, self.embed_dim, self.patch_size = num_blocks, embed_dim, patch_size
         self.num_heads, self.mlp_dim, self.dropout_p, self.output_dim = num_heads, mlp_dim, float(dropout), output_dim
+        # stochastic depth of the STUDENT stack (linspace(0, rate, num_blocks)); the teacher never drops a path
+        self.drop_path_rate = float(drop_path_rate)
+        R.drop_path_rates(self.drop_path_rate, num_blocks)        # a rate outside [0, 1) is a ValueError here
         self._rt = None
 
     # ------------------------------------------------------------------ runtime

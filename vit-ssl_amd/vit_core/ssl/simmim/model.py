@@ -39,7 +39,8 @@ class _SimMIMRuntime:
         self.store = R.FlatStore(model, device)
         st = self.store
         prefixes = [f"encoder_blocks.{i}." for i in range(len(model.encoder_blocks))]
-        self.stack = R.EncoderStack(st, prefixes, self.D, model.num_heads, model.mlp_dim, model.dropout_p)
+        self.stack = R.EncoderStack(st, prefixes, self.D, model.num_heads, model.mlp_dim, model.dropout_p,
+                                    drop_path=R.drop_path_rates(model.drop_path_rate, len(prefixes)))
         if self.geo.native:
             st.register_weight("proj", lambda: st.view("projection.weight", (self.D, self.Pd)), transposed_too=False)
             st.register_weight("head", lambda: st.view("simmim_head.weight", (self.Pd, self.D)))
@@ -119,7 +120,7 @@ class _SimMIMRuntime:
             if mask_cpu is None:
                 mask_cpu = draw_mask(B, self.N, self.model.mask_ratio)      # host RNG first (reference order)
             prepared = self.prepare_mask(mask_cpu, dev)
-        seed = R.next_seed() if (training and self.stack.p > 0) else 0
+        seed = R.next_seed() if self.stack.needs_seed(training) else 0
         idx_d, inv_d, mask_d = prepared
         Mm = idx_d.numel()
 
@@ -235,6 +236,7 @@ class SimMIMViT(nn.Module):
         mlp_dim: int = 3072,
         dropout: float = 0.1,
         mask_ratio: float = 0.6,
+        drop_path_rate: float = 0.0,
     ):
         super().__init__()
         self.encoder_blocks = nn.ModuleList(
@@ -250,6 +252,8 @@ class SimMIMViT(nn.Module):
         self.input_shape = tuple(input_shape)
         self.embed_dim, self.patch_size = embed_dim, patch_size
         self.num_heads, self.mlp_dim, self.dropout_p = num_heads, mlp_dim, float(dropout)
+        self.drop_path_rate = float(drop_path_rate)               # stochastic depth, linspace(0, rate, num_blocks); not a parameter
+        R.drop_path_rates(self.drop_path_rate, num_blocks)        # a rate outside [0, 1) is a ValueError here
         if input_shape[1] % patch_size != 0 or input_shape[2] % patch_size != 0:
             raise ValueError(
                 f"Image dimensions H={input_shape[1]}, W={input_shape[2]} must be divisible by patch_size={patch_size}")

@@ -32,7 +32,8 @@ class _ViTRuntime:
         self.bb = BackboneRuntime(
             st, "", dict(weight="patch_embedding.conv.weight", bias="patch_embedding.conv.bias",
                          cls="patch_embedding.cls_token", pos="patch_embedding.positional_embedding"),
-            len(model.encoder_blocks), C, P, (Hh // P, Ww // P), self.D, model.num_heads, model.mlp_dim, model.dropout_p)
+            len(model.encoder_blocks), C, P, (Hh // P, Ww // P), self.D, model.num_heads, model.mlp_dim, model.dropout_p,
+            drop_path=R.drop_path_rates(model.drop_path_rate, len(model.encoder_blocks)))
         self.ncls = model.num_classes
         self.rec = None                   # what the last saving forward keeps of the head for its backward
         self.save_gen = 0                 # id of that forward
@@ -99,7 +100,7 @@ class _ViTRuntime:
         st, g = self.store, self.ws.get
         tag = "head." if save else "head.tmp."
         st.refresh_weights()
-        seed = R.next_seed() if (training and self.bb.stack.p > 0) else 0
+        seed = R.next_seed() if self.bb.stack.needs_seed(training) else 0
         feats, probs = self.bb.forward(x, training, seed, save=save if save_backbone is None else save_backbone, slot="a",
                                        return_attn=return_attn)
         B, dev = feats.shape[0], feats.device
@@ -195,6 +196,7 @@ class ViT(nn.Module):
         num_heads: int = 8,
         mlp_dim: int = 3072,
         dropout: float = 0.1,
+        drop_path_rate: float = 0.0,
     ):
         super().__init__()
         self.encoder_blocks = nn.ModuleList(
@@ -205,6 +207,10 @@ class ViT(nn.Module):
         self.input_shape = tuple(input_shape)
         self.num_classes, self.embed_dim, self.patch_size = num_classes, embed_dim, patch_size
         self.num_heads, self.mlp_dim, self.dropout_p = num_heads, mlp_dim, float(dropout)
+        # stochastic depth (timm's drop_path_rate): block i drops a sample from each residual branch with probability
+        # rate * i / (num_blocks - 1) while training; not a parameter
+        self.drop_path_rate = float(drop_path_rate)
+        R.drop_path_rates(self.drop_path_rate, num_blocks)        # a rate outside [0, 1) is a ValueError here
         self._rt = None
 
     def runtime(self, device=None) -> _ViTRuntime:

@@ -15,6 +15,7 @@ ATTENTION_HD_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "inc
 PATCH_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "vitssl_patch.h"))
 OPTIM_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "vitssl_optim.h"))
 MIXUP_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "vitssl_mixup.h"))
+DROPPATH_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "vitssl_droppath.h"))
 
 
 class VitsslError(RuntimeError):
@@ -44,6 +45,11 @@ class Fp8TnJob(C.Structure):
 class OptimSegment(C.Structure):
     """vitssl_optim_segment_t"""
     _fields_ = [("offset", C.c_int64), ("n", C.c_int64), ("lr_scale", C.c_float), ("weight_decay", C.c_float)]
+
+
+class RowScale(C.Structure):
+    """vitssl_rowscale_t"""
+    _fields_ = [("scale", C.c_void_p), ("groups", C.c_int64), ("rows_per_group", C.c_int)]
 
 
 class Gemm(C.Structure):
@@ -170,6 +176,18 @@ PROTOTYPES_MIXUP = {
     "vitssl_classify_loss_mix": [_vp, _vp, _vp, _vp, _i, _i, _i, C.c_double, _i64, _f, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
 }
 
+# include/vitssl_droppath.h (stochastic depth: the table of per-sample branch scales and the row-scaled forms of the residual
+# GEMM and of the two kernels that emit the masked gradient operand): every entry point launches.
+DROPPATH_SITE_BIT = 0x80000000          # VITSSL_DROPPATH_SITE_BIT
+DROPPATH_MAX_SITES = 128                # VITSSL_DROPPATH_MAX_SITES
+PROTOTYPES_DROPPATH = {
+    "vitssl_droppath_table": [_vp, C.POINTER(C.c_float), C.POINTER(C.c_uint32), _i, _i, C.c_uint64, _vp],
+    "vitssl_gemm_bf16_nt_rows": [C.POINTER(Gemm), C.POINTER(RowScale), _vp],
+    "vitssl_layernorm_bwd_rows": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, Dropout, C.POINTER(RowScale), _i64, _i, _vp,
+                                  _i64, _vp],
+    "vitssl_grad_mask_cast_rows": [_vp, _vp, _vp, Dropout, C.POINTER(RowScale), _i64, _i, _vp, _i64, _vp],
+}
+
 _lib = None
 
 
@@ -229,6 +247,14 @@ def mixup_header_symbols():
     return sorted(set(re.findall(r"\b(vitssl_[a-z0-9_]+)\s*\(", txt)))
 
 
+def droppath_header_symbols():
+    """Entry points declared in include/vitssl_droppath.h."""
+    with open(DROPPATH_HEADER_PATH) as f:
+        txt = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)        # the comments name functions of vitssl_hip.h
+    txt = re.sub(r"^\s*#.*$", "", txt, flags=re.M)                    # and so do the macros
+    return sorted(set(re.findall(r"\b(vitssl_[a-z0-9_]+)\s*\(", txt)))
+
+
 def lib():
     global _lib
     if _lib is not None:
@@ -283,7 +309,7 @@ def lib():
         getattr(l, sizing).argtypes = [C.c_int]
     for name, args in (list(PROTOTYPES.items()) + list(PROTOTYPES_TRANSFORMS.items()) + list(PROTOTYPES_METRICS.items())
                        + list(PROTOTYPES_CLASSIFY.items()) + list(PROTOTYPES_ATTENTION_HD.items()) + list(PROTOTYPES_PATCH.items())
-                       + list(PROTOTYPES_OPTIM.items()) + list(PROTOTYPES_MIXUP.items())):
+                       + list(PROTOTYPES_OPTIM.items()) + list(PROTOTYPES_MIXUP.items()) + list(PROTOTYPES_DROPPATH.items())):
         fn = getattr(l, name)  # AttributeError if the symbol is missing
         fn.restype = C.c_int
         fn.argtypes = args

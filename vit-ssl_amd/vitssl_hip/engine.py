@@ -501,11 +501,26 @@ class GradReducer:
         return 1.0 / self.world
 
 
+def drop_path_rates(rate: float, layers: int) -> List[float]:
+    """The stochastic-depth schedule of the ViT recipes (timm's `drop_path_rate`): block i of `layers` drops its two residual
+    branches with probability rate * i / (layers - 1), i.e. linspace(0, rate, layers); 0 for a single block."""
+    rate = float(rate)
+    if not 0.0 <= rate < 1.0:
+        raise ValueError(f"drop_path_rate must lie in [0, 1), got {rate}")
+    if layers <= 1:
+        return [0.0] * max(layers, 0)
+    return [rate * i / (layers - 1) for i in range(layers)]
+
+
 class EncoderStack:
-    """L pre-LN transformer blocks (vit_core/encoder_block.py:40-53) on a flat store."""
+    """L pre-LN transformer blocks (vit_core/encoder_block.py:40-53) on a flat store.
+
+    `drop_path` (stochastic depth, include/vitssl_droppath.h): per-block probabilities with which a training forward drops a
+    whole sample from the block's attention branch and, drawn independently, from its MLP branch; survivors are scaled by
+    1 / (1 - rate).  None or all zeros: nothing of it is launched.  bf16 operands only."""
 
     def __init__(self, store: FlatStore, block_prefixes: List[str], D: int, H: int, F: int, p_drop: float,
-                 site_base: int = 0):
+                 site_base: int = 0, drop_path: Optional[List[float]] = None):
         if D % H != 0:
             raise AssertionError(f"d_model({D}) must be cleanly divisible by num_heads({H})!")
         self.store = store
@@ -517,6 +532,17 @@ class EncoderStack:
         self.ws = Workspace()
         self._saved = {}
         self.fp8 = linear_operands() == "fp8"
+        rates = [float(r) for r in drop_path] if drop_path is not None else []
+        if rates and len(rates) != self.L:
+            raise ValueError(f"drop_path holds {len(rates)} rates for {self.L} blocks")
+        if any(not 0.0 <= r < 1.0 for r in rates):
+            raise ValueError(f"drop_path rates must lie in [0, 1), got {rates}")
+        self.drop_path = rates if any(r > 0.0 for r in rates) else None
+        if self.drop_path is not None and self.fp8:
+            raise L.VitsslError("drop path (drop_path_rate > 0) is built for bf16 linear operands only: use bf16 operands "
+                                "(set_linear_operands('bf16') or VITSSL_LINEAR_OPERANDS=bf16) or drop_path_rate = 0")
+        if self.drop_path is not None and 2 * self.L > L.DROPPATH_MAX_SITES:
+            raise L.VitsslError(f"drop path covers up to {L.DROPPATH_MAX_SITES // 2} blocks a stack, got {self.L}")
         if self.fp8 and (D % 128 != 0 or F % 128 != 0):
             raise L.VitsslError(f"fp8 linear operands need embed_dim ({D}) and mlp_dim ({F}) to be multiples of 128")
         for b in self.bp:
@@ -554,6 +580,22 @@ class EncoderStack:
             return ops.NO_DROP
         return ops.make_dropout(self.p, seed, self.site_base + 3 * i + which)
 
+    def needs_seed(self, training: bool) -> bool:
+        """Whether a forward in this mode draws from the dropout stream (element dropout or drop path): callers take a step seed
+        from the torch generator exactly then."""
+        return bool(training) and (self.p > 0.0 or self.drop_path is not None)
+
+    def drop_path_sites(self) -> List[Tuple[float, int]]:
+        """(rate, site) of the table's rows: row 2 i is block i's attention branch, row 2 i + 1 its MLP branch.  The sites carry
+        VITSSL_DROPPATH_SITE_BIT, which no dropout site (site_base + 3 i + which) has, plus site_base, so the stacks of one model
+        (spaced like their dropout sites) draw apart as well."""
+        return [(r, L.DROPPATH_SITE_BIT | ((self.site_base + 2 * i + br) & 0x7FFFFFFF)) for i, r in enumerate(self.drop_path or [])
+                for br in (0, 1)]
+
+    def drop_path_table(self, slot: str = "a") -> Optional[torch.Tensor]:
+        """The f32 [2 L, B] table of branch scales the last saving forward of `slot` applied (None: drop path did not run)."""
+        return self._saved[slot].get("dp")
+
     def check_tokens(self, T: int):
         """Refuse a head dim or a sequence length the attention kernels of this operand mode do not cover.  Models call it at the top of
         their forward, before the first kernel of the step; forward() below repeats it for lone blocks."""
@@ -580,6 +622,13 @@ class EncoderStack:
         g = self.ws.get
         probs = None
         rec = {"B": B, "T": T, "seed": seed, "training": training, "blocks": []}
+        # drop path: one table of per-sample scales for the whole call, kept with the slot for the backward
+        dp = None
+        if training and self.drop_path is not None:
+            dp = ops.droppath_table(self.drop_path_sites(), B, seed, g(f"{slot}.dp" if save else f"{slot}.tmp.dp", (2 * self.L, B), F32, dev))
+        rec["dp"] = dp
+        # (a block whose rate is 0 -- the first one of every schedule -- keeps the plain launches: its rows of the table are ones)
+        rows = lambda i, br: (dp[2 * i + br], T) if dp is not None and self.drop_path[i] > 0.0 else None      # noqa: E731
         cur = x
         for i in range(self.L):
             tag = f"{slot}.{i}." if save else f"{slot}.tmp."
@@ -623,10 +672,11 @@ class EncoderStack:
                 ops.layernorm_fwd(*ln1, h1, mean1, rstd1)
                 ops.gemm_nt(h1, st.w(self._n(i, "wqkv")), qkv, L.EPI_BF16)
                 ops.attn_fwd_any(qkv, att, lse, B, T, H, dh, probs=probs if i == self.L - 1 else None)
-                ops.gemm_nt(att, st.w(self._n(i, "wo")), xmid, L.EPI_RESID, aux=cur, drop=self._drop(i, 0, seed, training))
+                ops.gemm_nt(att, st.w(self._n(i, "wo")), xmid, L.EPI_RESID, aux=cur, drop=self._drop(i, 0, seed, training), rows=rows(i, 0))
                 ops.layernorm_fwd(*ln2, h2, mean2, rstd2)
                 ops.gemm_nt(h2, st.w(self._n(i, "w1")), u, L.EPI_GELU, bias=b1, out1=a, drop=self._drop(i, 1, seed, training))
-                ops.gemm_nt(a, st.w(self._n(i, "w2")), xout, L.EPI_RESID, bias=b2, aux=xmid, drop=self._drop(i, 2, seed, training))
+                ops.gemm_nt(a, st.w(self._n(i, "w2")), xout, L.EPI_RESID, bias=b2, aux=xmid, drop=self._drop(i, 2, seed, training),
+                            rows=rows(i, 1))
             if save:
                 rec["blocks"].append(dict(xin=cur, h1=h1, mean1=mean1, rstd1=rstd1, qkv=qkv, att=att, lse=lse, xmid=xmid,
                                           h2=h2, mean2=mean2, rstd2=rstd2, u=u, a=a))
@@ -671,9 +721,12 @@ class EncoderStack:
         # buffer (gm2) instead of over gm.  VITSSL_TN_BATCH=0: one launch per gradient, as before.
         batch = _os.environ.get("VITSSL_TN_BATCH", "1") != "0"
         wgrad = not input_grad_only
+        dp = rec.get("dp")      # drop path: the forward's table; the masked operand of a branch takes the branch's row of it
+        rows = lambda i, br: (dp[2 * i + br], T) if dp is not None and self.drop_path[i] > 0.0 else None      # noqa: E731
         gm2 = w(bw + "gm2", (M, D), BF16, dev) if batch and wgrad else gm
         # top of the chain: dropout-mask + cast of g, and the last block's linear_out bias grad
-        ops.grad_mask_cast(g, gm, gv(self._n(last, "feed_forward.linear_out.bias")), self._drop(last, 2, seed, training))
+        ops.grad_mask_cast(g, gm, gv(self._n(last, "feed_forward.linear_out.bias")), self._drop(last, 2, seed, training),
+                           rows=rows(last, 1))
         for i in range(last, -1, -1):
             s = rec["blocks"][i]
             a_ = self.bp[i] + "self_attention."
@@ -691,7 +744,7 @@ class EncoderStack:
                 ops.gemm_tn(*wgrads[1])
             ops.layernorm_bwd(dh_, s["xmid"], s["mean2"], s["rstd2"], st.view(self._n(i, "layer_norm2.weight")), g, g, gm2,
                               gv(self._n(i, "layer_norm2.weight")), gv(self._n(i, "layer_norm2.bias")), None,
-                              self._drop(i, 0, seed, training))
+                              self._drop(i, 0, seed, training), rows=rows(i, 0))
             # attention
             ops.gemm_nt(gm2, st.w(self._n(i, "wo") + ".T"), dh_, L.EPI_BF16)
             if wgrad and not batch:
@@ -705,7 +758,8 @@ class EncoderStack:
             if i > 0:
                 ops.layernorm_bwd(dh_, s["xin"], s["mean1"], s["rstd1"], st.view(self._n(i, "layer_norm1.weight")), g, g, gm,
                                   gv(self._n(i, "layer_norm1.weight")), gv(self._n(i, "layer_norm1.bias")),
-                                  gv(self._n(i - 1, "feed_forward.linear_out.bias")), self._drop(i - 1, 2, seed, training))
+                                  gv(self._n(i - 1, "feed_forward.linear_out.bias")), self._drop(i - 1, 2, seed, training),
+                                  rows=rows(i - 1, 1))
             else:
                 ops.layernorm_bwd(dh_, s["xin"], s["mean1"], s["rstd1"], st.view(self._n(i, "layer_norm1.weight")), g, g, None,
                                   gv(self._n(i, "layer_norm1.weight")), gv(self._n(i, "layer_norm1.bias")), None, ops.NO_DROP)

@@ -129,29 +129,60 @@ def grad_mask_cast_fp8(g, gm, gm8, scale, amax, gm_colsum=None, drop=NO_DROP):
          *_sum_ws(g.device, rows, cols), _stream())
 
 
-def layernorm_bwd(dy, x, mean, rstd, gamma, g_res, g_out, gm, dgamma, dbeta, gm_colsum=None, drop=NO_DROP):
+def droppath_table(pairs, B, seed, out):
+    """out f32 [len(pairs), B] = the per-sample branch scales (include/vitssl_droppath.h) of the (rate, site) pairs for `seed`:
+    1 / (1 - r_eff) where the dropout stream keeps the sample, 0 where it drops it; a rate of 0 gives a row of ones."""
+    n = len(pairs)
+    if not 1 <= n <= L.DROPPATH_MAX_SITES:
+        raise L.VitsslError(f"droppath_table: {n} (rate, site) pairs outside [1, {L.DROPPATH_MAX_SITES}]")
+    rates = (C.c_float * n)(*[float(r) for r, _ in pairs])
+    sites = (C.c_uint32 * n)(*[int(s) & 0xFFFFFFFF for _, s in pairs])
+    call("vitssl_droppath_table", _chk(out, F32, "scale", (n, B)), rates, sites, n, int(B), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
+         _stream())
+    return out
+
+
+def _rowscale(rows, M, name):
+    """vitssl_rowscale_t of rows = (scale f32 [groups], rows_per_group): row m of the [M, *] operand takes scale[m // rows_per_group]."""
+    scale, rpg = rows
+    rpg = int(rpg)
+    if rpg <= 0 or M % rpg != 0:
+        raise L.VitsslError(f"{name}: rows_per_group {rpg} does not divide the {M} rows")
+    r = L.RowScale()
+    r.scale = _chk(scale, F32, name + " rows.scale", (M // rpg,))
+    r.groups, r.rows_per_group = M // rpg, rpg
+    return r
+
+
+def layernorm_bwd(dy, x, mean, rstd, gamma, g_res, g_out, gm, dgamma, dbeta, gm_colsum=None, drop=NO_DROP, rows=None):
+    """rows=(scale, rows_per_group): vitssl_layernorm_bwd_rows, the bf16 operand `gm` scaled per row (drop path)."""
+    rs = () if rows is None else (C.byref(_rowscale(rows, x.shape[0], "layernorm_bwd")),)
     rows, cols = x.shape
     ev = _prof_begin()
-    call("vitssl_layernorm_bwd", _chk(dy, BF16, "dy", (rows, cols)), _chk(x, F32, "x"), _chk(mean, F32, "mean", (rows,)),
-         _chk(rstd, F32, "rstd", (rows,)), _chk(gamma, F32, "gamma", (cols,)), _opt(g_res, F32, "g_res", (rows, cols)),
+    call("vitssl_layernorm_bwd_rows" if rs else "vitssl_layernorm_bwd", _chk(dy, BF16, "dy", (rows, cols)), _chk(x, F32, "x"),
+         _chk(mean, F32, "mean", (rows,)), _chk(rstd, F32, "rstd", (rows,)), _chk(gamma, F32, "gamma", (cols,)),
+         _opt(g_res, F32, "g_res", (rows, cols)),
          _chk(g_out, F32, "g_out", (rows, cols)), _opt(gm, BF16, "gm", (rows, cols)), _chk(dgamma, F32, "dgamma", (cols,)),
-         _chk(dbeta, F32, "dbeta", (cols,)), _opt(gm_colsum, F32, "gm_colsum", (cols,)), drop, rows, cols, *_sum_ws(x.device, rows, cols),
-         _stream())
+         _chk(dbeta, F32, "dbeta", (cols,)), _opt(gm_colsum, F32, "gm_colsum", (cols,)), drop, *rs, rows, cols,
+         *_sum_ws(x.device, rows, cols), _stream())
     # dy bf16 + x fp32 (+ residual gradient fp32) in, gradient fp32 (+ masked bf16 operand) out
     _prof_end(ev, "ln_bwd", 0.0, rows * (cols * (2 + 4 + (4 if g_res is not None else 0) + 4 + (2 if gm is not None else 0)) + 8))
 
 
-def grad_mask_cast(g, gm, gm_colsum=None, drop=NO_DROP):
+def grad_mask_cast(g, gm, gm_colsum=None, drop=NO_DROP, rows=None):
+    """rows=(scale, rows_per_group): vitssl_grad_mask_cast_rows, `gm` scaled per row (drop path)."""
+    rs = () if rows is None else (C.byref(_rowscale(rows, g.shape[0], "grad_mask_cast")),)
     rows, cols = g.shape
-    call("vitssl_grad_mask_cast", _chk(g, F32, "g"), _chk(gm, BF16, "gm", (rows, cols)),
-         _opt(gm_colsum, F32, "gm_colsum", (cols,)), drop, rows, cols, *_sum_ws(g.device, rows, cols), _stream())
+    call("vitssl_grad_mask_cast_rows" if rs else "vitssl_grad_mask_cast", _chk(g, F32, "g"), _chk(gm, BF16, "gm", (rows, cols)),
+         _opt(gm_colsum, F32, "gm_colsum", (cols,)), drop, *rs, rows, cols, *_sum_ws(g.device, rows, cols), _stream())
 
 
 _OUT0_DTYPE = {L.EPI_BF16: BF16, L.EPI_F32: F32, L.EPI_GELU: BF16, L.EPI_RESID: F32, L.EPI_DGELU: BF16, L.EPI_EMBED: F32}
 
 
-def gemm_nt(A, B, out0, epilogue, bias=None, aux=None, out1=None, colsum=None, drop=NO_DROP, embed=None):
-    """out = A[M,K] @ B[N,K]^T with the fused epilogue (see include/vitssl_hip.h)."""
+def gemm_nt(A, B, out0, epilogue, bias=None, aux=None, out1=None, colsum=None, drop=NO_DROP, embed=None, rows=None):
+    """out = A[M,K] @ B[N,K]^T with the fused epilogue (see include/vitssl_hip.h).  rows=(scale, rows_per_group) selects
+    vitssl_gemm_bf16_nt_rows (EPI_RESID only): out0 = aux + scale[row // rows_per_group] * drop(acc + bias)."""
     M, K = A.shape
     N, K2 = B.shape
     if K != K2:
@@ -187,7 +218,12 @@ def gemm_nt(A, B, out0, epilogue, bias=None, aux=None, out1=None, colsum=None, d
         g.workspace, g.workspace_floats = _sum_ws(colsum.device, M, N)
     g.drop = drop
     ev = _prof_begin()
-    call("vitssl_gemm_bf16_nt", C.byref(g), _stream())
+    if rows is not None:
+        if epilogue != L.EPI_RESID:
+            raise L.VitsslError(f"gemm_nt: rows= belongs to EPI_RESID, got epilogue {epilogue}")
+        call("vitssl_gemm_bf16_nt_rows", C.byref(g), C.byref(_rowscale(rows, M, "gemm_nt")), _stream())
+    else:
+        call("vitssl_gemm_bf16_nt", C.byref(g), _stream())
     _prof_end(ev, f"gemm_nt[epi{epilogue}] {M}x{N}x{K}", 2.0 * M * N * K)
 
 
