@@ -74,11 +74,11 @@ typedef std::atomic<bool> VsOnce;   // "hipFuncSetAttribute already done" flags:
 float* vs_parts(float* workspace, int64_t workspace_floats, long long need, const char* who, const char* sizing = "vitssl_sum_workspace_floats");
 // the same for a sum over a [rows, cols] matrix: requires the documented vitssl_sum_workspace_floats(rows, cols), which must cover `need`
 float* vs_sum_parts(float* workspace, int64_t workspace_floats, long long need, long long rows, int cols, const char* who);
-// target[c] += sum over p = 0 .. nparts-1 of parts[p * stride + c], c < n, always summed in the same order; up to three
+// target[c] += sum over p = 0 .. nparts-1 of parts[p * stride + c], c < n, always summed in the same order; up to four
 // (target, parts) pairs of one shape in one launch (null targets are skipped)
 struct VsSums {
-  float* target[3];
-  const float* parts[3];
+  float* target[4];
+  const float* parts[4];
 };
 int vs_reduce_parts(const VsSums& sums, int nparts, long long n, long long stride, hipStream_t s);
 inline int vs_reduce_parts(float* target, const float* parts, int nparts, long long n, long long stride, hipStream_t s) {

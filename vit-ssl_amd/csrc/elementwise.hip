@@ -433,7 +433,7 @@ extern "C" int64_t vitssl_sum_workspace_floats(int64_t rows, int cols) {
 int vs_reduce_parts(const VsSums& sums, int nparts, long long n, long long stride, hipStream_t s) {
   VsSums packed = {};
   int k = 0;
-  for (int i = 0; i < 3; ++i)
+  for (int i = 0; i < 4; ++i)
     if (sums.target[i]) {
       packed.target[k] = sums.target[i];
       packed.parts[k++] = sums.parts[i];

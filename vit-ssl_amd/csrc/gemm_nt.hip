@@ -33,6 +33,7 @@
 #include <stdlib.h>
 #include <atomic>
 #include "../../include/vitssl_droppath.h"
+#include "../../include/vitssl_layerscale.h"
 #include "common.h"
 
 namespace {
@@ -85,6 +86,8 @@ struct NtParams {
   float* qamax;         // device slot that receives max |value| written to out2, before scaling (atomic max; NULL = none)
   const float* rowscale;   // EPI_RESID_ROWS: the branch of row m is multiplied by rowscale[m / rows_per_group] (include/vitssl_droppath.h)
   unsigned rows_per_group;
+  const float* colscale;   // EPI_RESID_LS: the branch of column n is multiplied by colscale[n] (LayerScale, include/vitssl_layerscale.h);
+                           // rowscale may be NULL there (no drop path) and out1, if given, receives the bf16 image of the branch
 #ifdef VITSSL_NT_STAMPS
   unsigned long long* stamps;   // diagnostic build only (tools/nt_stamps.py): [2: 100 MHz ticks, shader clocks][wg][2 wave groups][16 rounds][4]
 #endif
@@ -96,7 +99,10 @@ constexpr int EPI_F32_SPLITK = 100;
 // internal epilogue: VITSSL_EPI_RESID with a per-row scale of the branch (drop path, vitssl_gemm_bf16_nt_rows).  An epilogue id
 // of its own, so that the kernels of the plain residual launch are the instantiations they were.
 constexpr int EPI_RESID_ROWS = 101;
-constexpr bool epi_is_resid(int epi) { return epi == VITSSL_EPI_RESID || epi == EPI_RESID_ROWS; }
+// internal epilogue: VITSSL_EPI_RESID with a per-column scale of the branch (LayerScale, vitssl_gemm_bf16_nt_ls), an optional
+// per-row scale and an optional bf16 image of the branch before both scales.  Again an id of its own.
+constexpr int EPI_RESID_LS = 102;
+constexpr bool epi_is_resid(int epi) { return epi == VITSSL_EPI_RESID || epi == EPI_RESID_ROWS || epi == EPI_RESID_LS; }
 
 // XOR applied to the 16-byte chunk index of tile row r (source side for the DMA, and on
 // the fragment reads): BK=64 (128-B rows) chunk ^ ((r>>1)&7); BK=32 (64-B rows)
@@ -323,6 +329,9 @@ __device__ __forceinline__ void nt_epilogue(const NtParams& p, f32x4 (&acc)[4][C
   if constexpr (EPI == VITSSL_EPI_BF16 || EPI == VITSSL_EPI_GELU || EPI == VITSSL_EPI_DGELU) rsOut0 = window(p.out0, 2);
   if constexpr (EPI == VITSSL_EPI_F32 || epi_is_resid(EPI)) rsOut0 = window(p.out0, 4);
   if constexpr (EPI == VITSSL_EPI_GELU) rsOut1 = window(p.out1, 2);
+  if constexpr (EPI == EPI_RESID_LS) {
+    if (p.out1) rsOut1 = window(p.out1, 2);         // launch-uniform: the branch image is optional
+  }
   if constexpr (epi_is_resid(EPI)) rsAux = window(p.aux, 4);
   if constexpr (EPI == VITSSL_EPI_DGELU) rsAux = window(p.aux, 2);
 
@@ -331,6 +340,7 @@ __device__ __forceinline__ void nt_epilogue(const NtParams& p, f32x4 (&acc)[4][C
   int nn[2][2];
   bool okn[2][2];
   f32x4 bias4[2][2];
+  f32x4 gam4[2][2];        // RESID_LS: colscale of this lane's 16 columns, loaded once per column tile like the bias
   // dropout stream (common.h): the state word of group g = row * N/4 + col/4 is g * C0 + k0 = (row term) + (column term);
   // the row term advances by a launch constant per 16-row tile, the column terms are four lane constants
   constexpr bool DROPS = EPI == VITSSL_EPI_GELU || epi_is_resid(EPI);
@@ -351,6 +361,10 @@ __device__ __forceinline__ void nt_epilogue(const NtParams& p, f32x4 (&acc)[4][C
       okn[jp][h] = nn[jp][h] < p.N;
       bias4[jp][h] = f32x4{0.f, 0.f, 0.f, 0.f};
       if (p.bias && (EPI != EPI_F32_SPLITK || blockIdx.y == 0) && okn[jp][h]) bias4[jp][h] = *(const f32x4*)(p.bias + nn[jp][h]);
+      if constexpr (EPI == EPI_RESID_LS) {
+        gam4[jp][h] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (okn[jp][h]) gam4[jp][h] = *(const f32x4*)(p.colscale + nn[jp][h]);
+      }
     }
 
   // Rows are walked in groups; inside a group the loop order is row -> pair, so the two
@@ -377,6 +391,17 @@ __device__ __forceinline__ void nt_epilogue(const NtParams& p, f32x4 (&acc)[4][C
   float rsc[NB][RG];         // RESID_ROWS: the scale of this lane's accumulator row (row tile ig + ii), requested with the group's residual
   auto load_group = [&](const int ig, const int b) {
     const int cnt = MI - ig < RG ? MI - ig : RG;
+    if constexpr (EPI == EPI_RESID_LS) {
+#pragma unroll
+      for (int ii = 0; ii < RG; ++ii) {
+        if (ii >= cnt) continue;
+        rsc[b][ii] = 1.0f;
+        if (p.rowscale) {                           // launch-uniform; indexed as in the rows form below
+          const long long mr = m0 + wm * CFG::WROWS + (ig + ii) * 16 + (lane & 15);
+          rsc[b][ii] = p.rowscale[mr < p.M ? (unsigned)mr / p.rows_per_group : 0u];
+        }
+      }
+    }
     if constexpr (EPI == EPI_RESID_ROWS) {
 #pragma unroll
       for (int ii = 0; ii < RG; ++ii) {
@@ -580,7 +605,27 @@ __device__ __forceinline__ void nt_epilogue(const NtParams& p, f32x4 (&acc)[4][C
             res[gb][ii][jp][0] = *(const f32x4*)(xs + tw32);
             res[gb][ii][jp][1] = *(const f32x4*)(xs + (tw32 ^ 64u));
           }
-          if constexpr (EPI == EPI_RESID_ROWS) {
+          if constexpr (EPI == EPI_RESID_LS) {
+            // rs * dropscale formed as the rows form forms it (rs is 1 without a table), then one more rounding for its product
+            // with the column's gamma: a gamma of ones gives the bits of the rows / plain launch.  The bf16 image of the branch
+            // carries the dropout mask and scale only.
+            const float rs = rsc[gb][ii];
+            const float cs = p.drop_on ? rs * p.dk.scale : rs;
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+              bool keep[4] = {true, true, true, true};
+              if (p.drop_on) drop_keep4(p.dk, drop_words_a0(p.dk, a0row + (unsigned)i * a0rowstep + a0col[jp][h]), keep);
+              float u[4];
+#pragma unroll
+              for (int r = 0; r < 4; ++r) {
+                const float kv = keep[r] ? v[h][r] : 0.f;
+                u[r] = p.drop_on ? kv * p.dk.scale : kv;
+                const float t = fmaf(kv, cs * gam4[jp][h][r], res[gb][ii][jp][h][r]);
+                v[h][r] = rs == 0.f ? res[gb][ii][jp][h][r] : t;
+              }
+              out_a[jp][h] = u32x2{pack_bf2(u[0], u[1]), pack_bf2(u[2], u[3])};
+            }
+          } else if constexpr (EPI == EPI_RESID_ROWS) {
             // the row's scale times the dropout scale (1 when dropout is off: a table of ones gives the plain launch's bits); a
             // dropped row (scale 0) stores the residual itself, whatever the accumulator holds
             const float rs = rsc[gb][ii];
@@ -639,6 +684,9 @@ __device__ __forceinline__ void nt_epilogue(const NtParams& p, f32x4 (&acc)[4][C
       }
       if constexpr (EPI == VITSSL_EPI_GELU) {
         if (!Q8 || p.out1) store_bf16_row(rsOut1, i, out_b, IC<0>{});   // same for the GELU output
+      }
+      if constexpr (EPI == EPI_RESID_LS) {
+        if (p.out1) store_bf16_row(rsOut1, i, out_a, IC<2>{});          // read again only in backward: non-temporal, like g'
       }
       if constexpr (Q8EPI) {
         if (q8) {
@@ -1282,7 +1330,7 @@ int launch_pp(NtParams p, hipStream_t s) {
   const float epi_us = EPI == VITSSL_EPI_BF16 ? 2.f : EPI == VITSSL_EPI_GELU ? 7.f : EPI == VITSSL_EPI_DGELU ? 5.f
                        : epi_is_resid(EPI) ? 8.f : 4.f;
   const float tile_us = (float)(p.K * p.esz / 128) * 1.45f * (float)CFG::MI / 8.f + epi_us;
-  constexpr int MASK_BIT = EPI == EPI_RESID_ROWS ? VITSSL_EPI_RESID : EPI;      // the rows form staggers as the residual epilogue does
+  constexpr int MASK_BIT = (EPI == EPI_RESID_ROWS || EPI == EPI_RESID_LS) ? VITSSL_EPI_RESID : EPI;      // the rows / LayerScale forms stagger as the residual epilogue does
   p.stagger = ((stagger_mask >> MASK_BIT) & 1) ? (int)(stagger_scale * tile_us * 100.f) : 0;
   nt_note_grid((int)grid);
   hipLaunchKernelGGL((gemm_nt_pp_kernel<EPI, CFG, F8>), dim3((unsigned)grid), dim3(CFG::THREADS), LDS, s, p);
@@ -1492,8 +1540,9 @@ static unsigned long long* g_nt_stamps = nullptr;
 extern "C" void vitssl_debug_nt_stamps(void* buf) { g_nt_stamps = (unsigned long long*)buf; }
 #endif
 
-static int gemm_nt_entry(const vitssl_gemm_t* g, int esz, const vitssl_fp8_gemm_t* q, void* stream, const vitssl_rowscale_t* rows = nullptr) {
-  const char* who = rows ? "gemm_nt_rows" : esz == 1 ? "gemm_fp8_nt" : "gemm_nt";
+static int gemm_nt_entry(const vitssl_gemm_t* g, int esz, const vitssl_fp8_gemm_t* q, void* stream, const vitssl_rowscale_t* rows = nullptr,
+                         const vitssl_colscale_t* cols = nullptr, void* branch = nullptr) {
+  const char* who = cols ? "gemm_nt_ls" : rows ? "gemm_nt_rows" : esz == 1 ? "gemm_fp8_nt" : "gemm_nt";
   VS_CHECK_ARG(g && g->A && g->B && (g->out0 || (esz == 1 && g->epilogue == VITSSL_EPI_DGELU && q && q->out_fp8)), "%s: null operand", who);
   VS_CHECK_ARG(g->M > 0 && g->N > 0 && g->K > 0, "%s: empty problem M=%lld N=%d K=%d", who, (long long)g->M, g->N, g->K);
   VS_CHECK_ARG(g->K % (128 / esz) == 0, "%s: K=%d must be a multiple of %d", who, g->K, 128 / esz);
@@ -1528,6 +1577,7 @@ static int gemm_nt_entry(const vitssl_gemm_t* g, int esz, const vitssl_fp8_gemm_
   p.qamax = q ? q->out_amax : nullptr;
   p.rowscale = nullptr;
   p.rows_per_group = 1;
+  p.colscale = nullptr;
 #ifdef VITSSL_NT_STAMPS
   p.stamps = g_nt_stamps;
 #endif
@@ -1536,6 +1586,22 @@ static int gemm_nt_entry(const vitssl_gemm_t* g, int esz, const vitssl_fp8_gemm_
                "%s: column sums are built for the BF16 / F32 / DGELU epilogues only", who);
   VS_CHECK_ARG(!p.drop_on || (unsigned long long)g->M * (unsigned long long)g->N < (1ull << 34),
                "%s: dropout over %lld x %d elements: the stream's group counter is 32 bits (M * N < 2^34)", who, (long long)g->M, g->N);
+  if (cols) {      // vitssl_gemm_bf16_nt_ls: the residual epilogue with a per-column scale of the branch (and optional row scales)
+    VS_CHECK_ARG(g->epilogue == VITSSL_EPI_RESID, "%s: column scales are built for VITSSL_EPI_RESID only, got epilogue %d", who, g->epilogue);
+    VS_CHECK_ARG(g->aux, "%s: EPI_RESID needs aux (residual)", who);
+    VS_CHECK_ARG(cols->gamma, "%s: null gamma", who);
+    VS_CHECK_ARG(cols->cols == g->N, "%s: cols (%d) must equal N (%d)", who, cols->cols, g->N);
+    if (rows) {
+      VS_CHECK_ARG(rows->scale && rows->groups > 0 && rows->rows_per_group > 0, "%s: row scales need scale, groups > 0 and rows_per_group > 0", who);
+      VS_CHECK_ARG(rows->groups * (int64_t)rows->rows_per_group == g->M, "%s: groups (%lld) * rows_per_group (%d) must equal M (%lld)", who,
+                   (long long)rows->groups, rows->rows_per_group, (long long)g->M);
+      p.rowscale = rows->scale;
+      p.rows_per_group = (unsigned)rows->rows_per_group;
+    }
+    p.colscale = cols->gamma;
+    p.out1 = branch;
+    return launch_nt<EPI_RESID_LS>(p, s);
+  }
   if (rows) {      // vitssl_gemm_bf16_nt_rows: the residual epilogue with a per-row scale of the branch
     VS_CHECK_ARG(g->epilogue == VITSSL_EPI_RESID, "%s: row scales are built for VITSSL_EPI_RESID only, got epilogue %d", who, g->epilogue);
     VS_CHECK_ARG(g->aux, "%s: EPI_RESID needs aux (residual)", who);
@@ -1574,6 +1640,12 @@ extern "C" int vitssl_gemm_bf16_nt(const vitssl_gemm_t* g, void* stream) { retur
 extern "C" int vitssl_gemm_bf16_nt_rows(const vitssl_gemm_t* g, const vitssl_rowscale_t* rows, void* stream) {
   VS_CHECK_ARG(rows, "gemm_nt_rows: null row scales (vitssl_gemm_bf16_nt is the launch without them)");
   return gemm_nt_entry(g, 2, nullptr, stream, rows);
+}
+
+extern "C" int vitssl_gemm_bf16_nt_ls(const vitssl_gemm_t* g, const vitssl_colscale_t* cols, const vitssl_rowscale_t* rows,
+                                      void* branch_bf16, void* stream) {
+  VS_CHECK_ARG(cols, "gemm_nt_ls: null column scales (vitssl_gemm_bf16_nt / vitssl_gemm_bf16_nt_rows are the launches without them)");
+  return gemm_nt_entry(g, 2, nullptr, stream, rows, cols, branch_bf16);
 }
 
 extern "C" int vitssl_gemm_fp8_nt(const vitssl_gemm_t* g, const vitssl_fp8_gemm_t* q, void* stream) {

@@ -11,6 +11,7 @@
 // across the block's 4 waves in LDS and added to global with one atomic per column
 // per block.
 #include "../../include/vitssl_droppath.h"
+#include "../../include/vitssl_layerscale.h"
 #include "common.h"
 
 namespace {
@@ -109,8 +110,23 @@ constexpr int ln_bwd_blocks(int V, bool has_ln, bool has_cs) {
 // ROWS (drop path, include/vitssl_droppath.h): the bf16 operand of row r is multiplied once more, by rowscale[r / rows_per_group];
 // g_out, dgamma and dbeta are not.  An instantiation of its own: the plain kernels are what they were.  (The row-pair form without
 // column sums spills at 3 workgroups per CU once it also holds the pair's two scales: it takes the budget of the form with them.)
-template <int V, bool HAS_LN, bool HAS_CS, bool Q8 = false, bool PAIR = false, bool ROWS = false>
-__global__ __launch_bounds__(LN_THREADS, ln_bwd_blocks(V, HAS_LN, HAS_CS || (ROWS && PAIR))) void ln_bwd_kernel(const bf16_t* __restrict__ dy, const float* __restrict__ x,
+// LS (LayerScale, include/vitssl_layerscale.h; built with ROWS and HAS_CS, rowscale and gm_colsum may be NULL at run time): the
+// bf16 operand is multiplied once more, by lsgamma[column], and where dls is given a fourth column sum, of sc * g_out * branch, is
+// kept; the branch image is requested with the row's other operands so that the prefetch stays one round trip.
+struct LnLsArgs {                                   // the arguments only the LayerScale form takes
+  const float* gamma;                               // f32 [cols]
+  const bf16_t* branch;                             // bf16 [rows, cols] or NULL
+  float* dls;                                       // slot rows of gamma's gradient or NULL (with branch)
+};
+__device__ __forceinline__ const LnLsArgs& ln_first(const LnLsArgs& a) { return a; }
+// (1024 columns with LayerNorm: the four sums and the branch image do not fit the two-workgroup budget without scratch; rows above
+// 512 columns run one workgroup per CU anyway, ln_grid)
+constexpr int ln_bwd_ls_blocks(int V, bool has_ln) { return has_ln && V == 4 ? 1 : ln_bwd_blocks(V, has_ln, true); }
+
+// (the LayerScale arguments travel as a parameter pack, empty in every other instantiation: those keep the argument list, and so
+// the code, they had)
+template <int V, bool HAS_LN, bool HAS_CS, bool Q8 = false, bool PAIR = false, bool ROWS = false, typename... LSARGS>
+__global__ __launch_bounds__(LN_THREADS, sizeof...(LSARGS) ? ln_bwd_ls_blocks(V, HAS_LN) : ln_bwd_blocks(V, HAS_LN, HAS_CS || (ROWS && PAIR))) void ln_bwd_kernel(const bf16_t* __restrict__ dy, const float* __restrict__ x,
                                                             const float* __restrict__ mean, const float* __restrict__ rstd,
                                                             const float* __restrict__ gamma, const float* g_res,
                                                             float* g_out, bf16_t* __restrict__ gm, float* __restrict__ dgamma,
@@ -118,7 +134,18 @@ __global__ __launch_bounds__(LN_THREADS, ln_bwd_blocks(V, HAS_LN, HAS_CS || (ROW
                                                             DropKey dk, int drop_on, long long rows, int cols,
                                                             unsigned char* __restrict__ gm8 = nullptr,
                                                             const float* __restrict__ qscale = nullptr, float* qamax = nullptr,
-                                                            const float* __restrict__ rowscale = nullptr, unsigned rows_per_group = 1) {
+                                                            const float* __restrict__ rowscale = nullptr, unsigned rows_per_group = 1,
+                                                            LSARGS... lsargs) {
+  constexpr bool LS = sizeof...(LSARGS) > 0;
+  const float* __restrict__ lsgamma = nullptr;
+  const bf16_t* __restrict__ branch = nullptr;
+  float* __restrict__ dls = nullptr;
+  if constexpr (LS) {
+    const LnLsArgs& a = ln_first(lsargs...);
+    lsgamma = a.gamma;
+    branch = a.branch;
+    dls = a.dls;
+  }
   __shared__ __attribute__((aligned(16))) float red[4][V * 256];   // [wave][col]
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -126,7 +153,9 @@ __global__ __launch_bounds__(LN_THREADS, ln_bwd_blocks(V, HAS_LN, HAS_CS || (ROW
   const int c4h = PAIR ? c4n >> 1 : c4n;            // float4 per row
   static_assert(!PAIR || (HAS_LN && !Q8), "row pairs are built for the LayerNorm form with a bf16 image");
   static_assert(!ROWS || !Q8, "row scales are built for the bf16 image");
+  static_assert(!LS || (ROWS && HAS_CS), "LayerScale is built on the form with row scales and column sums");
   f32x4 g[V], acc_dg[V], acc_db[V], acc_cs[V];
+  f32x4 lsg[V], acc_ls[V];                          // LS: gamma of the slot's four columns, running sum of its gradient
   bool hi[V];                                       // PAIR: the slot holds columns of the pair's second row
 #pragma unroll
   for (int v = 0; v < V; ++v) {
@@ -136,6 +165,10 @@ __global__ __launch_bounds__(LN_THREADS, ln_bwd_blocks(V, HAS_LN, HAS_CS || (ROW
     acc_db[v] = acc_dg[v];
     acc_cs[v] = acc_dg[v];
     if (HAS_LN && c4 < c4n) g[v] = *(const f32x4*)(gamma + 4 * (c4 - (hi[v] ? c4h : 0)));
+    if constexpr (LS) {
+      acc_ls[v] = acc_dg[v];
+      if (c4 < c4n) lsg[v] = *(const f32x4*)(lsgamma + 4 * (c4 - (hi[v] ? c4h : 0)));
+    }
   }
   const float inv = 1.0f / (float)(PAIR ? cols >> 1 : cols);
   const float qs = (Q8 && qscale) ? *qscale : 1.0f;
@@ -143,13 +176,20 @@ __global__ __launch_bounds__(LN_THREADS, ln_bwd_blocks(V, HAS_LN, HAS_CS || (ROW
   // raw operands of one row (HAS_LN): x, residual gradient, packed dy, statistics
   f32x4 nx[V], ngr[V];
   u32x2 ndy[V];
+  u32x2 nbr[V];                                     // LS: the row's packed branch image
   float nmu = 0.f, nrs = 0.f, nmuB = 0.f, nrsB = 0.f;
   float nsc = 1.f, nscB = 1.f;                      // ROWS: scale of the row (PAIR: of the pair's two rows); rows < 2^31
   auto fetch = [&](long long row) {
     if (!HAS_LN || row >= rows) return;
-    if constexpr (ROWS) {
+    if constexpr (ROWS && !LS) {
       nsc = rowscale[(PAIR ? 2u * (unsigned)row : (unsigned)row) / rows_per_group];
       if constexpr (PAIR) nscB = rowscale[(2u * (unsigned)row + 1u) / rows_per_group];
+    }
+    if constexpr (LS) {
+      if (rowscale) {                               // kernel-argument uniform: LayerScale without drop path keeps the ones
+        nsc = rowscale[(PAIR ? 2u * (unsigned)row : (unsigned)row) / rows_per_group];
+        if constexpr (PAIR) nscB = rowscale[(2u * (unsigned)row + 1u) / rows_per_group];
+      }
     }
     if constexpr (PAIR) {
       nmu = mean[2 * row];
@@ -166,6 +206,9 @@ __global__ __launch_bounds__(LN_THREADS, ln_bwd_blocks(V, HAS_LN, HAS_CS || (ROW
       if (c4 < c4n) {
         if (g_res) ngr[v] = *(const f32x4*)(g_res + row * cols + 4 * c4);
         ndy[v] = *(const u32x2*)(dy + row * cols + 4 * c4);
+        if constexpr (LS) {
+          if (dls) nbr[v] = *(const u32x2*)(branch + row * cols + 4 * c4);
+        }
         nx[v] = *(const f32x4*)(x + row * cols + 4 * c4);
       }
     }
@@ -174,11 +217,15 @@ __global__ __launch_bounds__(LN_THREADS, ln_bwd_blocks(V, HAS_LN, HAS_CS || (ROW
   fetch((long long)blockIdx.x * 4 + wave);
   for (long long row = (long long)blockIdx.x * 4 + wave; row < rows; row += row_step) {
     f32x4 dx[V];
+    u32x2 brp[V];                                   // LS: the branch image of this row (taken before the next row's fetch)
     float sc = 1.f, scB = 1.f;
     // (mask + cast form: no prefetch to ride on.  A row belongs to one wave, so the index is made wave-uniform and the scale comes
     // through the scalar cache: as a vector load at the loop head it made every row wait for the previous row's stores first,
     // +16 us at 50432 x 768)
-    if constexpr (ROWS && !HAS_LN) sc = rowscale[__builtin_amdgcn_readfirstlane((unsigned)row / rows_per_group)];
+    if constexpr (ROWS && !HAS_LN && !LS) sc = rowscale[__builtin_amdgcn_readfirstlane((unsigned)row / rows_per_group)];
+    if constexpr (LS && !HAS_LN) {
+      if (rowscale) sc = rowscale[__builtin_amdgcn_readfirstlane((unsigned)row / rows_per_group)];
+    }
     if constexpr (ROWS && HAS_LN) {
       sc = nsc;
       scB = nscB;
@@ -192,6 +239,10 @@ __global__ __launch_bounds__(LN_THREADS, ln_bwd_blocks(V, HAS_LN, HAS_CS || (ROW
         xh[v] = nx[v];
         gr[v] = ngr[v];
         dyp[v] = ndy[v];
+      }
+      if constexpr (LS) {
+#pragma unroll
+        for (int v = 0; v < V; ++v) brp[v] = nbr[v];
       }
       fetch(row + row_step);                      // in flight during everything below
       float s1 = 0.f, s2 = 0.f, s1B = 0.f, s2B = 0.f;
@@ -235,6 +286,9 @@ __global__ __launch_bounds__(LN_THREADS, ln_bwd_blocks(V, HAS_LN, HAS_CS || (ROW
       for (int v = 0; v < V; ++v) {
         const int c4 = lane + 64 * v;
         if (c4 < c4n) dx[v] = *(const f32x4*)(g_res + row * cols + 4 * c4);
+        if constexpr (LS) {
+          if (dls && c4 < c4n) brp[v] = *(const u32x2*)(branch + row * cols + 4 * c4);
+        }
       }
     }
     if (gm || (Q8 && gm8)) {
@@ -250,6 +304,15 @@ __global__ __launch_bounds__(LN_THREADS, ln_bwd_blocks(V, HAS_LN, HAS_CS || (ROW
             for (int r = 0; r < 4; ++r) o[r] = keep[r] ? o[r] * dk.scale : 0.f;
           }
           if constexpr (ROWS) o *= hi[v] ? scB : sc;
+          if constexpr (LS) {
+            o *= lsg[v];
+            if (dls) {                             // d gamma: rs * g_out * u; a dropped sample (rs == 0) adds exact zeros
+              const float rsv = hi[v] ? scB : sc;
+              const f32x4 u = {bf_lo(brp[v][0]), bf_hi(brp[v][0]), bf_lo(brp[v][1]), bf_hi(brp[v][1])};
+#pragma unroll
+              for (int r = 0; r < 4; ++r) acc_ls[v][r] += rsv == 0.f ? 0.f : rsv * dx[v][r] * u[r];
+            }
+          }
           if (gm) {                              // fp8 path: the bf16 image is optional
             u32x2 w = {pack_bf2(o[0], o[1]), pack_bf2(o[2], o[3])};
             *(u32x2*)(gm + row * cols + 4 * c4) = w;
@@ -272,16 +335,22 @@ __global__ __launch_bounds__(LN_THREADS, ln_bwd_blocks(V, HAS_LN, HAS_CS || (ROW
   }
   // cross-wave column reduction into this block's slot row of each sum (LDS buffer reused); launch_ln_bwd sums the slots
 #pragma unroll
-  for (int qty = 0; qty < 3; ++qty) {
+  for (int qty = 0; qty < (LS ? 4 : 3); ++qty) {
     if (qty < 2 && !HAS_LN) continue;
     if (qty == 2 && !HAS_CS) continue;
     float* target = qty == 0 ? dgamma : (qty == 1 ? dbeta : gm_colsum);
+    if constexpr (LS) {
+      if (qty == 3) target = dls;
+    }
     if (!target) continue;   // kernel-argument uniform
 #pragma unroll
     for (int v = 0; v < V; ++v) {
       const int c4 = lane + 64 * v;
       if (c4 < c4n) {
-        const f32x4 a = qty == 0 ? acc_dg[v] : (qty == 1 ? acc_db[v] : acc_cs[v]);
+        f32x4 a = qty == 0 ? acc_dg[v] : (qty == 1 ? acc_db[v] : acc_cs[v]);
+        if constexpr (LS) {
+          if (qty == 3) a = acc_ls[v];
+        }
         *(f32x4*)&red[wave][4 * c4] = a;
       }
     }
@@ -350,6 +419,54 @@ int launch_ln_bwd_rows(const void* dy, const float* x, const float* mean, const 
 #undef VS_LNR
   VS_CHECK_LAUNCH("layernorm_bwd_rows");
   return VITSSL_OK;
+}
+
+// LayerScale (include/vitssl_layerscale.h): the launches of launch_ln_bwd_rows for the LS instantiations (always built with the
+// column sums; gm_colsum, the row scales and dls may be absent at run time), then the four sums' slot rows added in one pass.
+template <bool HAS_LN>
+int launch_ln_bwd_ls(const char* who, const void* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
+                     const float* g_res, float* g_out, void* gm, float* dgamma, float* dbeta, float* gm_colsum, vitssl_dropout_t drop,
+                     const vitssl_rowscale_t* rsc, const float* lsgamma, const void* branch, float* dls, int64_t rows, int cols,
+                     float* workspace, int64_t workspace_floats, hipStream_t s) {
+  DropKey dk = make_drop_key(drop);
+  const int on = dk.thr != 0;
+  VS_CHECK_ARG(!on || (unsigned long long)rows * (unsigned long long)cols < (1ull << 34),
+               "%s: the dropout stream's group counter is 32 bits (rows * cols < 2^34)", who);
+  const bool pair = HAS_LN && cols == 384 && (rows & 1) == 0;
+  const int grid = pair ? ln_grid(rows / 2, false, 768) : ln_grid(rows, false, cols);
+  const long long slab = (long long)grid * cols;
+  const bool sums = (HAS_LN && (dgamma || dbeta)) || gm_colsum || dls;
+  float *pg = nullptr, *pb = nullptr, *pc = nullptr, *pl = nullptr;
+  if (sums) {
+    const long long promised = vitssl_layerscale_workspace_floats(rows, cols);
+    VS_CHECK_ARG(4 * slab <= promised, "%s: this launch needs %lld floats of workspace, vitssl_layerscale_workspace_floats(%lld, %d) promises %lld",
+                 who, 4 * slab, (long long)rows, cols, promised);
+    float* parts = vs_parts(workspace, workspace_floats, promised, who, "vitssl_layerscale_workspace_floats");
+    if (!parts) return VITSSL_ERR_ARG;
+    pg = HAS_LN && dgamma ? parts : nullptr;
+    pb = HAS_LN && dbeta ? parts + slab : nullptr;
+    pc = gm_colsum ? parts + 2 * slab : nullptr;
+    pl = dls ? parts + 3 * slab : nullptr;
+  }
+  const float* rscale = rsc ? rsc->scale : nullptr;
+  const unsigned rpg = rsc ? (unsigned)rsc->rows_per_group : 1u;
+  const LnLsArgs lsa = {lsgamma, (const bf16_t*)branch, pl};
+#define VS_LNL(V, PAIR, GRID, ROWS_, COLS_)                                                                                          \
+  hipLaunchKernelGGL((ln_bwd_kernel<V, HAS_LN, true, false, PAIR, true, LnLsArgs>), dim3(GRID), dim3(LN_THREADS), 0, s,              \
+                     (const bf16_t*)dy, x, mean, rstd, gamma, g_res, g_out, (bf16_t*)gm, pg, pb, pc, dk, on, (long long)(ROWS_), COLS_, \
+                     (unsigned char*)nullptr, (const float*)nullptr, (float*)nullptr, rscale, rpg, lsa)
+  if (pair) {
+    if constexpr (HAS_LN) VS_LNL(3, true, grid, rows / 2, 768);      // two rows per wave, as the plain entry
+  } else if (cols <= 256) VS_LNL(1, false, grid, rows, cols);
+  else if (cols <= 512) VS_LNL(2, false, grid, rows, cols);
+  else if (cols <= 768) VS_LNL(3, false, grid, rows, cols);
+  else if (cols <= 1024) VS_LNL(4, false, grid, rows, cols);
+  else VS_LNL(8, false, grid, rows, cols);
+#undef VS_LNL
+  VS_CHECK_LAUNCH(who);
+  if (!sums) return VITSSL_OK;
+  return vs_reduce_parts(VsSums{{pg ? dgamma : nullptr, pb ? dbeta : nullptr, pc ? gm_colsum : nullptr, pl ? dls : nullptr}, {pg, pb, pc, pl}},
+                         grid, cols, cols, s);
 }
 
 template <bool HAS_LN, bool Q8 = false>
@@ -531,4 +648,37 @@ extern "C" int vitssl_grad_mask_cast_rows(const float* g, void* gm_bf16, float* 
   if (int rc = check_rowscale("grad_mask_cast_rows", rowscale, rows)) return rc;
   return launch_ln_bwd<false>(nullptr, nullptr, nullptr, nullptr, nullptr, g, nullptr, gm_bf16, nullptr, nullptr, gm_colsum, drop,
                               rows, cols, workspace, workspace_floats, (hipStream_t)stream, nullptr, nullptr, nullptr, rowscale);
+}
+
+// ---- LayerScale: the same two contracts with the bf16 operand also scaled per column, and gamma's gradient (include/vitssl_layerscale.h)
+static int check_ls(const char* who, const vitssl_rowscale_t* rowscale, const vitssl_colscale_t* colscale, const void* branch,
+                    const float* dls, int64_t rows, int cols) {
+  VS_CHECK_ARG(rows > 0 && cols > 0 && cols % 4 == 0 && cols <= 2048, "%s: cols=%d must be a multiple of 4 and <= 2048", who, cols);
+  VS_CHECK_ARG(rows < (1ll << 31), "%s: rows = %lld outside rows < 2^31", who, (long long)rows);
+  VS_CHECK_ARG(colscale && colscale->gamma, "%s: null column scales", who);
+  VS_CHECK_ARG(colscale->cols == cols, "%s: column scales hold %d entries for %d columns", who, colscale->cols, cols);
+  VS_CHECK_ARG((branch != nullptr) == (dls != nullptr), "%s: branch_bf16 and dls are given together or not at all", who);
+  if (rowscale) return check_rowscale(who, rowscale, rows);
+  return VITSSL_OK;
+}
+
+extern "C" int vitssl_layernorm_bwd_ls(const void* dy_bf16, const float* x, const float* mean, const float* rstd, const float* gamma,
+                                       const float* g_res, float* g_out, void* gm_bf16, float* dgamma, float* dbeta, float* gm_colsum,
+                                       vitssl_dropout_t drop, const vitssl_rowscale_t* rowscale, const vitssl_colscale_t* colscale,
+                                       const void* branch_bf16, float* dls, int64_t rows, int cols, float* workspace,
+                                       int64_t workspace_floats, void* stream) {
+  VS_CHECK_ARG(dy_bf16 && x && mean && rstd && gamma && g_out && dgamma && dbeta && gm_bf16, "layernorm_bwd_ls: null pointer");
+  if (int rc = check_ls("layernorm_bwd_ls", rowscale, colscale, branch_bf16, dls, rows, cols)) return rc;
+  return launch_ln_bwd_ls<true>("layernorm_bwd_ls", dy_bf16, x, mean, rstd, gamma, g_res, g_out, gm_bf16, dgamma, dbeta, gm_colsum, drop,
+                                rowscale, colscale->gamma, branch_bf16, dls, rows, cols, workspace, workspace_floats, (hipStream_t)stream);
+}
+
+extern "C" int vitssl_grad_mask_cast_ls(const float* g, void* gm_bf16, float* gm_colsum, vitssl_dropout_t drop,
+                                        const vitssl_rowscale_t* rowscale, const vitssl_colscale_t* colscale, const void* branch_bf16,
+                                        float* dls, int64_t rows, int cols, float* workspace, int64_t workspace_floats, void* stream) {
+  VS_CHECK_ARG(g && gm_bf16, "grad_mask_cast_ls: null pointer");
+  if (int rc = check_ls("grad_mask_cast_ls", rowscale, colscale, branch_bf16, dls, rows, cols)) return rc;
+  return launch_ln_bwd_ls<false>("grad_mask_cast_ls", nullptr, nullptr, nullptr, nullptr, nullptr, g, nullptr, gm_bf16, nullptr, nullptr,
+                                 gm_colsum, drop, rowscale, colscale->gamma, branch_bf16, dls, rows, cols, workspace, workspace_floats,
+                                 (hipStream_t)stream);
 }

@@ -103,6 +103,9 @@ def build_model(config):
     rate = cfg_get(config, "model", "drop_path_rate")      # optional: stochastic depth (absent or 0: the models as they always were)
     if rate:
         backbone["drop_path_rate"] = float(rate)
+    init = cfg_get(config, "model", "layer_scale_init")    # optional: LayerScale (absent or null: no new parameter, key or launch)
+    if init is not None:
+        backbone["layer_scale_init"] = init                # (checked by the models: a finite float > 0, else ValueError)
     makers = {
         "supervised": lambda: ViT(num_classes=m("num_classes"), **backbone),
         "simmim": lambda: SimMIMViT(mask_ratio=m("mask_ratio"), **backbone),

@@ -8,7 +8,7 @@ constructor signature and `state_dict` keys and runs its forward and backward th
 tensors on the CPU are rejected -- there is no fallback path.
 """
 from .attention import MultiHeadedAttention, ScaledDotProductAttention
-from .encoder_block import EncoderBlock
+from .encoder_block import EncoderBlock, LayerScale
 from .feed_forward import FeedForwardBlock
 from .patch_embedding import (
     ConvolutionalPatchEmbedding,
@@ -20,6 +20,7 @@ from .vit import ViT
 __all__ = [
     "ViT",
     "EncoderBlock",
+    "LayerScale",
     "FeedForwardBlock",
     "MultiHeadedAttention",
     "ScaledDotProductAttention",

@@ -9,7 +9,7 @@ from ._runtime import BF16, F32, L, ops
 
 class BackboneRuntime:
     def __init__(self, store, prefix: str, embed_names: dict, num_blocks: int, in_ch: int, patch: int, grid, D: int, H: int,
-                 Fd: int, p_drop: float, site_base: int = 0, drop_path=None):
+                 Fd: int, p_drop: float, site_base: int = 0, drop_path=None, layer_scale: bool = False):
         """embed_names: {'weight','bias','cls','pos'} -> parameter names (relative to the
         store) of the patch projection, CLS token and positional embedding."""
         self.store, self.prefix = store, prefix
@@ -20,7 +20,7 @@ class BackboneRuntime:
         self.Pd, self.Pdp = self.geo.Pd, self.geo.Pdp
         self.T0 = grid[0] * grid[1] + 1
         blocks = [f"{prefix}encoder_blocks.{i}." for i in range(num_blocks)]
-        self.stack = R.EncoderStack(store, blocks, D, H, Fd, p_drop, site_base=site_base, drop_path=drop_path)
+        self.stack = R.EncoderStack(store, blocks, D, H, Fd, p_drop, site_base=site_base, drop_path=drop_path, layer_scale=layer_scale)
         self.wkey = prefix + "patch_proj"
         if self.geo.native:
             store.register_weight(self.wkey, lambda: store.view(embed_names["weight"], (D, self.Pd)), transposed_too=False)

@@ -394,10 +394,10 @@ class _StackFn(Function):
 class StackRunner:
     """A private FlatStore + EncoderStack for a module that owns encoder blocks."""
 
-    def __init__(self, module, block_prefixes, D, H, Fd, p, device, drop_path=None):
+    def __init__(self, module, block_prefixes, D, H, Fd, p, device, drop_path=None, layer_scale=False):
         self.module = module
         self.store = R.FlatStore(module, device)
-        self.stack = R.EncoderStack(self.store, block_prefixes, D, H, Fd, p, drop_path=drop_path)
+        self.stack = R.EncoderStack(self.store, block_prefixes, D, H, Fd, p, drop_path=drop_path, layer_scale=layer_scale)
         self.device = device
         self._slots = 0
         self._gen = 0

@@ -7,7 +7,7 @@ is updated inside forward (before the loss sees it, also in eval), as in the ref
 under data parallelism its batch mean is all-reduced so every rank keeps the same centre.
 """
 import copy
-from typing import List
+from typing import List, Optional
 
 import torch
 import torch.distributed as dist
@@ -17,7 +17,7 @@ from torch.autograd import Function
 from ... import _runtime as R
 from ..._runtime import BF16, F32, L, ops
 from ..._backbone import BackboneRuntime
-from ...encoder_block import EncoderBlock
+from ...encoder_block import EncoderBlock, check_layer_scale_init
 from ...patch_embedding import DynamicPatchEmbedding
 from ._head_runtime import HeadRuntime
 from .head import DINOHead
@@ -28,12 +28,14 @@ class ViTBackbone(nn.Module):
     (reference: ssl/dino/model.py:12-45).  Parameter container inside DINOViT; usable on its
     own through the modules' stand-alone paths."""
 
-    def __init__(self, num_blocks, input_shape, embed_dim, patch_size, num_heads=8, mlp_dim=3072, dropout=0.1,
-                 drop_path_rate: float = 0.0):
+    def __init__(self, num_blocks, input_shape, embed_dim, patch_size, num_heads=8, mlp_dim=3072, dropout=0.1, *,
+                 layer_scale_init: Optional[float] = None, drop_path_rate: float = 0.0):
         super().__init__()
+        self.layer_scale_init = check_layer_scale_init(layer_scale_init)      # LayerScale: None = none of it; else a finite float > 0
         self.drop_path_rate = float(drop_path_rate)      # read by the owning runtime (DINOViT: the student's only); not a parameter
         rates = R.drop_path_rates(self.drop_path_rate, num_blocks)      # (the blocks run one by one when the backbone is called on its own)
-        self.encoder_blocks = nn.ModuleList([EncoderBlock(embed_dim, num_heads, mlp_dim, dropout, drop_path=r) for r in rates])
+        self.encoder_blocks = nn.ModuleList([EncoderBlock(embed_dim, num_heads, mlp_dim, dropout, layer_scale_init=self.layer_scale_init,
+                                                          drop_path=r) for r in rates])
         self.patch_embedding = DynamicPatchEmbedding(input_shape, embed_dim, patch_size)
 
     def forward(self, x: torch.Tensor, return_attn=False):
@@ -61,7 +63,8 @@ class _DINORuntime:
             self.stores[who] = st
             self.bb[who] = BackboneRuntime(st, pre, names, model.num_blocks, C, P, grid, D, model.num_heads, model.mlp_dim,
                                            model.dropout_p,
-                                           drop_path=R.drop_path_rates(model.drop_path_rate, model.num_blocks) if who == "student" else None)
+                                           drop_path=R.drop_path_rates(model.drop_path_rate, model.num_blocks) if who == "student" else None,
+                                           layer_scale=model.layer_scale_init is not None)
             self.head[who] = HeadRuntime(st, f"{who}_head.", D, K)
         if self.stores["teacher"].numel != self.stores["student"].numel:
             raise L.VitsslError("DINOViT: teacher and student parameter layouts differ")
@@ -160,11 +163,16 @@ class DINOViT(nn.Module):
         dropout: float = 0.1,
         output_dim: int = 65536,
         center_momentum: float = 0.9,
+        *,
+        layer_scale_init: Optional[float] = None,
         drop_path_rate: float = 0.0,
     ):
         super().__init__()
         self.center_momentum = center_momentum
-        self.teacher_backbone = ViTBackbone(num_blocks, input_shape, embed_dim, patch_size, num_heads, mlp_dim, dropout)
+        # LayerScale in the student AND the teacher (whose gammas follow the EMA like every parameter); None: none of it
+        self.layer_scale_init = check_layer_scale_init(layer_scale_init)
+        self.teacher_backbone = ViTBackbone(num_blocks, input_shape, embed_dim, patch_size, num_heads, mlp_dim, dropout,
+                                            layer_scale_init=self.layer_scale_init)
         self.student_backbone = copy.deepcopy(self.teacher_backbone)
         self.teacher_head = DINOHead(embed_dim, output_dim)
         self.student_head = DINOHead(embed_dim, output_dim)

@@ -13,13 +13,15 @@ Two ways to train:
     overlapped RCCL gradient all-reduce and flat AdamW with no autograd graph at all
     (what utils.trainers.SimMIMTrainer and bench.py use).
 """
+from typing import Optional
+
 import torch
 from torch import nn
 from torch.autograd import Function
 
 from ... import _runtime as R
 from ..._runtime import BF16, F32, L, ops
-from ...encoder_block import EncoderBlock
+from ...encoder_block import EncoderBlock, check_layer_scale_init
 from .masking import draw_mask, mask_indices_np
 
 
@@ -40,7 +42,8 @@ class _SimMIMRuntime:
         st = self.store
         prefixes = [f"encoder_blocks.{i}." for i in range(len(model.encoder_blocks))]
         self.stack = R.EncoderStack(st, prefixes, self.D, model.num_heads, model.mlp_dim, model.dropout_p,
-                                    drop_path=R.drop_path_rates(model.drop_path_rate, len(prefixes)))
+                                    drop_path=R.drop_path_rates(model.drop_path_rate, len(prefixes)),
+                                    layer_scale=model.layer_scale_init is not None)
         if self.geo.native:
             st.register_weight("proj", lambda: st.view("projection.weight", (self.D, self.Pd)), transposed_too=False)
             st.register_weight("head", lambda: st.view("simmim_head.weight", (self.Pd, self.D)))
@@ -236,11 +239,14 @@ class SimMIMViT(nn.Module):
         mlp_dim: int = 3072,
         dropout: float = 0.1,
         mask_ratio: float = 0.6,
+        *,
+        layer_scale_init: Optional[float] = None,
         drop_path_rate: float = 0.0,
     ):
         super().__init__()
+        self.layer_scale_init = check_layer_scale_init(layer_scale_init)      # LayerScale: None = none of it; else a finite float > 0
         self.encoder_blocks = nn.ModuleList(
-            [EncoderBlock(embed_dim, num_heads, mlp_dim, dropout) for _ in range(num_blocks)]
+            [EncoderBlock(embed_dim, num_heads, mlp_dim, dropout, layer_scale_init=self.layer_scale_init) for _ in range(num_blocks)]
         )
         self.unfold = nn.Unfold(kernel_size=(patch_size, patch_size), stride=patch_size)
         self.projection = nn.Linear((input_shape[0] * patch_size * patch_size), embed_dim)

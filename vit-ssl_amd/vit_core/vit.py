@@ -9,6 +9,8 @@ Two ways to train, as for SimMIMViT:
 Both run the one classification head of `_ViTRuntime` (`forward` / `loss` / `backward`: workspace buffers, GEMM operands cached
 on the store's `weights_key()`); `_ViTFn` only slices and copies the logits out and pads the incoming gradient.  The runtime keeps
 the activations of ONE saving forward, whichever path made it: a backward through an older graph raises VitsslError."""
+from typing import Optional
+
 import torch
 from torch import nn
 from torch.autograd import Function
@@ -16,7 +18,7 @@ from torch.autograd import Function
 from . import _runtime as R
 from ._runtime import BF16, F32, L, _round_up, ops
 from ._backbone import BackboneRuntime
-from .encoder_block import EncoderBlock
+from .encoder_block import EncoderBlock, check_layer_scale_init
 from .mlp_head import MLPHead
 from .patch_embedding import ConvolutionalPatchEmbedding
 
@@ -33,7 +35,8 @@ class _ViTRuntime:
             st, "", dict(weight="patch_embedding.conv.weight", bias="patch_embedding.conv.bias",
                          cls="patch_embedding.cls_token", pos="patch_embedding.positional_embedding"),
             len(model.encoder_blocks), C, P, (Hh // P, Ww // P), self.D, model.num_heads, model.mlp_dim, model.dropout_p,
-            drop_path=R.drop_path_rates(model.drop_path_rate, len(model.encoder_blocks)))
+            drop_path=R.drop_path_rates(model.drop_path_rate, len(model.encoder_blocks)),
+            layer_scale=model.layer_scale_init is not None)
         self.ncls = model.num_classes
         self.rec = None                   # what the last saving forward keeps of the head for its backward
         self.save_gen = 0                 # id of that forward
@@ -196,11 +199,15 @@ class ViT(nn.Module):
         num_heads: int = 8,
         mlp_dim: int = 3072,
         dropout: float = 0.1,
+        *,
+        layer_scale_init: Optional[float] = None,
         drop_path_rate: float = 0.0,
     ):
         super().__init__()
+        # LayerScale (timm's init_values): None = no new parameter, key or launch; else a finite float > 0 (ValueError otherwise)
+        self.layer_scale_init = check_layer_scale_init(layer_scale_init)
         self.encoder_blocks = nn.ModuleList(
-            [EncoderBlock(embed_dim, num_heads, mlp_dim, dropout) for _ in range(num_blocks)]
+            [EncoderBlock(embed_dim, num_heads, mlp_dim, dropout, layer_scale_init=self.layer_scale_init) for _ in range(num_blocks)]
         )
         self.patch_embedding = ConvolutionalPatchEmbedding(input_shape, embed_dim, patch_size)
         self.classification_head = MLPHead(embed_dim, num_classes)

@@ -16,6 +16,7 @@ PATCH_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", 
 OPTIM_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "vitssl_optim.h"))
 MIXUP_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "vitssl_mixup.h"))
 DROPPATH_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "vitssl_droppath.h"))
+LAYERSCALE_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "vitssl_layerscale.h"))
 
 
 class VitsslError(RuntimeError):
@@ -50,6 +51,11 @@ class OptimSegment(C.Structure):
 class RowScale(C.Structure):
     """vitssl_rowscale_t"""
     _fields_ = [("scale", C.c_void_p), ("groups", C.c_int64), ("rows_per_group", C.c_int)]
+
+
+class ColScale(C.Structure):
+    """vitssl_colscale_t"""
+    _fields_ = [("gamma", C.c_void_p), ("cols", C.c_int)]
 
 
 class Gemm(C.Structure):
@@ -188,6 +194,16 @@ PROTOTYPES_DROPPATH = {
     "vitssl_grad_mask_cast_rows": [_vp, _vp, _vp, Dropout, C.POINTER(RowScale), _i64, _i, _vp, _i64, _vp],
 }
 
+# include/vitssl_layerscale.h (LayerScale: the column-scaled forms of the residual GEMM and of the two kernels that emit the masked
+# gradient operand, which also sum gamma's gradient), and the workspace query of those two, which returns an int64 count instead of a status (lib() below).
+PROTOTYPES_LAYERSCALE = {
+    "vitssl_gemm_bf16_nt_ls": [C.POINTER(Gemm), C.POINTER(ColScale), C.POINTER(RowScale), _vp, _vp],
+    "vitssl_layernorm_bwd_ls": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, Dropout, C.POINTER(RowScale), C.POINTER(ColScale),
+                                _vp, _vp, _i64, _i, _vp, _i64, _vp],
+    "vitssl_grad_mask_cast_ls": [_vp, _vp, _vp, Dropout, C.POINTER(RowScale), C.POINTER(ColScale), _vp, _vp, _i64, _i, _vp, _i64, _vp],
+    "vitssl_layerscale_workspace_floats": [C.c_int64, C.c_int],
+}
+
 _lib = None
 
 
@@ -255,6 +271,14 @@ def droppath_header_symbols():
     return sorted(set(re.findall(r"\b(vitssl_[a-z0-9_]+)\s*\(", txt)))
 
 
+def layerscale_header_symbols():
+    """Entry points declared in include/vitssl_layerscale.h (the launching ones and the workspace query)."""
+    with open(LAYERSCALE_HEADER_PATH) as f:
+        txt = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)        # the comments name functions of the other headers
+    txt = re.sub(r"^\s*#.*$", "", txt, flags=re.M)
+    return sorted(set(re.findall(r"\b(vitssl_[a-z0-9_]+)\s*\(", txt)))
+
+
 def lib():
     global _lib
     if _lib is not None:
@@ -309,10 +333,12 @@ def lib():
         getattr(l, sizing).argtypes = [C.c_int]
     for name, args in (list(PROTOTYPES.items()) + list(PROTOTYPES_TRANSFORMS.items()) + list(PROTOTYPES_METRICS.items())
                        + list(PROTOTYPES_CLASSIFY.items()) + list(PROTOTYPES_ATTENTION_HD.items()) + list(PROTOTYPES_PATCH.items())
-                       + list(PROTOTYPES_OPTIM.items()) + list(PROTOTYPES_MIXUP.items()) + list(PROTOTYPES_DROPPATH.items())):
+                       + list(PROTOTYPES_OPTIM.items()) + list(PROTOTYPES_MIXUP.items()) + list(PROTOTYPES_DROPPATH.items())
+                       + list(PROTOTYPES_LAYERSCALE.items())):
         fn = getattr(l, name)  # AttributeError if the symbol is missing
         fn.restype = C.c_int
         fn.argtypes = args
+    l.vitssl_layerscale_workspace_floats.restype = C.c_int64
     _lib = l
     return l
 

@@ -517,10 +517,15 @@ class EncoderStack:
 
     `drop_path` (stochastic depth, include/vitssl_droppath.h): per-block probabilities with which a training forward drops a
     whole sample from the block's attention branch and, drawn independently, from its MLP branch; survivors are scaled by
-    1 / (1 - rate).  None or all zeros: nothing of it is launched.  bf16 operands only."""
+    1 / (1 - rate).  None or all zeros: nothing of it is launched.  bf16 operands only.
+
+    `layer_scale` (LayerScale, include/vitssl_layerscale.h): the store holds `<block>layer_scale1.gamma` and
+    `<block>layer_scale2.gamma` (f32 [D]) and every forward, in every mode, multiplies the attention branch by the first and the
+    MLP branch by the second, per channel; a saving forward also keeps the two branches as bf16 images (2 * L * M * D * 2 bytes),
+    from which the backward sums gamma's gradients.  False: nothing of it is launched.  bf16 operands only."""
 
     def __init__(self, store: FlatStore, block_prefixes: List[str], D: int, H: int, F: int, p_drop: float,
-                 site_base: int = 0, drop_path: Optional[List[float]] = None):
+                 site_base: int = 0, drop_path: Optional[List[float]] = None, layer_scale: bool = False):
         if D % H != 0:
             raise AssertionError(f"d_model({D}) must be cleanly divisible by num_heads({H})!")
         self.store = store
@@ -543,6 +548,17 @@ class EncoderStack:
                                 "(set_linear_operands('bf16') or VITSSL_LINEAR_OPERANDS=bf16) or drop_path_rate = 0")
         if self.drop_path is not None and 2 * self.L > L.DROPPATH_MAX_SITES:
             raise L.VitsslError(f"drop path covers up to {L.DROPPATH_MAX_SITES // 2} blocks a stack, got {self.L}")
+        self.layer_scale = bool(layer_scale)
+        if self.layer_scale:
+            if self.fp8:
+                raise L.VitsslError("LayerScale (layer_scale_init) is built for bf16 linear operands only: use bf16 operands "
+                                    "(set_linear_operands('bf16') or VITSSL_LINEAR_OPERANDS=bf16) or leave layer_scale_init out")
+            for b in self.bp:
+                for leaf in ("layer_scale1.gamma", "layer_scale2.gamma"):
+                    if b + leaf not in store.offsets:
+                        raise L.VitsslError(f"LayerScale: the store holds no parameter {b + leaf!r}")
+                    if store.offsets[b + leaf][1] != D:
+                        raise L.VitsslError(f"LayerScale: {b + leaf!r} holds {store.offsets[b + leaf][1]} values, expected embed_dim = {D}")
         if self.fp8 and (D % 128 != 0 or F % 128 != 0):
             raise L.VitsslError(f"fp8 linear operands need embed_dim ({D}) and mlp_dim ({F}) to be multiples of 128")
         for b in self.bp:
@@ -629,9 +645,13 @@ class EncoderStack:
         rec["dp"] = dp
         # (a block whose rate is 0 -- the first one of every schedule -- keeps the plain launches: its rows of the table are ones)
         rows = lambda i, br: (dp[2 * i + br], T) if dp is not None and self.drop_path[i] > 0.0 else None      # noqa: E731
+        # LayerScale: both residual launches of every block take the column-scaled entry; only a saving forward writes the branches
+        ls = lambda i, k, branch: dict(cols=st.view(self._n(i, f"layer_scale{k}.gamma")), branch=branch) if self.layer_scale else {}   # noqa: E731
         cur = x
         for i in range(self.L):
             tag = f"{slot}.{i}." if save else f"{slot}.tmp."
+            ls1 = g(tag + "ls1", (M, D), BF16, dev) if self.layer_scale and save else None
+            ls2 = g(tag + "ls2", (M, D), BF16, dev) if self.layer_scale and save else None
             h1 = None if self.fp8 else g(tag + "h1", (M, D), BF16, dev)
             mean1 = g(tag + "mean1", (M,), F32, dev)
             rstd1 = g(tag + "rstd1", (M,), F32, dev)
@@ -672,16 +692,19 @@ class EncoderStack:
                 ops.layernorm_fwd(*ln1, h1, mean1, rstd1)
                 ops.gemm_nt(h1, st.w(self._n(i, "wqkv")), qkv, L.EPI_BF16)
                 ops.attn_fwd_any(qkv, att, lse, B, T, H, dh, probs=probs if i == self.L - 1 else None)
-                ops.gemm_nt(att, st.w(self._n(i, "wo")), xmid, L.EPI_RESID, aux=cur, drop=self._drop(i, 0, seed, training), rows=rows(i, 0))
+                ops.gemm_nt(att, st.w(self._n(i, "wo")), xmid, L.EPI_RESID, aux=cur, drop=self._drop(i, 0, seed, training), rows=rows(i, 0),
+                            **ls(i, 1, ls1))
                 ops.layernorm_fwd(*ln2, h2, mean2, rstd2)
                 ops.gemm_nt(h2, st.w(self._n(i, "w1")), u, L.EPI_GELU, bias=b1, out1=a, drop=self._drop(i, 1, seed, training))
                 ops.gemm_nt(a, st.w(self._n(i, "w2")), xout, L.EPI_RESID, bias=b2, aux=xmid, drop=self._drop(i, 2, seed, training),
-                            rows=rows(i, 1))
+                            rows=rows(i, 1), **ls(i, 2, ls2))
             if save:
                 rec["blocks"].append(dict(xin=cur, h1=h1, mean1=mean1, rstd1=rstd1, qkv=qkv, att=att, lse=lse, xmid=xmid,
                                           h2=h2, mean2=mean2, rstd2=rstd2, u=u, a=a))
                 if self.fp8:
                     rec["blocks"][-1].update(h1_8=h1_8, att8=att8, h2_8=h2_8, a8=a8)
+                if self.layer_scale:
+                    rec["blocks"][-1].update(ls1=ls1, ls2=ls2)
             cur = xout
         if save:
             self._saved[slot] = rec
@@ -724,9 +747,20 @@ class EncoderStack:
         dp = rec.get("dp")      # drop path: the forward's table; the masked operand of a branch takes the branch's row of it
         rows = lambda i, br: (dp[2 * i + br], T) if dp is not None and self.drop_path[i] > 0.0 else None      # noqa: E731
         gm2 = w(bw + "gm2", (M, D), BF16, dev) if batch and wgrad else gm
+
+        def ls(i, k):
+            """LayerScale arguments of the kernel that emits the masked operand of branch k of block i: gamma, and (unless the
+            blocks are frozen) the saved branch and the slot of gamma's gradient."""
+            if not self.layer_scale:
+                return {}
+            name = self._n(i, f"layer_scale{k}.gamma")
+            if not wgrad:
+                return dict(cols=st.view(name))
+            return dict(cols=st.view(name), branch=rec["blocks"][i][f"ls{k}"], dls=gv(name))
+
         # top of the chain: dropout-mask + cast of g, and the last block's linear_out bias grad
         ops.grad_mask_cast(g, gm, gv(self._n(last, "feed_forward.linear_out.bias")), self._drop(last, 2, seed, training),
-                           rows=rows(last, 1))
+                           rows=rows(last, 1), **ls(last, 2))
         for i in range(last, -1, -1):
             s = rec["blocks"][i]
             a_ = self.bp[i] + "self_attention."
@@ -744,7 +778,7 @@ class EncoderStack:
                 ops.gemm_tn(*wgrads[1])
             ops.layernorm_bwd(dh_, s["xmid"], s["mean2"], s["rstd2"], st.view(self._n(i, "layer_norm2.weight")), g, g, gm2,
                               gv(self._n(i, "layer_norm2.weight")), gv(self._n(i, "layer_norm2.bias")), None,
-                              self._drop(i, 0, seed, training), rows=rows(i, 0))
+                              self._drop(i, 0, seed, training), rows=rows(i, 0), **ls(i, 1))
             # attention
             ops.gemm_nt(gm2, st.w(self._n(i, "wo") + ".T"), dh_, L.EPI_BF16)
             if wgrad and not batch:
@@ -759,13 +793,16 @@ class EncoderStack:
                 ops.layernorm_bwd(dh_, s["xin"], s["mean1"], s["rstd1"], st.view(self._n(i, "layer_norm1.weight")), g, g, gm,
                                   gv(self._n(i, "layer_norm1.weight")), gv(self._n(i, "layer_norm1.bias")),
                                   gv(self._n(i - 1, "feed_forward.linear_out.bias")), self._drop(i - 1, 2, seed, training),
-                                  rows=rows(i - 1, 1))
+                                  rows=rows(i - 1, 1), **ls(i - 1, 2))
             else:
                 ops.layernorm_bwd(dh_, s["xin"], s["mean1"], s["rstd1"], st.view(self._n(i, "layer_norm1.weight")), g, g, None,
                                   gv(self._n(i, "layer_norm1.weight")), gv(self._n(i, "layer_norm1.bias")), None, ops.NO_DROP)
             if reducer is not None and wgrad:
                 # every gradient of block i is final, except linear_out.bias of block i-1,
-                # which belongs to the next (lower) range
+                # which belongs to the next (lower) range.  (LayerScale: layer_scale1.gamma of block i came from this block's
+                # LayerNorm-2 backward, layer_scale2.gamma of block i from the LayerNorm-1 backward of block i + 1 -- or from the
+                # top grad_mask_cast -- before that block's range was handed over; the launch just above wrote layer_scale2.gamma
+                # of block i - 1, which like its linear_out.bias belongs to the next range.)
                 lo, hi = self.block_span(i)
                 reducer.ready(lo, hi)
         return g

@@ -154,8 +154,45 @@ def _rowscale(rows, M, name):
     return r
 
 
-def layernorm_bwd(dy, x, mean, rstd, gamma, g_res, g_out, gm, dgamma, dbeta, gm_colsum=None, drop=NO_DROP, rows=None):
-    """rows=(scale, rows_per_group): vitssl_layernorm_bwd_rows, the bf16 operand `gm` scaled per row (drop path)."""
+def _colscale(cols, N, name):
+    """vitssl_colscale_t of cols = gamma f32 [N]: column n of the [*, N] operand takes gamma[n] (LayerScale)."""
+    c = L.ColScale()
+    c.gamma = _chk(cols, F32, name + " cols(gamma)", (N,))
+    c.cols = N
+    return c
+
+
+def _ls_ws(device, rows, cols):
+    """(pointer, floats) of scratch for the LayerScale backward entry points (vitssl_layerscale_workspace_floats)."""
+    ws = _tn_workspace(device, int(L.lib().vitssl_layerscale_workspace_floats(rows, cols)))
+    return C.c_void_p(ws.data_ptr()), ws.numel()
+
+
+def _ls_args(cols, branch, dls, rows_t, M, N, name):
+    """(rowscale or NULL, colscale, branch, dls) of a LayerScale backward launch; branch and dls come together or not at all."""
+    if (branch is None) != (dls is None):
+        raise L.VitsslError(f"{name}: branch= and dls= are given together (gamma's gradient) or both left out")
+    rs = C.byref(_rowscale(rows_t, M, name)) if rows_t is not None else None
+    return rs, C.byref(_colscale(cols, N, name)), _opt(branch, BF16, name + " branch", (M, N)), _opt(dls, F32, name + " dls", (N,))
+
+
+def layernorm_bwd(dy, x, mean, rstd, gamma, g_res, g_out, gm, dgamma, dbeta, gm_colsum=None, drop=NO_DROP, rows=None, cols=None,
+                  branch=None, dls=None):
+    """rows=(scale, rows_per_group): vitssl_layernorm_bwd_rows, the bf16 operand `gm` scaled per row (drop path).
+    cols=gamma f32 [cols]: vitssl_layernorm_bwd_ls (LayerScale), `gm` also scaled per column; with branch= (the forward's bf16
+    image of the branch) and dls= (f32 [cols]) gamma's gradient is accumulated into dls.  Composes with rows=."""
+    if cols is not None:
+        M, N = x.shape
+        ls = _ls_args(cols, branch, dls, rows, M, N, "layernorm_bwd")
+        ev = _prof_begin()
+        call("vitssl_layernorm_bwd_ls", _chk(dy, BF16, "dy", (M, N)), _chk(x, F32, "x"), _chk(mean, F32, "mean", (M,)),
+             _chk(rstd, F32, "rstd", (M,)), _chk(gamma, F32, "gamma", (N,)), _opt(g_res, F32, "g_res", (M, N)),
+             _chk(g_out, F32, "g_out", (M, N)), _chk(gm, BF16, "gm", (M, N)), _chk(dgamma, F32, "dgamma", (N,)),
+             _chk(dbeta, F32, "dbeta", (N,)), _opt(gm_colsum, F32, "gm_colsum", (N,)), drop, *ls, M, N, *_ls_ws(x.device, M, N), _stream())
+        _prof_end(ev, "ln_bwd", 0.0, M * (N * (2 + 4 + (4 if g_res is not None else 0) + 4 + 2 + (2 if branch is not None else 0)) + 8))
+        return
+    if branch is not None or dls is not None:
+        raise L.VitsslError("layernorm_bwd: branch= / dls= belong to cols= (LayerScale)")
     rs = () if rows is None else (C.byref(_rowscale(rows, x.shape[0], "layernorm_bwd")),)
     rows, cols = x.shape
     ev = _prof_begin()
@@ -169,8 +206,17 @@ def layernorm_bwd(dy, x, mean, rstd, gamma, g_res, g_out, gm, dgamma, dbeta, gm_
     _prof_end(ev, "ln_bwd", 0.0, rows * (cols * (2 + 4 + (4 if g_res is not None else 0) + 4 + (2 if gm is not None else 0)) + 8))
 
 
-def grad_mask_cast(g, gm, gm_colsum=None, drop=NO_DROP, rows=None):
-    """rows=(scale, rows_per_group): vitssl_grad_mask_cast_rows, `gm` scaled per row (drop path)."""
+def grad_mask_cast(g, gm, gm_colsum=None, drop=NO_DROP, rows=None, cols=None, branch=None, dls=None):
+    """rows=(scale, rows_per_group): vitssl_grad_mask_cast_rows, `gm` scaled per row (drop path).
+    cols=gamma (with branch= and dls= for gamma's gradient): vitssl_grad_mask_cast_ls (LayerScale); composes with rows=."""
+    if cols is not None:
+        M, N = g.shape
+        ls = _ls_args(cols, branch, dls, rows, M, N, "grad_mask_cast")
+        call("vitssl_grad_mask_cast_ls", _chk(g, F32, "g"), _chk(gm, BF16, "gm", (M, N)), _opt(gm_colsum, F32, "gm_colsum", (N,)), drop,
+             *ls, M, N, *_ls_ws(g.device, M, N), _stream())
+        return
+    if branch is not None or dls is not None:
+        raise L.VitsslError("grad_mask_cast: branch= / dls= belong to cols= (LayerScale)")
     rs = () if rows is None else (C.byref(_rowscale(rows, g.shape[0], "grad_mask_cast")),)
     rows, cols = g.shape
     call("vitssl_grad_mask_cast_rows" if rs else "vitssl_grad_mask_cast", _chk(g, F32, "g"), _chk(gm, BF16, "gm", (rows, cols)),
@@ -180,9 +226,13 @@ def grad_mask_cast(g, gm, gm_colsum=None, drop=NO_DROP, rows=None):
 _OUT0_DTYPE = {L.EPI_BF16: BF16, L.EPI_F32: F32, L.EPI_GELU: BF16, L.EPI_RESID: F32, L.EPI_DGELU: BF16, L.EPI_EMBED: F32}
 
 
-def gemm_nt(A, B, out0, epilogue, bias=None, aux=None, out1=None, colsum=None, drop=NO_DROP, embed=None, rows=None):
+def gemm_nt(A, B, out0, epilogue, bias=None, aux=None, out1=None, colsum=None, drop=NO_DROP, embed=None, rows=None, cols=None,
+            branch=None):
     """out = A[M,K] @ B[N,K]^T with the fused epilogue (see include/vitssl_hip.h).  rows=(scale, rows_per_group) selects
-    vitssl_gemm_bf16_nt_rows (EPI_RESID only): out0 = aux + scale[row // rows_per_group] * drop(acc + bias)."""
+    vitssl_gemm_bf16_nt_rows (EPI_RESID only): out0 = aux + scale[row // rows_per_group] * drop(acc + bias).
+    cols=gamma f32 [N] selects vitssl_gemm_bf16_nt_ls (EPI_RESID only; LayerScale, composes with rows=):
+    out0 = aux + scale[row // rows_per_group] * gamma[col] * drop(acc + bias), and branch= (bf16 [M, N], optional) receives
+    drop(acc + bias), what the backward multiplies gamma's gradient from."""
     M, K = A.shape
     N, K2 = B.shape
     if K != K2:
@@ -218,7 +268,14 @@ def gemm_nt(A, B, out0, epilogue, bias=None, aux=None, out1=None, colsum=None, d
         g.workspace, g.workspace_floats = _sum_ws(colsum.device, M, N)
     g.drop = drop
     ev = _prof_begin()
-    if rows is not None:
+    if cols is not None:
+        if epilogue != L.EPI_RESID:
+            raise L.VitsslError(f"gemm_nt: cols= belongs to EPI_RESID, got epilogue {epilogue}")
+        call("vitssl_gemm_bf16_nt_ls", C.byref(g), C.byref(_colscale(cols, N, "gemm_nt")),
+             C.byref(_rowscale(rows, M, "gemm_nt")) if rows is not None else None, _opt(branch, BF16, "branch", (M, N)), _stream())
+    elif branch is not None:
+        raise L.VitsslError("gemm_nt: branch= belongs to cols= (LayerScale)")
+    elif rows is not None:
         if epilogue != L.EPI_RESID:
             raise L.VitsslError(f"gemm_nt: rows= belongs to EPI_RESID, got epilogue {epilogue}")
         call("vitssl_gemm_bf16_nt_rows", C.byref(g), C.byref(_rowscale(rows, M, "gemm_nt")), _stream())
