@@ -5,8 +5,9 @@ Same entry points and config keys as the reference (utils/train_utils.py:12-51:
 `optimizer`, `lr_scheduler.{main,warmup}`, `warmup_*`), different machinery: every section is
 read through `_spec` into a (name, kwargs) pair, and an AdamW request over a model that exposes
 its flat parameter store is answered with the fused flat-buffer optimizer kernel instead of
-torch.optim.AdamW; the optional keys `training.clip_grad_norm`, `training.no_weight_decay` and `training.layer_decay` reach that
-optimizer as its per-parameter settings (`_group_options`) and are refused with any other.  `get_transforms` returns callables with the reference's per-image semantics that also carry the
+torch.optim.AdamW, and a Lamb request (torch.optim has none) with the fused LAMB over the same store; the optional keys
+`training.clip_grad_norm`, `training.no_weight_decay` and `training.layer_decay` reach either fused optimizer as its per-parameter
+settings (`_group_options`) and are refused with any other.  `get_transforms` returns callables with the reference's per-image semantics that also carry the
 GPU multi-crop recipe (`.view_spec`, see `data.ViewSpec.from_config`) or, for the crop / flip / ToTensor and Resize / ToTensor
 lists, the recipe of the fused transform kernel (`.transform_spec`, see `data.TransformSpec.from_config`).
 """
@@ -23,6 +24,8 @@ from .schedulers import LinearWarmupScheduler
 
 logger = logging.getLogger(__name__)
 _FUSED_ADAMW_KEYS = {"lr", "betas", "eps", "weight_decay"}
+_FUSED_LAMB_KEYS = _FUSED_ADAMW_KEYS | {"always_adapt", "trust_clip"}
+_LAMB_NAMES = ("Lamb", "LAMB", "lamb")
 _GROUP_KEYS = ("clip_grad_norm", "no_weight_decay", "layer_decay")
 
 
@@ -156,7 +159,7 @@ def make_criterion(config):
 
 
 def _group_options(config, store):
-    """The optional keys beside `training.optimizer` as FusedAdamW's keyword arguments ({} when none is present):
+    """The optional keys beside `training.optimizer` as FusedAdamW's / FusedLamb's keyword arguments ({} when none is present):
     `clip_grad_norm` (> 0), `no_weight_decay` (true, or a list of fnmatch patterns over parameter names) and
     `layer_decay` (0 < d <= 1: lr multiplier d ** (L + 1 - layer_id), see vitssl_hip.engine.layer_id).  `store` is the
     FlatStore whose names they are keyed by, or None when only the presence of the keys is asked for."""
@@ -182,7 +185,7 @@ def _group_options(config, store):
             patterns = [str(pattern) for pattern in rule]
             exempt = {name for name in store.names if any(fnmatch.fnmatchcase(name, pattern) for pattern in patterns)}
         _, kwargs = _spec(config, "training", "optimizer")
-        decay = float(kwargs.get("weight_decay", 1e-2))
+        decay = float(kwargs.get("weight_decay", 1e-2))        # the default of both fused optimizers
         out["weight_decay_of"] = lambda name: 0.0 if name in exempt else decay
     if "layer_decay" in present:
         d = float(present["layer_decay"])
@@ -199,11 +202,22 @@ def make_optimizer(config, model):
         from vitssl_hip.optim import FusedAdamW
         store = model.trainable_store() if hasattr(model, "trainable_store") else model.flat_store()
         return FusedAdamW(store, **kwargs, **_group_options(config, store))
+    if name in _LAMB_NAMES:
+        # torch.optim has no Lamb: the fused one is the only one there is, so what it cannot take is refused here
+        if not hasattr(model, "flat_store"):
+            raise ValueError(f"training.optimizer.name = {name} is the fused LAMB (vitssl_hip.optim.FusedLamb), which steps a model's "
+                             f"flat parameter store; {type(model).__name__} has no flat_store()")
+        unknown = sorted(set(kwargs) - _FUSED_LAMB_KEYS)
+        if unknown:
+            raise ValueError(f"training.optimizer.params {unknown} are unknown to the fused LAMB; it takes {sorted(_FUSED_LAMB_KEYS)}")
+        from vitssl_hip.optim import FusedLamb
+        store = model.trainable_store() if hasattr(model, "trainable_store") else model.flat_store()
+        return FusedLamb(store, **kwargs, **_group_options(config, store))
     ignored = _group_options(config, None)
     if ignored:
-        raise ValueError(f"training.{' / training.'.join(sorted(ignored))} need the fused AdamW (optimizer name AdamW with only "
-                         f"{sorted(_FUSED_ADAMW_KEYS)} under params, over a model with a flat store); the optimizer configured here "
-                         f"is {name} with params {sorted(kwargs)}")
+        raise ValueError(f"training.{' / training.'.join(sorted(ignored))} need the fused AdamW or the fused LAMB (optimizer name AdamW "
+                         f"with only {sorted(_FUSED_ADAMW_KEYS)} under params, or Lamb with only {sorted(_FUSED_LAMB_KEYS)}, over a "
+                         f"model with a flat store); the optimizer configured here is {name} with params {sorted(kwargs)}")
     return getattr(optim, name)((p for p in model.parameters() if p.requires_grad), **kwargs)
 
 

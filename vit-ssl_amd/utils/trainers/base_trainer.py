@@ -66,8 +66,8 @@ class BaseTrainer(ABC):
         self.reducer = GradReducer(self._dp_store().gflat)
 
     def _is_fused(self) -> bool:
-        from vitssl_hip.optim import FusedAdamW
-        return isinstance(self.optimizer, FusedAdamW) and hasattr(self.model, "train_step")
+        from vitssl_hip.optim import FusedAdamW, FusedLamb
+        return isinstance(self.optimizer, (FusedAdamW, FusedLamb)) and hasattr(self.model, "train_step")
 
     def _log_grad_norm(self, epoch, values):
         """With `training.clip_grad_norm`: log the pre-clip gradient norm of the epoch's last step.  Called once per epoch where

@@ -17,6 +17,7 @@ OPTIM_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", 
 MIXUP_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "vitssl_mixup.h"))
 DROPPATH_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "vitssl_droppath.h"))
 LAYERSCALE_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "vitssl_layerscale.h"))
+LAMB_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "vitssl_lamb.h"))
 
 
 class VitsslError(RuntimeError):
@@ -204,6 +205,14 @@ PROTOTYPES_LAYERSCALE = {
     "vitssl_layerscale_workspace_floats": [C.c_int64, C.c_int],
 }
 
+# include/vitssl_lamb.h (segmented LAMB over the table of vitssl_optim.h): the launching entry point, and the host-side sizing
+# function of its workspace, which returns an int64 count instead of a status (lib() below).
+LAMB_ALWAYS_ADAPT, LAMB_TRUST_CLIP = 1, 2          # VITSSL_LAMB_ALWAYS_ADAPT, VITSSL_LAMB_TRUST_CLIP
+PROTOTYPES_LAMB = {
+    "vitssl_lamb_workspace_bytes": [C.POINTER(OptimSegment), _i],
+    "vitssl_lamb_segments": [_vp, _vp, _vp, _vp, _vp, _i, _f, _f, _f, _f, _i, _f, _vp, _f, _i, _vp, _vp, _i64, _vp],
+}
+
 _lib = None
 
 
@@ -279,6 +288,14 @@ def layerscale_header_symbols():
     return sorted(set(re.findall(r"\b(vitssl_[a-z0-9_]+)\s*\(", txt)))
 
 
+def lamb_header_symbols():
+    """Entry points declared in include/vitssl_lamb.h (the launching one and the workspace sizing function)."""
+    with open(LAMB_HEADER_PATH) as f:
+        txt = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)        # the comments name functions of the other headers
+    txt = re.sub(r"^\s*#.*$", "", txt, flags=re.M)
+    return sorted(set(re.findall(r"\b(vitssl_[a-z0-9_]+)\s*\(", txt)))
+
+
 def lib():
     global _lib
     if _lib is not None:
@@ -334,11 +351,12 @@ def lib():
     for name, args in (list(PROTOTYPES.items()) + list(PROTOTYPES_TRANSFORMS.items()) + list(PROTOTYPES_METRICS.items())
                        + list(PROTOTYPES_CLASSIFY.items()) + list(PROTOTYPES_ATTENTION_HD.items()) + list(PROTOTYPES_PATCH.items())
                        + list(PROTOTYPES_OPTIM.items()) + list(PROTOTYPES_MIXUP.items()) + list(PROTOTYPES_DROPPATH.items())
-                       + list(PROTOTYPES_LAYERSCALE.items())):
+                       + list(PROTOTYPES_LAYERSCALE.items()) + list(PROTOTYPES_LAMB.items())):
         fn = getattr(l, name)  # AttributeError if the symbol is missing
         fn.restype = C.c_int
         fn.argtypes = args
     l.vitssl_layerscale_workspace_floats.restype = C.c_int64
+    l.vitssl_lamb_workspace_bytes.restype = C.c_int64
     _lib = l
     return l
 

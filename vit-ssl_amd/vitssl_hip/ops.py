@@ -740,7 +740,9 @@ class AdamWPlan:
     """Device-resident segment table of `vitssl_adamw_segments` / `vitssl_grad_sumsq` (include/vitssl_optim.h) over a flat
     store of `numel` floats, with the workspace of the norm and its one-float result slot.  `segments`: (offset, n, lr_scale,
     weight_decay) per parameter that takes part, in ascending order; checked on the host by the library when the plan is
-    built (offsets multiples of 4 floats, no overlap, inside the store).  Built once and kept until the set of parameters changes."""
+    built (offsets multiples of 4 floats, no overlap, inside the store).  Built once and kept until the set of parameters changes.
+    `lamb_buffers()` adds, on first use, what `vitssl_lamb_segments` (include/vitssl_lamb.h) needs: its workspace and the
+    `trust` tensor [nseg]; a plan that only AdamW uses never allocates them."""
 
     def __init__(self, segments, numel, device):
         segments = [(int(o), int(n), float(s), float(w)) for o, n, s, w in segments]
@@ -754,6 +756,17 @@ class AdamWPlan:
         self.table = host.to(device)
         self.workspace = torch.empty(int(l.vitssl_grad_sumsq_workspace_bytes(self.nseg)), dtype=torch.uint8, device=device)
         self.sumsq = torch.zeros(1, dtype=F32, device=device)
+        self._rows, self.lamb_workspace, self.trust = arr, None, None
+
+    def lamb_buffers(self):
+        """(workspace, trust) of lamb_segments, allocated on the first call"""
+        if self.trust is None:
+            nbytes = int(L.lib().vitssl_lamb_workspace_bytes(self._rows, self.nseg))
+            if nbytes <= 0:
+                raise L.VitsslError(f"vitssl_lamb_workspace_bytes refused a table of {self.nseg} segments")
+            self.lamb_workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.table.device)
+            self.trust = torch.ones(self.nseg, dtype=F32, device=self.table.device)
+        return self.lamb_workspace, self.trust
 
 
 def _flat(t, name, plan):
@@ -781,6 +794,24 @@ def adamw_segments(p, g, m, v, plan, lr, beta1, beta2, eps, step, gscale=1.0, su
          _chk(plan.table, torch.uint8, "table"), plan.nseg, float(lr), float(beta1), float(beta2), float(eps), int(step), float(gscale),
          _opt(sumsq, F32, "sumsq", (1,)), float(max_norm), _stream())
     _prof_end(ev, "adamw_segments", 0.0, 28 * plan.elements)
+
+
+def lamb_segments(p, g, m, v, plan, lr, beta1, beta2, eps, step, gscale=1.0, sumsq=None, max_norm=0.0, always_adapt=False,
+                  trust_clip=False, trust=None, workspace=None):
+    """One LAMB step over the plan's segments (include/vitssl_lamb.h): the moment pass, the per-segment trust ratios and the
+    apply pass, three launches.  `sumsq` clips as in adamw_segments; g is not written.  The ratios land in `trust`
+    (default: the plan's tensor [nseg]), which is returned; reading it is the caller's synchronisation."""
+    ws0, trust0 = (None, None) if (trust is not None and workspace is not None) else plan.lamb_buffers()
+    trust = trust0 if trust is None else trust
+    ws = ws0 if workspace is None else workspace
+    flags = (L.LAMB_ALWAYS_ADAPT if always_adapt else 0) | (L.LAMB_TRUST_CLIP if trust_clip else 0)
+    ev = _prof_begin()
+    call("vitssl_lamb_segments", _flat(p, "p", plan), _flat(g, "g", plan), _flat(m, "m", plan), _flat(v, "v", plan),
+         _chk(plan.table, torch.uint8, "table"), plan.nseg, float(lr), float(beta1), float(beta2), float(eps), int(step), float(gscale),
+         _opt(sumsq, F32, "sumsq", (1,)), float(max_norm), flags, _chk(trust, F32, "trust", (plan.nseg,)),
+         _chk(ws, torch.uint8, "workspace"), ws.numel(), _stream())
+    _prof_end(ev, "lamb_segments", 0.0, 40 * plan.elements)        # moments: p, g, m, v read, m, v written; apply: p, m, v read, p written
+    return trust
 
 
 def ema(teacher, student, m):
