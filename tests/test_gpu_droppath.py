@@ -11,7 +11,11 @@
 Shapes: (B, T) = (16, 17): M = 272, sample edges inside the 16-row MFMA groups and a sample across the 256-row tile edge; (3, 197):
 M = 591, odd (the 384-column LayerNorm backward then takes one row per wave, the other two take the two-rows-per-wave path);
 (1, 64): one sample.  Seeds are chosen on the CPU so that every case has a kept and a dropped sample (asserted); with one sample that
-is two seeds, one of each kind."""
+is two seeds, one of each kind.
+
+WIDTHS: the two backward bodies once more at every edge of the launch's column-count ladder (256 / 260, 512 / 516, 1024 / 1028 and
+2048: V = 1, 2, 2, 3, 4, 8, 8) with (B, T) = (3, 5): M = 15, odd, four workgroups of which the last has three live waves; and
+384 columns with M = 10 (five row pairs) and M = 15 (no pairs)."""
 import numpy as np
 import pytest
 import torch
@@ -23,6 +27,7 @@ pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 F32, BF16 = torch.float32, torch.bfloat16
 SHAPES = [(16, 17), (3, 197), (1, 64)]
+WIDTHS = [(3, 5, c) for c in (256, 260, 512, 516, 1024, 1028, 2048)] + [(2, 5, 384), (3, 5, 384)]
 SITE = DP.site(1, 0)
 
 
@@ -260,3 +265,17 @@ def test_grad_mask_cast_rows(ops, B, T, cols, p, cs):
     ones = run((torch.ones(B, device=DEV), T))
     for a, b in zip(ones, plain):
         assert a is None or torch.equal(bits(a), bits(b))
+
+
+@pytest.mark.parametrize("cs", [True, False], ids=["colsum", "nocolsum"])
+@pytest.mark.parametrize("p", [0.0, 0.1], ids=["nodrop", "drop0.1"])
+@pytest.mark.parametrize("B,T,cols", WIDTHS, ids=str)
+def test_layernorm_bwd_rows_widths(ops, B, T, cols, p, cs):
+    test_layernorm_bwd_rows(ops, B, T, cols, p, cs)
+
+
+@pytest.mark.parametrize("cs", [True, False], ids=["colsum", "nocolsum"])
+@pytest.mark.parametrize("p", [0.0, 0.1], ids=["nodrop", "drop0.1"])
+@pytest.mark.parametrize("B,T,cols", WIDTHS, ids=str)
+def test_grad_mask_cast_rows_widths(ops, B, T, cols, p, cs):
+    test_grad_mask_cast_rows(ops, B, T, cols, p, cs)

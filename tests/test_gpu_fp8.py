@@ -98,10 +98,10 @@ def _same_e4m3(a, b):
     return (a == b) | (((a & 0x7F) == 0) & ((b & 0x7F) == 0))
 
 
-def test_layernorm_bwd_fp8_image():
+def test_layernorm_bwd_fp8_image(cols=768):
     from vitssl_hip import ops
     torch.manual_seed(6)
-    rows, cols = 500, 768
+    rows = 500
     x = torch.randn(rows, cols, device=DEV)
     dy = (torch.randn(rows, cols, device=DEV) * 1e-3).to(torch.bfloat16)
     gres = torch.randn(rows, cols, device=DEV) * 1e-3
@@ -139,7 +139,13 @@ def test_layernorm_bwd_fp8_image():
     assert abs(float(amax) - float((g * keep / 0.9).abs().max())) <= 1e-4 * float(amax)
 
 
-@pytest.mark.parametrize("cols", [128, 384, 768, 1024])
+@pytest.mark.parametrize("cols", [512, 2048])
+def test_layernorm_bwd_fp8_image_widths(cols):
+    """the same body at V = 2 and V = 8 of the launch's column-count ladder (768 above: V = 3)"""
+    test_layernorm_bwd_fp8_image(cols)
+
+
+@pytest.mark.parametrize("cols", [128, 384, 512, 768, 1024, 2048])
 def test_layernorm_fwd_fp8_images(cols):
     from vitssl_hip import ops
     torch.manual_seed(cols)

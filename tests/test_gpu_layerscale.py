@@ -11,7 +11,8 @@
 
 Shapes as in tests/test_gpu_droppath.py: (B, T) = (16, 17): M = 272, sample edges inside the 16-row MFMA groups and a sample across
 the 256-row tile edge; (3, 197): M = 591, odd (the 384-column LayerNorm backward then takes one row per wave, the other two the
-two-rows-per-wave path); (1, 64): one sample."""
+two-rows-per-wave path); (1, 64): one sample.  The two backward bodies run once more at its WIDTHS: every edge of the launch's
+column-count ladder at M = 15, and 384 columns with and without row pairs."""
 import ctypes as C
 
 import numpy as np
@@ -20,7 +21,7 @@ import torch
 
 import _gemm_exact as X
 from _util import rel_l2
-from test_gpu_droppath import SHAPES, bits, scales_for
+from test_gpu_droppath import SHAPES, WIDTHS, bits, scales_for
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -274,6 +275,22 @@ def test_grad_mask_cast_ls(ops, B, T, cols, p, cs, with_rows):
         base, ones = run(rows_arg), run(rows_arg, torch.ones(cols, device=DEV))
         for a, b in zip(ones[:2], base[:2]):
             assert a is None or torch.equal(bits(a), bits(b))
+
+
+@pytest.mark.parametrize("with_rows", [False, True], ids=["norows", "rows0.3"])
+@pytest.mark.parametrize("cs", [True, False], ids=["colsum", "nocolsum"])
+@pytest.mark.parametrize("p", [0.0, 0.1], ids=["nodrop", "drop0.1"])
+@pytest.mark.parametrize("B,T,cols", WIDTHS, ids=str)
+def test_layernorm_bwd_ls_widths(ops, B, T, cols, p, cs, with_rows):
+    test_layernorm_bwd_ls(ops, B, T, cols, p, cs, with_rows)
+
+
+@pytest.mark.parametrize("with_rows", [False, True], ids=["norows", "rows0.3"])
+@pytest.mark.parametrize("cs", [True, False], ids=["colsum", "nocolsum"])
+@pytest.mark.parametrize("p", [0.0, 0.1], ids=["nodrop", "drop0.1"])
+@pytest.mark.parametrize("B,T,cols", WIDTHS, ids=str)
+def test_grad_mask_cast_ls_widths(ops, B, T, cols, p, cs, with_rows):
+    test_grad_mask_cast_ls(ops, B, T, cols, p, cs, with_rows)
 
 
 def test_backward_entries_refuse_bad_arguments(ops, L):

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """sha256 of the losses and of the flat parameter buffer after 4 seeded steps of tiny models, with the losses themselves to 9
-digits, one line per case: the three fused train_steps (ViT in its three backward schedules) and ViT through autograd.  Two
-commits that print the same lines compute the same thing bit for bit (dropout 0.1 included: its seeds come from
-torch.manual_seed).
+digits, one line per case: the three fused train_steps (ViT in its three backward schedules) and ViT through autograd, then
+SimMIM again with drop path, with LayerScale, with both, and with fp8 linear operands (the other forms of the LayerNorm
+backward launch).  Two commits that print the same lines compute the same thing bit for bit (dropout 0.1 included: its seeds
+come from torch.manual_seed).
 
 usage: python tools/step_digest.py"""
 import hashlib
@@ -35,13 +36,18 @@ def images(n, size, seed):
     return torch.rand(n, 3, size, size, generator=torch.Generator().manual_seed(seed)).to(DEV)
 
 
-def simmim():
+def simmim(name="simmim", operands="bf16", **extra):
     from vit_core.ssl.simmim.model import SimMIMViT
+    from vitssl_hip.engine import set_linear_operands
     from vitssl_hip.optim import FusedAdamW
     torch.manual_seed(1)
-    m = SimMIMViT(**TINY).to(DEV).train()
-    opt, x = FusedAdamW(m.flat_store(), lr=1e-3, weight_decay=1e-2), images(8, 32, 2)
-    report("simmim", [m.train_step(x, opt) for _ in range(STEPS)], m.flat_store())
+    set_linear_operands(operands)          # read when the model's encoder stack is built
+    try:
+        m = SimMIMViT(**TINY, **extra).to(DEV).train()
+        opt, x = FusedAdamW(m.flat_store(), lr=1e-3, weight_decay=1e-2), images(8, 32, 2)
+        report(name, [m.train_step(x, opt) for _ in range(STEPS)], m.flat_store())
+    finally:
+        set_linear_operands("bf16")
 
 
 def dino():
@@ -88,3 +94,7 @@ if __name__ == "__main__":
         vit(s)
     vit("autograd", 10)
     vit("autograd", 64)
+    simmim("simmim droppath", drop_path_rate=0.1)
+    simmim("simmim layerscale", layer_scale_init=1e-5)
+    simmim("simmim dp+ls", drop_path_rate=0.1, layer_scale_init=1e-5)
+    simmim("simmim fp8", operands="fp8")

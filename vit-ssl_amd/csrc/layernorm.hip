@@ -8,8 +8,10 @@
 // of the new residual gradient, and the dropout-masked bf16 copy the next
 // (reverse-order) GEMM consumes; per column: dgamma, dbeta and the bias-gradient
 // column sum are accumulated in registers across the rows a wave visits, reduced
-// across the block's 4 waves in LDS and added to global with one atomic per column
-// per block.
+// across the block's 4 waves in LDS and stored to the block's slot row of the caller's
+// workspace; a reduce launch then adds the slot rows to the targets in a fixed order
+// (common.h, deterministic sums).  Every backward entry point goes through the one
+// launch_ln_bwd below, which alone decides the grid and so the slot layout.
 #include "../../include/vitssl_droppath.h"
 #include "../../include/vitssl_layerscale.h"
 #include "common.h"
@@ -384,163 +386,116 @@ inline int ln_grid(long long rows, bool fwd = false, int cols = 1024) {
   return (int)g;
 }
 
-// The launches of launch_ln_bwd_parts below for the ROWS instantiations: the same column-count paths, the 384-column row pairs
-// included, the same grids (so the slot rows of the sums are laid out as launch_ln_bwd expects).
-template <bool HAS_LN>
-int launch_ln_bwd_rows(const void* dy, const float* x, const float* mean, const float* rstd, const float* gamma, const float* g_res,
-                       float* g_out, void* gm, float* dgamma, float* dbeta, float* gm_colsum, DropKey dk, int on, int64_t rows, int cols,
-                       hipStream_t s, vitssl_rowscale_t rsc) {
-  const unsigned rpg = (unsigned)rsc.rows_per_group;
-#define VS_LNR(V, CS, PAIR, GRID, ROWS_, COLS_)                                                                                     \
-  hipLaunchKernelGGL((ln_bwd_kernel<V, HAS_LN, CS, false, PAIR, true>), dim3(GRID), dim3(LN_THREADS), 0, s, (const bf16_t*)dy, x, mean, \
-                     rstd, gamma, g_res, g_out, (bf16_t*)gm, dgamma, dbeta, gm_colsum, dk, on, (long long)(ROWS_), COLS_,             \
-                     (unsigned char*)nullptr, (const float*)nullptr, (float*)nullptr, rsc.scale, rpg)
-  if constexpr (HAS_LN) {
-    if (cols == 384 && (rows & 1) == 0) {            // two rows per wave (PAIR)
-      const int pgrid = ln_grid(rows / 2, false, 768);
-      if (gm_colsum) VS_LNR(3, true, true, pgrid, rows / 2, 768);
-      else VS_LNR(3, false, true, pgrid, rows / 2, 768);
-      VS_CHECK_LAUNCH("layernorm_bwd_rows");
-      return VITSSL_OK;
-    }
-  }
-  const int grid = ln_grid(rows, false, cols);
-#define VS_LNRV(V)                                          \
-  do {                                                      \
-    if (gm_colsum) VS_LNR(V, true, false, grid, rows, cols); \
-    else VS_LNR(V, false, false, grid, rows, cols);          \
-  } while (0)
-  if (cols <= 256) VS_LNRV(1);
-  else if (cols <= 512) VS_LNRV(2);
-  else if (cols <= 768) VS_LNRV(3);
-  else if (cols <= 1024) VS_LNRV(4);
-  else VS_LNRV(8);
-#undef VS_LNRV
-#undef VS_LNR
-  VS_CHECK_LAUNCH("layernorm_bwd_rows");
-  return VITSSL_OK;
-}
+// One call of any backward entry point.  The form -- HAS_LN, Q8 (the fp8 triple), ROWS (row scales) and LS (the LayerScale triple) --
+// is the entry point's compile-time choice; the members a form does not take stay null.
+struct LnBwdCall {
+  const char* who;                                  // the name the entry point's messages carry
+  const void* dy;
+  const float *x, *mean, *rstd, *gamma, *g_res;
+  float* g_out;
+  void* gm;
+  float *dgamma, *dbeta, *gm_colsum;
+  vitssl_dropout_t drop;
+  int64_t rows;
+  int cols;
+  float* workspace;
+  int64_t workspace_floats;
+  hipStream_t s;
+  void* gm8;                                        // Q8
+  const float* qscale;
+  float* qamax;
+  const vitssl_rowscale_t* rowscale;                // ROWS (LS: or NULL)
+  const float* lsgamma;                             // LS
+  const void* branch;
+  float* dls;
+};
 
-// LayerScale (include/vitssl_layerscale.h): the launches of launch_ln_bwd_rows for the LS instantiations (always built with the
-// column sums; gm_colsum, the row scales and dls may be absent at run time), then the four sums' slot rows added in one pass.
-template <bool HAS_LN>
-int launch_ln_bwd_ls(const char* who, const void* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
-                     const float* g_res, float* g_out, void* gm, float* dgamma, float* dbeta, float* gm_colsum, vitssl_dropout_t drop,
-                     const vitssl_rowscale_t* rsc, const float* lsgamma, const void* branch, float* dls, int64_t rows, int cols,
-                     float* workspace, int64_t workspace_floats, hipStream_t s) {
-  DropKey dk = make_drop_key(drop);
+// The launch path of every backward form.  The kernel writes one slot row per block for each column sum (dgamma, dbeta, gm_colsum
+// and, with LayerScale, dls); they are then added to the targets in a fixed order (common.h, deterministic sums).  The grid, and
+// with it the layout of the slot rows, is decided here and nowhere else.  What is built: row pairs (PAIR) for the bf16 image of
+// the LayerNorm form at V = 3 only; LayerScale with the column sums and the row scales only (gm_colsum, the row scales and dls may
+// be absent at run time).
+template <bool HAS_LN, bool Q8 = false, bool ROWS = false, bool LS = false>
+int launch_ln_bwd(const LnBwdCall& c) {
+  static_assert(!Q8 || !ROWS, "row scales are built for the bf16 image");
+  static_assert(!LS || ROWS, "LayerScale is built on the form with row scales");
+  const int64_t rows = c.rows;
+  const int cols = c.cols;
+  DropKey dk = make_drop_key(c.drop);
   const int on = dk.thr != 0;
   VS_CHECK_ARG(!on || (unsigned long long)rows * (unsigned long long)cols < (1ull << 34),
-               "%s: the dropout stream's group counter is 32 bits (rows * cols < 2^34)", who);
-  const bool pair = HAS_LN && cols == 384 && (rows & 1) == 0;
-  const int grid = pair ? ln_grid(rows / 2, false, 768) : ln_grid(rows, false, cols);
+               "%s: the dropout stream's group counter is 32 bits (rows * cols < 2^34)", c.who);
+  constexpr bool CAN_PAIR = HAS_LN && !Q8;
+  const bool pair = CAN_PAIR && cols == 384 && (rows & 1) == 0;   // two rows per wave: the kernel sees rows / 2 rows of 768 columns
+  const long long krows = pair ? rows / 2 : rows;
+  const int kcols = pair ? 768 : cols;
+  const int grid = ln_grid(krows, false, kcols);
   const long long slab = (long long)grid * cols;
-  const bool sums = (HAS_LN && (dgamma || dbeta)) || gm_colsum || dls;
-  float *pg = nullptr, *pb = nullptr, *pc = nullptr, *pl = nullptr;
-  if (sums) {
-    const long long promised = vitssl_layerscale_workspace_floats(rows, cols);
-    VS_CHECK_ARG(4 * slab <= promised, "%s: this launch needs %lld floats of workspace, vitssl_layerscale_workspace_floats(%lld, %d) promises %lld",
-                 who, 4 * slab, (long long)rows, cols, promised);
-    float* parts = vs_parts(workspace, workspace_floats, promised, who, "vitssl_layerscale_workspace_floats");
+
+  constexpr int NSUMS = LS ? 4 : 3;
+  float* const target[4] = {HAS_LN ? c.dgamma : nullptr, HAS_LN ? c.dbeta : nullptr, c.gm_colsum, LS ? c.dls : nullptr};
+  float* slot[4] = {nullptr, nullptr, nullptr, nullptr};
+  const bool sums = target[0] || target[1] || target[2] || target[3];
+  if (sums) {                                       // the documented promise is what the caller's workspace is held to (vs_sum_parts)
+    const char* sizing = LS ? "vitssl_layerscale_workspace_floats" : "vitssl_sum_workspace_floats";
+    const long long promised = LS ? vitssl_layerscale_workspace_floats(rows, cols) : vitssl_sum_workspace_floats(rows, cols);
+    VS_CHECK_ARG(NSUMS * slab <= promised, "%s: this launch needs %lld floats of workspace, %s(%lld, %d) promises %lld", c.who,
+                 NSUMS * slab, sizing, (long long)rows, cols, promised);
+    float* parts = vs_parts(c.workspace, c.workspace_floats, promised, c.who, sizing);
     if (!parts) return VITSSL_ERR_ARG;
-    pg = HAS_LN && dgamma ? parts : nullptr;
-    pb = HAS_LN && dbeta ? parts + slab : nullptr;
-    pc = gm_colsum ? parts + 2 * slab : nullptr;
-    pl = dls ? parts + 3 * slab : nullptr;
+    for (int q = 0; q < NSUMS; ++q)
+      if (target[q]) slot[q] = parts + q * slab;
   }
-  const float* rscale = rsc ? rsc->scale : nullptr;
-  const unsigned rpg = rsc ? (unsigned)rsc->rows_per_group : 1u;
-  const LnLsArgs lsa = {lsgamma, (const bf16_t*)branch, pl};
-#define VS_LNL(V, PAIR, GRID, ROWS_, COLS_)                                                                                          \
-  hipLaunchKernelGGL((ln_bwd_kernel<V, HAS_LN, true, false, PAIR, true, LnLsArgs>), dim3(GRID), dim3(LN_THREADS), 0, s,              \
-                     (const bf16_t*)dy, x, mean, rstd, gamma, g_res, g_out, (bf16_t*)gm, pg, pb, pc, dk, on, (long long)(ROWS_), COLS_, \
-                     (unsigned char*)nullptr, (const float*)nullptr, (float*)nullptr, rscale, rpg, lsa)
+
+  const float* rscale = c.rowscale ? c.rowscale->scale : nullptr;
+  const unsigned rpg = c.rowscale ? (unsigned)c.rowscale->rows_per_group : 1u;
+#define VS_LN_BWD_ARGS                                                                                                              \
+  dim3(grid), dim3(LN_THREADS), 0, c.s, (const bf16_t*)c.dy, c.x, c.mean, c.rstd, c.gamma, c.g_res, c.g_out, (bf16_t*)c.gm, slot[0], \
+      slot[1], slot[2], dk, on, krows, kcols, (unsigned char*)c.gm8, c.qscale, c.qamax, rscale, rpg
+  auto launch = [&](auto v, auto cs, auto pr) {
+    constexpr int V = decltype(v)::value;
+    constexpr bool CS = decltype(cs)::value, PAIR = decltype(pr)::value;
+    static_assert(!PAIR || (CAN_PAIR && V == 3), "row pairs: the LayerNorm form with a bf16 image, 2 x 384 columns");
+    static_assert(!LS || CS, "LayerScale is built with the column sums");
+    if constexpr (LS)
+      hipLaunchKernelGGL((ln_bwd_kernel<V, HAS_LN, CS, Q8, PAIR, ROWS, LnLsArgs>), VS_LN_BWD_ARGS,
+                         LnLsArgs{c.lsgamma, (const bf16_t*)c.branch, slot[3]});
+    else
+      hipLaunchKernelGGL((ln_bwd_kernel<V, HAS_LN, CS, Q8, PAIR, ROWS>), VS_LN_BWD_ARGS);
+  };
+#undef VS_LN_BWD_ARGS
+  auto with_cs = [&](auto v, auto pr) {
+    if (LS || c.gm_colsum) launch(v, std::true_type{}, pr);
+    else if constexpr (!LS) launch(v, std::false_type{}, pr);
+  };
+  using std::integral_constant;
   if (pair) {
-    if constexpr (HAS_LN) VS_LNL(3, true, grid, rows / 2, 768);      // two rows per wave, as the plain entry
-  } else if (cols <= 256) VS_LNL(1, false, grid, rows, cols);
-  else if (cols <= 512) VS_LNL(2, false, grid, rows, cols);
-  else if (cols <= 768) VS_LNL(3, false, grid, rows, cols);
-  else if (cols <= 1024) VS_LNL(4, false, grid, rows, cols);
-  else VS_LNL(8, false, grid, rows, cols);
-#undef VS_LNL
-  VS_CHECK_LAUNCH(who);
+    if constexpr (CAN_PAIR) with_cs(integral_constant<int, 3>{}, std::true_type{});
+  } else if (cols <= 256) with_cs(integral_constant<int, 1>{}, std::false_type{});
+  else if (cols <= 512) with_cs(integral_constant<int, 2>{}, std::false_type{});
+  else if (cols <= 768) with_cs(integral_constant<int, 3>{}, std::false_type{});
+  else if (cols <= 1024) with_cs(integral_constant<int, 4>{}, std::false_type{});
+  else with_cs(integral_constant<int, 8>{}, std::false_type{});
+  VS_CHECK_LAUNCH(LS ? c.who : (ROWS ? "layernorm_bwd_rows" : "layernorm_bwd"));
   if (!sums) return VITSSL_OK;
-  return vs_reduce_parts(VsSums{{pg ? dgamma : nullptr, pb ? dbeta : nullptr, pc ? gm_colsum : nullptr, pl ? dls : nullptr}, {pg, pb, pc, pl}},
-                         grid, cols, cols, s);
+  return vs_reduce_parts(VsSums{{target[0], target[1], target[2], target[3]}, {slot[0], slot[1], slot[2], slot[3]}}, grid, cols, cols, c.s);
 }
 
-template <bool HAS_LN, bool Q8 = false>
-int launch_ln_bwd_parts(const void* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
-                  const float* g_res, float* g_out, void* gm, float* dgamma, float* dbeta, float* gm_colsum,
-                  vitssl_dropout_t drop, int64_t rows, int cols, hipStream_t s, void* gm8 = nullptr,
-                  const float* qscale = nullptr, float* qamax = nullptr, const vitssl_rowscale_t* rsc = nullptr) {
-  DropKey dk = make_drop_key(drop);
-  const int on = dk.thr != 0;
-  VS_CHECK_ARG(!on || (unsigned long long)rows * (unsigned long long)cols < (1ull << 34),
-               "layernorm_bwd / grad_mask_cast: the dropout stream's group counter is 32 bits (rows * cols < 2^34)");
-  if constexpr (!Q8) {
-    if (rsc) return launch_ln_bwd_rows<HAS_LN>(dy, x, mean, rstd, gamma, g_res, g_out, gm, dgamma, dbeta, gm_colsum, dk, on, rows, cols, s, *rsc);
-  }
-  if constexpr (HAS_LN && !Q8) {
-    if (cols == 384 && (rows & 1) == 0) {            // two rows per wave (PAIR)
-      const int pgrid = ln_grid(rows / 2, false, 768);
-      if (gm_colsum)
-        hipLaunchKernelGGL((ln_bwd_kernel<3, true, true, false, true>), dim3(pgrid), dim3(LN_THREADS), 0, s, (const bf16_t*)dy, x, mean,
-                           rstd, gamma, g_res, g_out, (bf16_t*)gm, dgamma, dbeta, gm_colsum, dk, on, (long long)(rows / 2), 768,
-                           (unsigned char*)nullptr, (const float*)nullptr, (float*)nullptr);
-      else
-        hipLaunchKernelGGL((ln_bwd_kernel<3, true, false, false, true>), dim3(pgrid), dim3(LN_THREADS), 0, s, (const bf16_t*)dy, x, mean,
-                           rstd, gamma, g_res, g_out, (bf16_t*)gm, dgamma, dbeta, gm_colsum, dk, on, (long long)(rows / 2), 768,
-                           (unsigned char*)nullptr, (const float*)nullptr, (float*)nullptr);
-      VS_CHECK_LAUNCH("layernorm_bwd");
-      return VITSSL_OK;
-    }
-  }
-  const int grid = ln_grid(rows, false, cols);
-#define VS_LNB(V)                                                                                                        \
-  do {                                                                                                                   \
-    if (gm_colsum)                                                                                                       \
-      hipLaunchKernelGGL((ln_bwd_kernel<V, HAS_LN, true, Q8>), dim3(grid), dim3(LN_THREADS), 0, s, (const bf16_t*)dy, x, mean, \
-                         rstd, gamma, g_res, g_out, (bf16_t*)gm, dgamma, dbeta, gm_colsum, dk, on, (long long)rows, cols,  \
-                         (unsigned char*)gm8, qscale, qamax);                                                            \
-    else                                                                                                                 \
-      hipLaunchKernelGGL((ln_bwd_kernel<V, HAS_LN, false, Q8>), dim3(grid), dim3(LN_THREADS), 0, s, (const bf16_t*)dy, x, mean, \
-                         rstd, gamma, g_res, g_out, (bf16_t*)gm, dgamma, dbeta, gm_colsum, dk, on, (long long)rows, cols,  \
-                         (unsigned char*)gm8, qscale, qamax);                                                            \
-  } while (0)
-  if (cols <= 256) VS_LNB(1);
-  else if (cols <= 512) VS_LNB(2);
-  else if (cols <= 768) VS_LNB(3);
-  else if (cols <= 1024) VS_LNB(4);
-  else VS_LNB(8);
-#undef VS_LNB
-  VS_CHECK_LAUNCH("layernorm_bwd");
+template <bool Q8>
+int launch_ln_fwd(const char* who, const float* x, const float* gamma, const float* beta, void* y_bf16, void* y_fp8, float* mean,
+                  float* rstd, int64_t rows, int cols, float eps, hipStream_t s) {
+  const int grid = ln_grid(rows, true);
+#define VS_LNF(V)                                                                                                                 \
+  hipLaunchKernelGGL((ln_fwd_kernel<V, Q8>), dim3(grid), dim3(LN_THREADS), 0, s, x, gamma, beta, (bf16_t*)y_bf16, mean, rstd, \
+                     (long long)rows, cols, eps, (unsigned char*)y_fp8)
+  if (cols <= 256) VS_LNF(1);
+  else if (cols <= 512) VS_LNF(2);
+  else if (cols <= 768) VS_LNF(3);
+  else if (cols <= 1024) VS_LNF(4);
+  else VS_LNF(8);
+#undef VS_LNF
+  VS_CHECK_LAUNCH(who);
   return VITSSL_OK;
-}
-
-// The kernel writes one slot row per block for each column sum (dgamma, dbeta, gm_colsum); they are then added to the targets
-// in a fixed order (common.h, deterministic sums).
-template <bool HAS_LN, bool Q8 = false>
-int launch_ln_bwd(const void* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
-                  const float* g_res, float* g_out, void* gm, float* dgamma, float* dbeta, float* gm_colsum,
-                  vitssl_dropout_t drop, int64_t rows, int cols, float* workspace, int64_t workspace_floats, hipStream_t s,
-                  void* gm8 = nullptr, const float* qscale = nullptr, float* qamax = nullptr, const vitssl_rowscale_t* rsc = nullptr) {
-  const bool pair = HAS_LN && !Q8 && cols == 384 && (rows & 1) == 0;
-  const int grid = pair ? ln_grid(rows / 2, false, 768) : ln_grid(rows, false, cols);
-  const long long slab = (long long)grid * cols;
-  if (!((HAS_LN && (dgamma || dbeta)) || gm_colsum))
-    return launch_ln_bwd_parts<HAS_LN, Q8>(dy, x, mean, rstd, gamma, g_res, g_out, gm, nullptr, nullptr, nullptr, drop, rows, cols, s, gm8,
-                                           qscale, qamax, rsc);
-  float* parts = vs_sum_parts(workspace, workspace_floats, 3 * slab, rows, cols, "layernorm_bwd / grad_mask_cast");
-  if (!parts) return VITSSL_ERR_ARG;
-  float* pg = HAS_LN && dgamma ? parts : nullptr;
-  float* pb = HAS_LN && dbeta ? parts + slab : nullptr;
-  float* pc = gm_colsum ? parts + 2 * slab : nullptr;
-  const int rc = launch_ln_bwd_parts<HAS_LN, Q8>(dy, x, mean, rstd, gamma, g_res, g_out, gm, pg, pb, pc, drop, rows, cols, s, gm8,
-                                                 qscale, qamax, rsc);
-  if (rc != VITSSL_OK) return rc;
-  return vs_reduce_parts(VsSums{{pg ? dgamma : nullptr, pb ? dbeta : nullptr, pc ? gm_colsum : nullptr}, {pg, pb, pc}}, grid, cols,
-                         cols, s);
 }
 
 }  // namespace
@@ -549,78 +504,20 @@ extern "C" int vitssl_layernorm_fwd(const float* x, const float* gamma, const fl
                                     float* rstd, int64_t rows, int cols, float eps, void* stream) {
   VS_CHECK_ARG(x && gamma && beta && y_bf16 && mean && rstd, "layernorm_fwd: null pointer");
   VS_CHECK_ARG(rows > 0 && cols > 0 && cols % 4 == 0 && cols <= 2048, "layernorm_fwd: cols=%d must be a multiple of 4 and <= 2048", cols);
-  hipStream_t s = (hipStream_t)stream;
-  const int grid = ln_grid(rows, true);
-#define VS_LNF(V)                                                                                                   \
-  hipLaunchKernelGGL((ln_fwd_kernel<V, false>), dim3(grid), dim3(LN_THREADS), 0, s, x, gamma, beta, (bf16_t*)y_bf16, mean, rstd, \
-                     (long long)rows, cols, eps, (unsigned char*)nullptr)
-  if (cols <= 256) VS_LNF(1);
-  else if (cols <= 512) VS_LNF(2);
-  else if (cols <= 768) VS_LNF(3);
-  else if (cols <= 1024) VS_LNF(4);
-  else VS_LNF(8);
-#undef VS_LNF
-  VS_CHECK_LAUNCH("layernorm_fwd");
-  return VITSSL_OK;
+  return launch_ln_fwd<false>("layernorm_fwd", x, gamma, beta, y_bf16, nullptr, mean, rstd, rows, cols, eps, (hipStream_t)stream);
 }
 
 extern "C" int vitssl_layernorm_fwd_fp8(const float* x, const float* gamma, const float* beta, void* y_bf16, void* y_fp8,
                                         float* mean, float* rstd, int64_t rows, int cols, float eps, void* stream) {
   VS_CHECK_ARG(x && gamma && beta && y_fp8 && mean && rstd, "layernorm_fwd_fp8: null pointer");   // y_bf16 may be NULL
   VS_CHECK_ARG(rows > 0 && cols > 0 && cols % 4 == 0 && cols <= 2048, "layernorm_fwd_fp8: cols=%d must be a multiple of 4 and <= 2048", cols);
-  const int grid = ln_grid(rows, true);
-  hipStream_t s = (hipStream_t)stream;
-#define VS_LNF(V)                                                                                                         \
-  hipLaunchKernelGGL((ln_fwd_kernel<V, true>), dim3(grid), dim3(LN_THREADS), 0, s, x, gamma, beta, (bf16_t*)y_bf16, mean, rstd, \
-                     (long long)rows, cols, eps, (unsigned char*)y_fp8)
-  if (cols <= 256) VS_LNF(1);
-  else if (cols <= 512) VS_LNF(2);
-  else if (cols <= 768) VS_LNF(3);
-  else if (cols <= 1024) VS_LNF(4);
-  else VS_LNF(8);
-#undef VS_LNF
-  VS_CHECK_LAUNCH("layernorm_fwd_fp8");
-  return VITSSL_OK;
+  return launch_ln_fwd<true>("layernorm_fwd_fp8", x, gamma, beta, y_bf16, y_fp8, mean, rstd, rows, cols, eps, (hipStream_t)stream);
 }
 
-extern "C" int vitssl_layernorm_bwd(const void* dy_bf16, const float* x, const float* mean, const float* rstd,
-                                    const float* gamma, const float* g_res, float* g_out, void* gm_bf16, float* dgamma,
-                                    float* dbeta, float* gm_colsum, vitssl_dropout_t drop, int64_t rows, int cols,
-                                    float* workspace, int64_t workspace_floats, void* stream) {
-  VS_CHECK_ARG(dy_bf16 && x && mean && rstd && gamma && g_out && dgamma && dbeta, "layernorm_bwd: null pointer");
-  VS_CHECK_ARG(rows > 0 && cols > 0 && cols % 4 == 0 && cols <= 2048, "layernorm_bwd: cols=%d must be a multiple of 4 and <= 2048", cols);
-  VS_CHECK_ARG(!gm_colsum || gm_bf16, "layernorm_bwd: gm_colsum without gm_bf16");
-  return launch_ln_bwd<true>(dy_bf16, x, mean, rstd, gamma, g_res, g_out, gm_bf16, dgamma, dbeta, gm_colsum, drop, rows,
-                             cols, workspace, workspace_floats, (hipStream_t)stream);
-}
+// ---- backward.  The plain, fp8 and row-scale (drop path) forms share the name their workspace and dropout messages carry.
+static const char* const LN_BWD_WHO = "layernorm_bwd / grad_mask_cast";
 
-extern "C" int vitssl_layernorm_bwd_fp8(const void* dy_bf16, const float* x, const float* mean, const float* rstd,
-                                        const float* gamma, const float* g_res, float* g_out, void* gm_bf16, void* gm_fp8,
-                                        const float* qscale, float* qamax, float* dgamma, float* dbeta, float* gm_colsum,
-                                        vitssl_dropout_t drop, int64_t rows, int cols, float* workspace, int64_t workspace_floats, void* stream) {
-  VS_CHECK_ARG(dy_bf16 && x && mean && rstd && gamma && g_out && dgamma && dbeta && gm_fp8, "layernorm_bwd_fp8: null pointer");   // gm_bf16 may be NULL
-  VS_CHECK_ARG(rows > 0 && cols > 0 && cols % 4 == 0 && cols <= 2048, "layernorm_bwd_fp8: cols=%d must be a multiple of 4 and <= 2048", cols);
-  return launch_ln_bwd<true, true>(dy_bf16, x, mean, rstd, gamma, g_res, g_out, gm_bf16, dgamma, dbeta, gm_colsum, drop, rows,
-                                   cols, workspace, workspace_floats, (hipStream_t)stream, gm_fp8, qscale, qamax);
-}
-
-extern "C" int vitssl_grad_mask_cast_fp8(const float* g, void* gm_bf16, void* gm_fp8, const float* qscale, float* qamax,
-                                         float* gm_colsum, vitssl_dropout_t drop, int64_t rows, int cols, float* workspace, int64_t workspace_floats, void* stream) {
-  VS_CHECK_ARG(g && gm_fp8, "grad_mask_cast_fp8: null pointer");   // gm_bf16 may be NULL
-  VS_CHECK_ARG(rows > 0 && cols > 0 && cols % 4 == 0 && cols <= 2048, "grad_mask_cast_fp8: cols=%d must be a multiple of 4 and <= 2048", cols);
-  return launch_ln_bwd<false, true>(nullptr, nullptr, nullptr, nullptr, nullptr, g, nullptr, gm_bf16, nullptr, nullptr,
-                                    gm_colsum, drop, rows, cols, workspace, workspace_floats, (hipStream_t)stream, gm_fp8, qscale, qamax);
-}
-
-extern "C" int vitssl_grad_mask_cast(const float* g, void* gm_bf16, float* gm_colsum, vitssl_dropout_t drop,
-                                     int64_t rows, int cols, float* workspace, int64_t workspace_floats, void* stream) {
-  VS_CHECK_ARG(g && gm_bf16, "grad_mask_cast: null pointer");
-  VS_CHECK_ARG(rows > 0 && cols > 0 && cols % 4 == 0 && cols <= 2048, "grad_mask_cast: cols=%d must be a multiple of 4 and <= 2048", cols);
-  return launch_ln_bwd<false>(nullptr, nullptr, nullptr, nullptr, nullptr, g, nullptr, gm_bf16, nullptr, nullptr,
-                              gm_colsum, drop, rows, cols, workspace, workspace_floats, (hipStream_t)stream);
-}
-
-// ---- drop path: the same two contracts with the bf16 operand scaled per row (include/vitssl_droppath.h) ----------------------
+// (drop path: the _rows forms take the same contracts with the bf16 operand scaled per row, include/vitssl_droppath.h)
 static int check_rowscale(const char* who, const vitssl_rowscale_t* r, int64_t rows) {
   VS_CHECK_ARG(r && r->scale && r->groups > 0 && r->rows_per_group > 0, "%s: row scales need scale, groups > 0 and rows_per_group > 0", who);
   VS_CHECK_ARG(rows < (1ll << 31), "%s: rows = %lld outside rows < 2^31", who, (long long)rows);
@@ -636,8 +533,38 @@ extern "C" int vitssl_layernorm_bwd_rows(const void* dy_bf16, const float* x, co
   VS_CHECK_ARG(dy_bf16 && x && mean && rstd && gamma && g_out && dgamma && dbeta && gm_bf16, "layernorm_bwd_rows: null pointer");
   VS_CHECK_ARG(rows > 0 && cols > 0 && cols % 4 == 0 && cols <= 2048, "layernorm_bwd_rows: cols=%d must be a multiple of 4 and <= 2048", cols);
   if (int rc = check_rowscale("layernorm_bwd_rows", rowscale, rows)) return rc;
-  return launch_ln_bwd<true>(dy_bf16, x, mean, rstd, gamma, g_res, g_out, gm_bf16, dgamma, dbeta, gm_colsum, drop, rows, cols,
-                             workspace, workspace_floats, (hipStream_t)stream, nullptr, nullptr, nullptr, rowscale);
+  return launch_ln_bwd<true, false, true>({LN_BWD_WHO, dy_bf16, x, mean, rstd, gamma, g_res, g_out, gm_bf16, dgamma, dbeta, gm_colsum, drop,
+                                           rows, cols, workspace, workspace_floats, (hipStream_t)stream, nullptr, nullptr, nullptr, rowscale});
+}
+
+extern "C" int vitssl_layernorm_bwd(const void* dy_bf16, const float* x, const float* mean, const float* rstd,
+                                    const float* gamma, const float* g_res, float* g_out, void* gm_bf16, float* dgamma,
+                                    float* dbeta, float* gm_colsum, vitssl_dropout_t drop, int64_t rows, int cols,
+                                    float* workspace, int64_t workspace_floats, void* stream) {
+  VS_CHECK_ARG(dy_bf16 && x && mean && rstd && gamma && g_out && dgamma && dbeta, "layernorm_bwd: null pointer");
+  VS_CHECK_ARG(rows > 0 && cols > 0 && cols % 4 == 0 && cols <= 2048, "layernorm_bwd: cols=%d must be a multiple of 4 and <= 2048", cols);
+  VS_CHECK_ARG(!gm_colsum || gm_bf16, "layernorm_bwd: gm_colsum without gm_bf16");
+  return launch_ln_bwd<true>({LN_BWD_WHO, dy_bf16, x, mean, rstd, gamma, g_res, g_out, gm_bf16, dgamma, dbeta, gm_colsum, drop, rows, cols,
+                              workspace, workspace_floats, (hipStream_t)stream});
+}
+
+extern "C" int vitssl_layernorm_bwd_fp8(const void* dy_bf16, const float* x, const float* mean, const float* rstd,
+                                        const float* gamma, const float* g_res, float* g_out, void* gm_bf16, void* gm_fp8,
+                                        const float* qscale, float* qamax, float* dgamma, float* dbeta, float* gm_colsum,
+                                        vitssl_dropout_t drop, int64_t rows, int cols, float* workspace, int64_t workspace_floats, void* stream) {
+  VS_CHECK_ARG(dy_bf16 && x && mean && rstd && gamma && g_out && dgamma && dbeta && gm_fp8, "layernorm_bwd_fp8: null pointer");   // gm_bf16 may be NULL
+  VS_CHECK_ARG(rows > 0 && cols > 0 && cols % 4 == 0 && cols <= 2048, "layernorm_bwd_fp8: cols=%d must be a multiple of 4 and <= 2048", cols);
+  return launch_ln_bwd<true, true>({LN_BWD_WHO, dy_bf16, x, mean, rstd, gamma, g_res, g_out, gm_bf16, dgamma, dbeta, gm_colsum, drop, rows,
+                                    cols, workspace, workspace_floats, (hipStream_t)stream, gm_fp8, qscale, qamax});
+}
+
+// ---- the mask + cast + column-sum form of the same launch (no LayerNorm)
+extern "C" int vitssl_grad_mask_cast_fp8(const float* g, void* gm_bf16, void* gm_fp8, const float* qscale, float* qamax,
+                                         float* gm_colsum, vitssl_dropout_t drop, int64_t rows, int cols, float* workspace, int64_t workspace_floats, void* stream) {
+  VS_CHECK_ARG(g && gm_fp8, "grad_mask_cast_fp8: null pointer");   // gm_bf16 may be NULL
+  VS_CHECK_ARG(rows > 0 && cols > 0 && cols % 4 == 0 && cols <= 2048, "grad_mask_cast_fp8: cols=%d must be a multiple of 4 and <= 2048", cols);
+  return launch_ln_bwd<false, true>({LN_BWD_WHO, nullptr, nullptr, nullptr, nullptr, nullptr, g, nullptr, gm_bf16, nullptr, nullptr, gm_colsum,
+                                     drop, rows, cols, workspace, workspace_floats, (hipStream_t)stream, gm_fp8, qscale, qamax});
 }
 
 extern "C" int vitssl_grad_mask_cast_rows(const float* g, void* gm_bf16, float* gm_colsum, vitssl_dropout_t drop,
@@ -646,8 +573,17 @@ extern "C" int vitssl_grad_mask_cast_rows(const float* g, void* gm_bf16, float* 
   VS_CHECK_ARG(g && gm_bf16, "grad_mask_cast_rows: null pointer");
   VS_CHECK_ARG(rows > 0 && cols > 0 && cols % 4 == 0 && cols <= 2048, "grad_mask_cast_rows: cols=%d must be a multiple of 4 and <= 2048", cols);
   if (int rc = check_rowscale("grad_mask_cast_rows", rowscale, rows)) return rc;
-  return launch_ln_bwd<false>(nullptr, nullptr, nullptr, nullptr, nullptr, g, nullptr, gm_bf16, nullptr, nullptr, gm_colsum, drop,
-                              rows, cols, workspace, workspace_floats, (hipStream_t)stream, nullptr, nullptr, nullptr, rowscale);
+  return launch_ln_bwd<false, false, true>({LN_BWD_WHO, nullptr, nullptr, nullptr, nullptr, nullptr, g, nullptr, gm_bf16, nullptr, nullptr,
+                                            gm_colsum, drop, rows, cols, workspace, workspace_floats, (hipStream_t)stream, nullptr, nullptr,
+                                            nullptr, rowscale});
+}
+
+extern "C" int vitssl_grad_mask_cast(const float* g, void* gm_bf16, float* gm_colsum, vitssl_dropout_t drop,
+                                     int64_t rows, int cols, float* workspace, int64_t workspace_floats, void* stream) {
+  VS_CHECK_ARG(g && gm_bf16, "grad_mask_cast: null pointer");
+  VS_CHECK_ARG(rows > 0 && cols > 0 && cols % 4 == 0 && cols <= 2048, "grad_mask_cast: cols=%d must be a multiple of 4 and <= 2048", cols);
+  return launch_ln_bwd<false>({LN_BWD_WHO, nullptr, nullptr, nullptr, nullptr, nullptr, g, nullptr, gm_bf16, nullptr, nullptr, gm_colsum, drop,
+                               rows, cols, workspace, workspace_floats, (hipStream_t)stream});
 }
 
 // ---- LayerScale: the same two contracts with the bf16 operand also scaled per column, and gamma's gradient (include/vitssl_layerscale.h)
@@ -669,8 +605,9 @@ extern "C" int vitssl_layernorm_bwd_ls(const void* dy_bf16, const float* x, cons
                                        int64_t workspace_floats, void* stream) {
   VS_CHECK_ARG(dy_bf16 && x && mean && rstd && gamma && g_out && dgamma && dbeta && gm_bf16, "layernorm_bwd_ls: null pointer");
   if (int rc = check_ls("layernorm_bwd_ls", rowscale, colscale, branch_bf16, dls, rows, cols)) return rc;
-  return launch_ln_bwd_ls<true>("layernorm_bwd_ls", dy_bf16, x, mean, rstd, gamma, g_res, g_out, gm_bf16, dgamma, dbeta, gm_colsum, drop,
-                                rowscale, colscale->gamma, branch_bf16, dls, rows, cols, workspace, workspace_floats, (hipStream_t)stream);
+  return launch_ln_bwd<true, false, true, true>({"layernorm_bwd_ls", dy_bf16, x, mean, rstd, gamma, g_res, g_out, gm_bf16, dgamma, dbeta,
+                                                 gm_colsum, drop, rows, cols, workspace, workspace_floats, (hipStream_t)stream, nullptr, nullptr,
+                                                 nullptr, rowscale, colscale->gamma, branch_bf16, dls});
 }
 
 extern "C" int vitssl_grad_mask_cast_ls(const float* g, void* gm_bf16, float* gm_colsum, vitssl_dropout_t drop,
@@ -678,7 +615,7 @@ extern "C" int vitssl_grad_mask_cast_ls(const float* g, void* gm_bf16, float* gm
                                         float* dls, int64_t rows, int cols, float* workspace, int64_t workspace_floats, void* stream) {
   VS_CHECK_ARG(g && gm_bf16, "grad_mask_cast_ls: null pointer");
   if (int rc = check_ls("grad_mask_cast_ls", rowscale, colscale, branch_bf16, dls, rows, cols)) return rc;
-  return launch_ln_bwd_ls<false>("grad_mask_cast_ls", nullptr, nullptr, nullptr, nullptr, nullptr, g, nullptr, gm_bf16, nullptr, nullptr,
-                                 gm_colsum, drop, rowscale, colscale->gamma, branch_bf16, dls, rows, cols, workspace, workspace_floats,
-                                 (hipStream_t)stream);
+  return launch_ln_bwd<false, false, true, true>({"grad_mask_cast_ls", nullptr, nullptr, nullptr, nullptr, nullptr, g, nullptr, gm_bf16, nullptr,
+                                                  nullptr, gm_colsum, drop, rows, cols, workspace, workspace_floats, (hipStream_t)stream,
+                                                  nullptr, nullptr, nullptr, rowscale, colscale->gamma, branch_bf16, dls});
 }

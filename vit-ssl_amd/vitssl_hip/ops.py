@@ -110,25 +110,6 @@ def quantize_fp8(x, y8, scale=None, amax=None):
          _scalar(amax, "amax"), _stream())
 
 
-def layernorm_bwd_fp8(dy, x, mean, rstd, gamma, g_res, g_out, gm, gm8, scale, amax, dgamma, dbeta, gm_colsum=None, drop=NO_DROP):
-    """layernorm_bwd that also writes gm8 = e4m3(gm * scale) and records max|gm| in amax."""
-    rows, cols = x.shape
-    ev = _prof_begin()
-    call("vitssl_layernorm_bwd_fp8", _chk(dy, BF16, "dy", (rows, cols)), _chk(x, F32, "x"), _chk(mean, F32, "mean", (rows,)),
-         _chk(rstd, F32, "rstd", (rows,)), _chk(gamma, F32, "gamma", (cols,)), _opt(g_res, F32, "g_res", (rows, cols)),
-         _chk(g_out, F32, "g_out", (rows, cols)), _opt(gm, BF16, "gm", (rows, cols)), _chk(gm8, FP8, "gm8", (rows, cols)),
-         _scalar(scale, "scale"), _scalar(amax, "amax"), _chk(dgamma, F32, "dgamma", (cols,)), _chk(dbeta, F32, "dbeta", (cols,)),
-         _opt(gm_colsum, F32, "gm_colsum", (cols,)), drop, rows, cols, *_sum_ws(x.device, rows, cols), _stream())
-    _prof_end(ev, "ln_bwd", 0.0, rows * (cols * (2 + 4 + (4 if g_res is not None else 0) + 4 + (3 if gm is not None else 1)) + 8))
-
-
-def grad_mask_cast_fp8(g, gm, gm8, scale, amax, gm_colsum=None, drop=NO_DROP):
-    rows, cols = g.shape
-    call("vitssl_grad_mask_cast_fp8", _chk(g, F32, "g"), _opt(gm, BF16, "gm", (rows, cols)), _chk(gm8, FP8, "gm8", (rows, cols)),
-         _scalar(scale, "scale"), _scalar(amax, "amax"), _opt(gm_colsum, F32, "gm_colsum", (cols,)), drop, rows, cols,
-         *_sum_ws(g.device, rows, cols), _stream())
-
-
 def droppath_table(pairs, B, seed, out):
     """out f32 [len(pairs), B] = the per-sample branch scales (include/vitssl_droppath.h) of the (rate, site) pairs for `seed`:
     1 / (1 - r_eff) where the dropout stream keeps the sample, 0 where it drops it; a rate of 0 gives a row of ones."""
@@ -162,18 +143,47 @@ def _colscale(cols, N, name):
     return c
 
 
-def _ls_ws(device, rows, cols):
-    """(pointer, floats) of scratch for the LayerScale backward entry points (vitssl_layerscale_workspace_floats)."""
-    ws = _tn_workspace(device, int(L.lib().vitssl_layerscale_workspace_floats(rows, cols)))
-    return C.c_void_p(ws.data_ptr()), ws.numel()
+# LayerNorm backward has one launch path for all its forms (csrc/layernorm.hip); what differs is listed here: the suffix of the
+# entry point and the sizing function its workspace is held to.
+_LnForm = collections.namedtuple("_LnForm", "sfx query")
+_LN_PLAIN = _LnForm("", "vitssl_sum_workspace_floats")
+_LN_FP8 = _LnForm("_fp8", "vitssl_sum_workspace_floats")
+_LN_ROWS = _LnForm("_rows", "vitssl_sum_workspace_floats")
+_LN_LS = _LnForm("_ls", "vitssl_layerscale_workspace_floats")
 
 
-def _ls_args(cols, branch, dls, rows_t, M, N, name):
-    """(rowscale or NULL, colscale, branch, dls) of a LayerScale backward launch; branch and dls come together or not at all."""
-    if (branch is None) != (dls is None):
-        raise L.VitsslError(f"{name}: branch= and dls= are given together (gamma's gradient) or both left out")
-    rs = C.byref(_rowscale(rows_t, M, name)) if rows_t is not None else None
-    return rs, C.byref(_colscale(cols, N, name)), _opt(branch, BF16, name + " branch", (M, N)), _opt(dls, F32, name + " dls", (N,))
+def _ln_bwd(who, ln, g_res, gm, gm_colsum, drop, fp8=None, rows=None, cols=None, branch=None, dls=None):
+    """The launch behind layernorm_bwd / grad_mask_cast and their fp8 forms.  ln = (dy, x, mean, rstd, gamma, g_out, dgamma, dbeta),
+    or None for the mask + cast form, whose input is g_res; fp8 = (gm8, scale, amax)."""
+    M, N = (ln[1] if ln else g_res).shape
+    if cols is not None:
+        if (branch is None) != (dls is None):
+            raise L.VitsslError(f"{who}: branch= and dls= are given together (gamma's gradient) or both left out")
+        form = _LN_LS
+        extra = (C.byref(_rowscale(rows, M, who)) if rows is not None else None, C.byref(_colscale(cols, N, who)),
+                 _opt(branch, BF16, who + " branch", (M, N)), _opt(dls, F32, who + " dls", (N,)))
+    else:
+        if branch is not None or dls is not None:
+            raise L.VitsslError(f"{who}: branch= / dls= belong to cols= (LayerScale)")
+        form = _LN_FP8 if fp8 else (_LN_PLAIN if rows is None else _LN_ROWS)
+        extra = () if rows is None else (C.byref(_rowscale(rows, M, who)),)
+    if ln:
+        dy, x, mean, rstd, gamma, g_out, dgamma, dbeta = ln
+        head = (_chk(dy, BF16, "dy", (M, N)), _chk(x, F32, "x"), _chk(mean, F32, "mean", (M,)), _chk(rstd, F32, "rstd", (M,)),
+                _chk(gamma, F32, "gamma", (N,)), _opt(g_res, F32, "g_res", (M, N)), _chk(g_out, F32, "g_out", (M, N)))
+    else:
+        head = (_chk(g_res, F32, "g"),)
+    # (a missing gm: the library refuses it where the form needs it; the mask + cast and LayerScale forms refuse it here)
+    gm_p = (_opt if fp8 or (ln and form is not _LN_LS) else _chk)(gm, BF16, "gm", (M, N))
+    q8 = (_chk(fp8[0], FP8, "gm8", (M, N)), _scalar(fp8[1], "scale"), _scalar(fp8[2], "amax")) if fp8 else ()
+    sums = (_chk(dgamma, F32, "dgamma", (N,)), _chk(dbeta, F32, "dbeta", (N,))) if ln else ()
+    ws = _tn_workspace((ln[1] if ln else g_res).device, int(getattr(L.lib(), form.query)(M, N)))
+    ev = _prof_begin() if ln else None
+    call("vitssl_" + ("layernorm_bwd" if ln else "grad_mask_cast") + form.sfx, *head, gm_p, *q8, *sums,
+         _opt(gm_colsum, F32, "gm_colsum", (N,)), drop, *extra, M, N, C.c_void_p(ws.data_ptr()), ws.numel(), _stream())
+    # dy bf16 + x fp32 (+ residual gradient fp32) in, gradient fp32 (+ masked bf16 / e4m3 operand) out (+ the bf16 branch image in)
+    _prof_end(ev, "ln_bwd", 0.0, M * (N * (2 + 4 + (4 if g_res is not None else 0) + 4 + (2 if gm is not None else 0) + (1 if fp8 else 0)
+                                           + (2 if branch is not None else 0)) + 8))
 
 
 def layernorm_bwd(dy, x, mean, rstd, gamma, g_res, g_out, gm, dgamma, dbeta, gm_colsum=None, drop=NO_DROP, rows=None, cols=None,
@@ -181,46 +191,23 @@ def layernorm_bwd(dy, x, mean, rstd, gamma, g_res, g_out, gm, dgamma, dbeta, gm_
     """rows=(scale, rows_per_group): vitssl_layernorm_bwd_rows, the bf16 operand `gm` scaled per row (drop path).
     cols=gamma f32 [cols]: vitssl_layernorm_bwd_ls (LayerScale), `gm` also scaled per column; with branch= (the forward's bf16
     image of the branch) and dls= (f32 [cols]) gamma's gradient is accumulated into dls.  Composes with rows=."""
-    if cols is not None:
-        M, N = x.shape
-        ls = _ls_args(cols, branch, dls, rows, M, N, "layernorm_bwd")
-        ev = _prof_begin()
-        call("vitssl_layernorm_bwd_ls", _chk(dy, BF16, "dy", (M, N)), _chk(x, F32, "x"), _chk(mean, F32, "mean", (M,)),
-             _chk(rstd, F32, "rstd", (M,)), _chk(gamma, F32, "gamma", (N,)), _opt(g_res, F32, "g_res", (M, N)),
-             _chk(g_out, F32, "g_out", (M, N)), _chk(gm, BF16, "gm", (M, N)), _chk(dgamma, F32, "dgamma", (N,)),
-             _chk(dbeta, F32, "dbeta", (N,)), _opt(gm_colsum, F32, "gm_colsum", (N,)), drop, *ls, M, N, *_ls_ws(x.device, M, N), _stream())
-        _prof_end(ev, "ln_bwd", 0.0, M * (N * (2 + 4 + (4 if g_res is not None else 0) + 4 + 2 + (2 if branch is not None else 0)) + 8))
-        return
-    if branch is not None or dls is not None:
-        raise L.VitsslError("layernorm_bwd: branch= / dls= belong to cols= (LayerScale)")
-    rs = () if rows is None else (C.byref(_rowscale(rows, x.shape[0], "layernorm_bwd")),)
-    rows, cols = x.shape
-    ev = _prof_begin()
-    call("vitssl_layernorm_bwd_rows" if rs else "vitssl_layernorm_bwd", _chk(dy, BF16, "dy", (rows, cols)), _chk(x, F32, "x"),
-         _chk(mean, F32, "mean", (rows,)), _chk(rstd, F32, "rstd", (rows,)), _chk(gamma, F32, "gamma", (cols,)),
-         _opt(g_res, F32, "g_res", (rows, cols)),
-         _chk(g_out, F32, "g_out", (rows, cols)), _opt(gm, BF16, "gm", (rows, cols)), _chk(dgamma, F32, "dgamma", (cols,)),
-         _chk(dbeta, F32, "dbeta", (cols,)), _opt(gm_colsum, F32, "gm_colsum", (cols,)), drop, *rs, rows, cols,
-         *_sum_ws(x.device, rows, cols), _stream())
-    # dy bf16 + x fp32 (+ residual gradient fp32) in, gradient fp32 (+ masked bf16 operand) out
-    _prof_end(ev, "ln_bwd", 0.0, rows * (cols * (2 + 4 + (4 if g_res is not None else 0) + 4 + (2 if gm is not None else 0)) + 8))
+    _ln_bwd("layernorm_bwd", (dy, x, mean, rstd, gamma, g_out, dgamma, dbeta), g_res, gm, gm_colsum, drop, rows=rows, cols=cols,
+            branch=branch, dls=dls)
+
+
+def layernorm_bwd_fp8(dy, x, mean, rstd, gamma, g_res, g_out, gm, gm8, scale, amax, dgamma, dbeta, gm_colsum=None, drop=NO_DROP):
+    """layernorm_bwd that also writes gm8 = e4m3(gm * scale) and records max|gm| in amax."""
+    _ln_bwd("layernorm_bwd_fp8", (dy, x, mean, rstd, gamma, g_out, dgamma, dbeta), g_res, gm, gm_colsum, drop, fp8=(gm8, scale, amax))
 
 
 def grad_mask_cast(g, gm, gm_colsum=None, drop=NO_DROP, rows=None, cols=None, branch=None, dls=None):
     """rows=(scale, rows_per_group): vitssl_grad_mask_cast_rows, `gm` scaled per row (drop path).
     cols=gamma (with branch= and dls= for gamma's gradient): vitssl_grad_mask_cast_ls (LayerScale); composes with rows=."""
-    if cols is not None:
-        M, N = g.shape
-        ls = _ls_args(cols, branch, dls, rows, M, N, "grad_mask_cast")
-        call("vitssl_grad_mask_cast_ls", _chk(g, F32, "g"), _chk(gm, BF16, "gm", (M, N)), _opt(gm_colsum, F32, "gm_colsum", (N,)), drop,
-             *ls, M, N, *_ls_ws(g.device, M, N), _stream())
-        return
-    if branch is not None or dls is not None:
-        raise L.VitsslError("grad_mask_cast: branch= / dls= belong to cols= (LayerScale)")
-    rs = () if rows is None else (C.byref(_rowscale(rows, g.shape[0], "grad_mask_cast")),)
-    rows, cols = g.shape
-    call("vitssl_grad_mask_cast_rows" if rs else "vitssl_grad_mask_cast", _chk(g, F32, "g"), _chk(gm, BF16, "gm", (rows, cols)),
-         _opt(gm_colsum, F32, "gm_colsum", (cols,)), drop, *rs, rows, cols, *_sum_ws(g.device, rows, cols), _stream())
+    _ln_bwd("grad_mask_cast", None, g, gm, gm_colsum, drop, rows=rows, cols=cols, branch=branch, dls=dls)
+
+
+def grad_mask_cast_fp8(g, gm, gm8, scale, amax, gm_colsum=None, drop=NO_DROP):
+    _ln_bwd("grad_mask_cast_fp8", None, g, gm, gm_colsum, drop, fp8=(gm8, scale, amax))
 
 
 _OUT0_DTYPE = {L.EPI_BF16: BF16, L.EPI_F32: F32, L.EPI_GELU: BF16, L.EPI_RESID: F32, L.EPI_DGELU: BF16, L.EPI_EMBED: F32}
