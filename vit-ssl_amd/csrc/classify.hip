@@ -12,8 +12,12 @@
 // MIX (include/vitssl_mixup.h, vitssl_classify_loss_mix): the same kernels against the two-label target of a mixed image.  A
 // row whose two labels coincide, or whose weight is 0 or 1, runs the one-label statements below unchanged; a genuine
 // two-label row keeps the second label's term apart as well.  The one-label instantiation contains none of it.
+//
+// BCE (include/vitssl_bce.h, vitssl_classify_bce): binary cross-entropy on the same rows, labels and tables -- a kernel of its own
+// (classify_bce_kernel, one pass over the row) that shares row_state, the argmax order, the workspace slots and the finish kernel.
 #include "../../include/vitssl_classify.h"
 #include "../../include/vitssl_mixup.h"
+#include "../../include/vitssl_bce.h"
 #include "common.h"
 #include <math.h>
 
@@ -293,6 +297,115 @@ __global__ __launch_bounds__(CL_THREADS) void classify_finish_kernel(const doubl
   }
 }
 
+// BCE (include/vitssl_bce.h, vitssl_classify_bce): a sigmoid per class against the label-smoothed (MIX: two-label) target,
+// optionally thresholded to {0, 1}.  Neither the loss nor the gradient of an element needs a sum over the row, so a row of any
+// length is ONE pass: a chunk is read once, and its argmax candidates, its loss terms and its gradient leave with it.
+struct BceArgs {
+  ClArgs c;                  // eps: the smoothing
+  double thr;                // < 0: the soft target as it is
+  double div;                // what a row's sum over the classes is divided by: C, or 1 (sum_classes)
+};
+
+__device__ __forceinline__ double bce_target(double t, double thr) { return thr >= 0.0 ? (t > thr ? 1.0 : 0.0) : t; }
+
+// One element: its loss max(z, 0) - z t + log1p(exp(-|z|)) is returned, d = sigmoid(z) - t.  One exponential and one division
+// serve all of it: with ex = exp(-|z|) in [0, 1] and q = 1 / ((1 + ex)(2 + ex)),
+//   sigmoid(|z|) = (2 + ex) q,  sigmoid(-|z|) = ex sigmoid(|z|)                  (no cancellation in either tail)
+//   log1p(ex) = 2 atanh(u),  u = ex / (2 + ex) = ex (1 + ex) q <= 1/3:  2 u (1 + u^2/3 + u^4/5 + ... + u^34/35); the terms
+//   left out sum to less than (1/9)^18 / 37 / (1 - 1/9) = 2e-19 of the bracket, below half an ulp of an fp64 number
+// (the library's log1p spends about 80 fp64 additions an element on a range this argument never has).  Where t == 1 exactly
+// sigmoid(z) - 1 is formed as -sigmoid(-z).  Branch-free, so that the four elements of a piece interleave.
+__device__ __forceinline__ double bce_element(float zf, double t, double& d) {
+  const double z = (double)zf, ex = exp(-fabs(z)), w = 1.0 + ex, v = 2.0 + ex;
+  const double q = 1.0 / (w * v), r = v * q, er = ex * r, u = (ex * w) * q, u2 = u * u;
+  double p = 1.0 / 35.0;
+#pragma unroll
+  for (int k = 33; k >= 1; k -= 2) p = fma(p, u2, 1.0 / (double)k);
+  const bool pos = z >= 0.0;
+  d = t == 1.0 ? -(pos ? er : r) : (pos ? r : er) - t;
+  return (fmax(z, 0.0) - z * t) + 2.0 * u * p;
+}
+
+template <bool MIX>
+__global__ __launch_bounds__(CL_THREADS) void classify_bce_kernel(BceArgs b) {
+  const ClArgs& a = b.c;
+  const int lane = threadIdx.x & 63;
+  // (readfirstlane: the row is wave-uniform and the compiler is told so -- the row's state, labels and targets then live in
+  // scalar registers and `valid` is a scalar branch around the arithmetic, not an execution mask inside it)
+  const int row = __builtin_amdgcn_readfirstlane(blockIdx.x * CL_WAVES + (threadIdx.x >> 6));
+  if (row >= a.B) return;                                        // (no barrier below: waves are independent)
+  const int C = a.C;
+  long long la, lb;
+  float lm;
+  int nv = 0;                                                    // n_valid, counted by every wave as in classify_rows_kernel
+  for (int i = lane; i < a.B; i += 64) nv += row_state<MIX>(a.labels, a.partner, a.lam, i, a.B, C, a.ignore_index, la, lb, lm) == ROW_VALID ? 1 : 0;
+  nv = wave_sum_i(nv);
+  const bool valid = row_state<MIX>(a.labels, a.partner, a.lam, row, a.B, C, a.ignore_index, la, lb, lm) == ROW_VALID;
+  // the targets of the row's (up to) three kinds of column: s(y)[y] = on, s(y)[c != y] = off
+  const double off = a.eps / (double)C, on = (1.0 - a.eps) + off;
+  int y = -1, y2 = -1;                                           // -1 matches no column: nothing is indexed by a bad label
+  double ty = on, ty2 = off;
+  if (valid) {
+    y = (int)la;                                                 // one-label rows: a == b, l == 1 ...
+    if constexpr (MIX) {
+      if (la != lb && lm != 1.f) {
+        if (lm == 0.f) {
+          y = (int)lb;                                           // ... or l == 0
+        } else {
+          const double wa = (double)lm, wb = 1.0 - (double)lm;
+          y2 = (int)lb, ty = wa * on + wb * off, ty2 = wa * off + wb * on;
+        }
+      }
+    }
+  }
+  ty = bce_target(ty, b.thr), ty2 = bce_target(ty2, b.thr);
+  const double to = bce_target(off, b.thr);
+  const float* zr = a.logits + (long long)row * a.ld;
+  const double scale = a.upstream / ((double)nv * b.div);
+  bf16_t* dr = a.dlogits ? a.dlogits + (long long)row * a.ld_out : nullptr;
+  float* pr = a.parts ? a.parts + (long long)row * a.cp : nullptr;
+
+  float bv = -INFINITY;
+  int bi = INT_MAX;
+  double ls = 0.0;
+  for (int col = lane * 4; col < C; col += CL_CHUNK) {
+    const f32x4 v = *(const f32x4*)(zr + col);                   // ld % 4 == 0 and col < C <= ld: the 16 bytes lie in the row
+    f32x4 g = {0.f, 0.f, 0.f, 0.f};
+    const int n = min(C - col, 4);                               // 4 everywhere but in the row's last piece
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (e < n && arg_better(v[e], col + e, bv, bi)) bv = v[e], bi = col + e;
+    if (valid) {
+      double d[4], l[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) l[e] = bce_element(v[e], MIX && col + e == y2 ? ty2 : col + e == y ? ty : to, d[e]);
+#pragma unroll
+      for (int e = 0; e < 4; ++e)                                // (a column >= C holds anything, NaN included: computed, never used)
+        if (e < n) ls += l[e], g[e] = (float)(d[e] * scale);
+    }
+    if (dr) {                                                    // col < C <= ld_out and ld_out % 4 == 0
+      const u32x2 w = {pack_bf2(g[0], g[1]), pack_bf2(g[2], g[3])};
+      *(u32x2*)(dr + col) = w;
+    }
+    if (pr) *(f32x4*)(pr + col) = g;                             // cp = C rounded up to 4
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(bv, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    if (arg_better(ov, oi, bv, bi)) bv = ov, bi = oi;
+  }
+  ls = wave_sum_d(ls);
+  if (lane == 0) {
+    a.row_loss[row] = ls / b.div;
+    a.pred[row] = bi;
+  }
+  if (dr) {                                                      // the zero padding: columns cp .. ld_out-1 (both multiples of 4)
+    const u32x2 z = {0u, 0u};
+    for (int col = a.cp + lane * 4; col < a.ld_out; col += CL_CHUNK) *(u32x2*)(dr + col) = z;
+  }
+}
+
 inline long long cl_cp(int C) { return ((long long)C + 3) / 4 * 4; }
 inline long long cl_loss_floats(int B) { return ((long long)2 * B + 3) / 4 * 4; }   // B doubles, the gradient rows behind them 16-byte aligned
 
@@ -303,11 +416,16 @@ extern "C" int64_t vitssl_classify_loss_workspace_floats(int B, int C) {
   return cl_loss_floats(B) + (long long)B * cl_cp(C);
 }
 
-// both entry points: `who` names the caller in the messages; partner == nullptr is the one-label loss
+// every entry point: `who` names the caller in the messages; partner == nullptr is the one-label loss; bce: the sigmoid loss
+// of include/vitssl_bce.h with its threshold and its sum_classes flag (nullptr: cross-entropy)
+struct BceSpec {
+  double thr;
+  int sum_classes;
+};
 static int classify_launch(const char* who, const char* sizing, const float* logits, const int64_t* labels, const int32_t* partner, const float* lam,
                            int B, int C, int ld, double label_smoothing, int64_t ignore_index, float upstream, float* loss_out,
                            void* dlogits_bf16, int ld_out, float* dbias, int64_t* pred, int64_t* counters, int32_t* bad_labels,
-                           float* workspace, int64_t workspace_floats, void* stream) {
+                           float* workspace, int64_t workspace_floats, void* stream, const BceSpec* bce = nullptr) {
   VS_CHECK_ARG(logits && labels && loss_out && pred && counters && bad_labels, "%s: null pointer", who);
   VS_CHECK_ARG(B >= 1 && B <= CL_MAX_B, "%s: B = %d rows is outside 1 <= B <= 2^22", who, B);
   VS_CHECK_ARG(C >= 2 && C <= CL_MAX_C, "%s: C = %d classes is outside 2 <= C <= 65536", who, C);
@@ -337,7 +455,16 @@ static int classify_launch(const char* who, const char* sizing, const float* log
   a.B = B, a.C = C, a.ld = ld, a.ld_out = ld_out, a.cp = (int)cl_cp(C);
   const dim3 grid((unsigned)((B + CL_WAVES - 1) / CL_WAVES)), block(CL_THREADS);
   const bool reg = C <= CL_NV * CL_CHUNK;
-  if (!partner) {
+  if (bce) {
+    BceArgs b;
+    b.c = a;
+    b.thr = bce->thr;
+    b.div = bce->sum_classes ? 1.0 : (double)C;
+    if (!partner)
+      hipLaunchKernelGGL(classify_bce_kernel<false>, grid, block, 0, s, b);
+    else
+      hipLaunchKernelGGL(classify_bce_kernel<true>, grid, block, 0, s, b);
+  } else if (!partner) {
     if (reg)
       hipLaunchKernelGGL((classify_rows_kernel<true, false>), grid, block, 0, s, a);
     else
@@ -379,4 +506,17 @@ extern "C" int vitssl_classify_loss_mix(const float* logits, const int64_t* labe
   return classify_launch("classify_loss_mix", "vitssl_classify_loss_mix_workspace_floats", logits, labels, partner, lam, B, C, ld,
                          label_smoothing, ignore_index, upstream, loss_out, dlogits_bf16, ld_out, dbias, pred, counters, bad_labels, workspace,
                          workspace_floats, stream);
+}
+
+extern "C" int64_t vitssl_classify_bce_workspace_floats(int B, int C) { return vitssl_classify_loss_workspace_floats(B, C); }
+
+extern "C" int vitssl_classify_bce(const float* logits, const int64_t* labels, const int32_t* partner, const float* lam, int B, int C, int ld,
+                                   double smoothing, double target_threshold, int sum_classes, int64_t ignore_index, float upstream,
+                                   float* loss_out, void* dlogits_bf16, int ld_out, float* dbias, int64_t* pred, int64_t* counters,
+                                   int32_t* bad_labels, float* workspace, int64_t workspace_floats, void* stream) {
+  VS_CHECK_ARG((partner == nullptr) == (lam == nullptr), "classify_bce: partner and lam are either both NULL (one label) or both given");
+  VS_CHECK_ARG(target_threshold == target_threshold, "classify_bce: target_threshold is NaN (a negative value means no threshold)");
+  const BceSpec bce = {target_threshold, sum_classes != 0};
+  return classify_launch("classify_bce", "vitssl_classify_bce_workspace_floats", logits, labels, partner, lam, B, C, ld, smoothing, ignore_index,
+                         upstream, loss_out, dlogits_bf16, ld_out, dbias, pred, counters, bad_labels, workspace, workspace_floats, stream, &bce);
 }

@@ -154,8 +154,11 @@ def setup_device():
 
 
 def make_criterion(config):
+    """`training.criterion: {name, params}`: a criterion of utils.losses (BinaryCrossEntropy), else one of torch.nn."""
+    from . import losses
     name, kwargs = _spec(config, "training", "criterion")
-    return getattr(nn, name)(**kwargs)
+    cls = losses.CRITERIA.get(name)
+    return (getattr(nn, name) if cls is None else cls)(**kwargs)
 
 
 def _group_options(config, store):

@@ -1,8 +1,8 @@
 """Supervised / fine-tune trainer (reference: utils/trainers/supervised_trainer.py:30-48):
 logits = model(x); CrossEntropy; backward; step.  By default it runs the reference-style autograd path
 through the HIP engine; with `training.fused_step: true` (and the fused AdamW, a model with `train_step`, and
-nn.CrossEntropyLoss(weight=None, reduction="mean")) every step is `ViT.train_step` / `ViT.eval_step`: loss, backward,
-all-reduce and AdamW as one engine schedule that does only the work the model's frozen state needs, with one host read
+nn.CrossEntropyLoss(weight=None, reduction="mean") or utils.losses.BinaryCrossEntropy) every step is `ViT.train_step` /
+`ViT.eval_step`: loss, backward, all-reduce and AdamW as one engine schedule that does only the work the model's frozen state needs, with one host read
 per epoch.  Anything else falls back to the autograd path and says so once.
 `training.mixup: {mixup_alpha, cutmix_alpha, prob, switch_prob, mode}` (fused path only, else a ValueError at construction): the
 training batches are mixed on the GPU (data.GPUMixup, timm's Mixup semantics) and the loss is taken against the two-label targets.
@@ -22,6 +22,7 @@ import torch
 from torch import nn
 
 from .._config import cfg_get, to_plain
+from ..losses import BinaryCrossEntropy
 from ..train_utils import make_optimizer
 from .base_trainer import BaseTrainer
 
@@ -59,8 +60,9 @@ class SupervisedTrainer(BaseTrainer):
         if not self._fused_path():
             c = self.criterion
             raise ValueError("training.mixup needs the fused supervised step (training.fused_step: true, with the fused AdamW over a "
-                             "model with train_step and nn.CrossEntropyLoss(weight=None, reduction='mean')): only its loss kernel "
-                             f"takes two-label targets; configured here are training.fused_step = {getattr(self, 'fused_step', False)!r}, "
+                             "model with train_step and nn.CrossEntropyLoss(weight=None, reduction='mean') or "
+                             "utils.losses.BinaryCrossEntropy): only its loss kernels take two-label targets; configured here are "
+                             f"training.fused_step = {getattr(self, 'fused_step', False)!r}, "
                              f"optimizer {type(self.optimizer).__name__}, criterion {type(c).__name__}")
         self.mixup = GPUMixup(spec)
 
@@ -70,12 +72,21 @@ class SupervisedTrainer(BaseTrainer):
         if not getattr(self, "fused_step", False):
             return False
         c = self.criterion
-        ok = self._is_fused() and type(c) is nn.CrossEntropyLoss and c.weight is None and c.reduction == "mean"
+        known = (type(c) is nn.CrossEntropyLoss and c.weight is None and c.reduction == "mean") or type(c) is BinaryCrossEntropy
+        ok = self._is_fused() and known
         if not ok and not self._fallback_logged:
             logger.warning("training.fused_step is set, but the fused step needs the fused AdamW, a model with train_step and "
-                           "nn.CrossEntropyLoss(weight=None, reduction='mean'): using the autograd path")
+                           "nn.CrossEntropyLoss(weight=None, reduction='mean') or utils.losses.BinaryCrossEntropy: using the autograd path")
             self._fallback_logged = True
         return ok
+
+    def _loss_keywords(self):
+        """What train_step / eval_step are told about the criterion (one of the two `_fused_path` accepts)."""
+        c = self.criterion
+        if type(c) is BinaryCrossEntropy:
+            return dict(label_smoothing=c.smoothing, ignore_index=c.ignore_index, loss="bce", target_threshold=c.target_threshold,
+                        sum_classes=c.sum_classes)
+        return dict(label_smoothing=c.label_smoothing, ignore_index=c.ignore_index)
 
     def _rebuild_reducer(self):
         """Data parallel: the reducer expects the gradient ranges of the model's current frozen state."""
@@ -100,15 +111,13 @@ class SupervisedTrainer(BaseTrainer):
             self.metric_handler.update_classification(self.model.last_pred, labels, self.model.num_classes)
 
     def _train_epoch_fused(self, epoch):
-        c = self.criterion
         total, running, counters = 0, None, self._counters()
         for batch in self.train_loader:
             inputs, labels = self._labelled(batch, "train")
-            kw = {}
+            kw = self._loss_keywords()
             if getattr(self, "mixup", None) is not None:
                 kw["mix"] = self.mixup.draw(inputs.shape[0], inputs.shape[2], inputs.shape[3], self.transform_generator, inputs.device)
-            loss = self.model.train_step(inputs, labels, self.optimizer, self.reducer, label_smoothing=c.label_smoothing,
-                                         ignore_index=c.ignore_index, counters=counters, **kw)
+            loss = self.model.train_step(inputs, labels, self.optimizer, self.reducer, counters=counters, **kw)
             self._warmup_step(epoch)
             running = loss if running is None else running + loss
             self._fused_update_metrics(labels)
@@ -116,11 +125,11 @@ class SupervisedTrainer(BaseTrainer):
         return self._log_grad_norm(epoch, self._epoch_values(running, total, counters))
 
     def _validate_fused(self):
-        c = self.criterion
         total, running, counters = 0, None, self._counters()
+        kw = self._loss_keywords()
         for batch in self.val_loader:
             inputs, labels = self._labelled(batch, "val")
-            loss = self.model.eval_step(inputs, labels, label_smoothing=c.label_smoothing, ignore_index=c.ignore_index, counters=counters)
+            loss = self.model.eval_step(inputs, labels, counters=counters, **kw)
             running = loss if running is None else running + loss
             self._fused_update_metrics(labels)
             total += 1

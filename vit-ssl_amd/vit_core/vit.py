@@ -118,16 +118,21 @@ class _ViTRuntime:
             self.rec = dict(feats=feats, h=h, mean=mean, rstd=rstd, wt=wt, Nk=Nk, B=B)
         return logits, probs
 
-    def loss(self, logits, labels, tag, label_smoothing, ignore_index, counters, dlogits=None, dbias=None, mix=None):
+    def loss(self, logits, labels, tag, label_smoothing, ignore_index, counters, dlogits=None, dbias=None, mix=None, bce=None):
         """csrc/classify.hip on the padded logits -> (loss as a device scalar, pred i64 [B]).  `mix` (data.MixParams): against
-        the two-label targets of a mixed batch."""
+        the two-label targets of a mixed batch.  `bce` ((target_threshold, sum_classes), from `loss_spec`): binary cross-entropy
+        (vitssl_classify_bce, one- or two-label) instead of softmax cross-entropy."""
         B, dev = logits.shape[0], logits.device
         if labels.dtype != torch.int64 or not labels.is_contiguous():
             labels = labels.to(torch.int64).contiguous()
         loss_out = self.ws.get(tag + "loss_out", (2,), F32, dev)
         pred = self.ws.get(tag + "pred", (B,), torch.int64, dev)
         counters = self.counters if counters is None else counters
-        if mix is None:
+        if bce is not None:
+            ops.classify_bce(logits, labels, self.ncls, loss_out, pred, counters, self.bad_labels,
+                             partner=None if mix is None else mix.partner, lam=None if mix is None else mix.lam, dlogits=dlogits,
+                             dbias=dbias, smoothing=label_smoothing, target_threshold=bce[0], sum_classes=bce[1], ignore_index=ignore_index)
+        elif mix is None:
             ops.classify_loss(logits, labels, self.ncls, loss_out, pred, counters, self.bad_labels,
                               dlogits=dlogits, dbias=dbias, label_smoothing=label_smoothing, ignore_index=ignore_index)
         else:
@@ -186,6 +191,20 @@ class _ViTFn(Function):
             rt.backward(dlb, "full")
 
         return (None, None, None, None, None, *R.backward_grads("ViT", ctx.gen, rt.save_gen, st, run))
+
+
+def loss_spec(loss, target_threshold, sum_classes):
+    """The `loss`, `target_threshold` and `sum_classes` keywords of train_step / eval_step -> what `_ViTRuntime.loss` takes as
+    `bce`: None for "ce" (nothing new is launched), (target_threshold, sum_classes) for "bce"."""
+    if loss == "ce":
+        if target_threshold is not None or sum_classes:
+            raise ValueError('ViT: target_threshold and sum_classes belong to loss="bce"; loss="ce" takes neither')
+        return None
+    if loss != "bce":
+        raise ValueError(f'ViT: loss = {loss!r} is neither "ce" (softmax cross-entropy) nor "bce" (binary cross-entropy)')
+    if target_threshold is not None and not float(target_threshold) >= 0.0:
+        raise ValueError(f"ViT: target_threshold = {target_threshold!r} must be None or a number >= 0")
+    return (None if target_threshold is None else float(target_threshold), bool(sum_classes))
 
 
 class ViT(nn.Module):
@@ -250,7 +269,8 @@ class ViT(nn.Module):
             raise L.VitsslError(f"ViT: {n} label(s) outside [0, {self.num_classes}) reached train_step / eval_step; their rows were ignored")
 
     def train_step(self, x: torch.Tensor, labels: torch.Tensor, optimizer, reducer=None, label_smoothing: float = 0.0,
-                   ignore_index: int = -100, counters=None, mix=None) -> torch.Tensor:
+                   ignore_index: int = -100, counters=None, mix=None, loss: str = "ce", target_threshold=None,
+                   sum_classes: bool = False) -> torch.Tensor:
         """One full optimisation step (zero_grad -> forward -> CrossEntropyLoss(mean, label_smoothing, ignore_index) ->
         backward -> gradient all-reduce -> AdamW) with no autograd graph; returns the loss as a device scalar (no host sync).
         Equivalent to utils/trainers/supervised_trainer.py:33-40 of the reference.  Leaves `last_logits` ([B, C] view of the
@@ -259,8 +279,14 @@ class ViT(nn.Module):
         `mix` (data.MixParams, from data.GPUMixup.draw): Mixup / CutMix.  The batch is mixed into a workspace buffer
         (vitssl_mix_batch) and the loss is taken against the two-label targets lam s(y[i]) + (1 - lam) s(y[partner])
         (vitssl_classify_loss_mix); a row of an invalid table counts as a bad label (`check_labels`).  The counters then
-        compare the prediction with the row's own label.  Without `mix` nothing of this is launched."""
+        compare the prediction with the row's own label.  Without `mix` nothing of this is launched.
+        `loss="bce"`: binary cross-entropy (timm's BinaryCrossEntropy, the DeiT III loss; utils.losses.BinaryCrossEntropy is
+        its torch module) instead of softmax cross-entropy, in one launch of vitssl_classify_bce: a sigmoid per class against
+        the targets smoothed by `label_smoothing` (with `mix`: the two-label targets), set to (t > target_threshold) when a
+        threshold is given; a row's loss is the mean over its classes, their sum with `sum_classes`.  With "ce" (the default)
+        nothing of this is launched; any other value is a ValueError."""
         R.require_gpu(x, "ViT.train_step")
+        bce = loss_spec(loss, target_threshold, sum_classes)
         rt = self.runtime(x.device)
         st = rt.store
         with R.fused_step(self, st, optimizer, reducer) as apply:
@@ -273,21 +299,23 @@ class ViT(nn.Module):
                 x = mixed
             logits, _ = rt.forward(x, True, save=True, save_backbone=sched != "head")
             dlb = rt.ws.get("head.dlogits", tuple(logits.shape), BF16, x.device)
-            loss, pred = rt.loss(logits, labels, "head.", label_smoothing, ignore_index, counters, dlogits=dlb,
-                                 dbias=st.gview("classification_head.linear.bias"), mix=mix)
+            value, pred = rt.loss(logits, labels, "head.", label_smoothing, ignore_index, counters, dlogits=dlb,
+                                  dbias=st.gview("classification_head.linear.bias"), mix=mix, bce=bce)
             rt.backward(dlb, sched, reducer)
             apply()
             self.last_logits, self.last_pred = logits[:, :self.num_classes], pred
-            return loss
+            return value
 
     @torch.no_grad()
     def eval_step(self, x: torch.Tensor, labels: torch.Tensor, label_smoothing: float = 0.0, ignore_index: int = -100,
-                  counters=None) -> torch.Tensor:
+                  counters=None, loss: str = "ce", target_threshold=None, sum_classes: bool = False) -> torch.Tensor:
         """The no-grad half of train_step: forward in eval mode (no dropout) and the loss kernel without a gradient.  Saves
-        nothing and leaves the buffers of a pending backward alone; same `last_logits`, `last_pred` and counters."""
+        nothing and leaves the buffers of a pending backward alone; same `last_logits`, `last_pred` and counters; `loss`,
+        `target_threshold` and `sum_classes` as there."""
         R.require_gpu(x, "ViT.eval_step")
+        bce = loss_spec(loss, target_threshold, sum_classes)
         rt = self.runtime(x.device)
         logits, _ = rt.forward(x, False, save=False)
-        loss, pred = rt.loss(logits, labels, "head.tmp.", label_smoothing, ignore_index, counters)
+        value, pred = rt.loss(logits, labels, "head.tmp.", label_smoothing, ignore_index, counters, bce=bce)
         self.last_logits, self.last_pred = logits[:, :self.num_classes], pred
-        return loss
+        return value

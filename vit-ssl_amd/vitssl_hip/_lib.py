@@ -15,6 +15,7 @@ ATTENTION_HD_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "inc
 PATCH_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "vitssl_patch.h"))
 OPTIM_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "vitssl_optim.h"))
 MIXUP_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "vitssl_mixup.h"))
+BCE_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "vitssl_bce.h"))
 DROPPATH_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "vitssl_droppath.h"))
 LAYERSCALE_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "vitssl_layerscale.h"))
 LAMB_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "vitssl_lamb.h"))
@@ -213,6 +214,14 @@ PROTOTYPES_LAMB = {
     "vitssl_lamb_segments": [_vp, _vp, _vp, _vp, _vp, _i, _f, _f, _f, _f, _i, _f, _vp, _f, _i, _vp, _vp, _i64, _vp],
 }
 
+# include/vitssl_bce.h (binary cross-entropy of the supervised / fine-tune step, one- and two-label targets): the launching
+# entry point; the sizing function vitssl_classify_bce_workspace_floats (returns a count) is bound in lib() beside the other
+# sizing functions.
+PROTOTYPES_BCE = {
+    "vitssl_classify_bce": [_vp, _vp, _vp, _vp, _i, _i, _i, C.c_double, C.c_double, _i, _i64, _f, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp,
+                            _i64, _vp],
+}
+
 _lib = None
 
 
@@ -296,6 +305,13 @@ def lamb_header_symbols():
     return sorted(set(re.findall(r"\b(vitssl_[a-z0-9_]+)\s*\(", txt)))
 
 
+def bce_header_symbols():
+    """Entry points and sizing functions declared in include/vitssl_bce.h."""
+    with open(BCE_HEADER_PATH) as f:
+        txt = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)        # the comments name functions of the other headers
+    return sorted(set(re.findall(r"\b(vitssl_[a-z0-9_]+)\s*\(", txt)))
+
+
 def lib():
     global _lib
     if _lib is not None:
@@ -345,13 +361,15 @@ def lib():
     l.vitssl_classify_loss_workspace_floats.argtypes = [C.c_int, C.c_int]
     l.vitssl_classify_loss_mix_workspace_floats.restype = C.c_int64
     l.vitssl_classify_loss_mix_workspace_floats.argtypes = [C.c_int, C.c_int]
+    l.vitssl_classify_bce_workspace_floats.restype = C.c_int64
+    l.vitssl_classify_bce_workspace_floats.argtypes = [C.c_int, C.c_int]
     for sizing in ("vitssl_optim_table_bytes", "vitssl_grad_sumsq_workspace_bytes"):
         getattr(l, sizing).restype = C.c_int64
         getattr(l, sizing).argtypes = [C.c_int]
     for name, args in (list(PROTOTYPES.items()) + list(PROTOTYPES_TRANSFORMS.items()) + list(PROTOTYPES_METRICS.items())
                        + list(PROTOTYPES_CLASSIFY.items()) + list(PROTOTYPES_ATTENTION_HD.items()) + list(PROTOTYPES_PATCH.items())
                        + list(PROTOTYPES_OPTIM.items()) + list(PROTOTYPES_MIXUP.items()) + list(PROTOTYPES_DROPPATH.items())
-                       + list(PROTOTYPES_LAYERSCALE.items()) + list(PROTOTYPES_LAMB.items())):
+                       + list(PROTOTYPES_LAYERSCALE.items()) + list(PROTOTYPES_LAMB.items()) + list(PROTOTYPES_BCE.items())):
         fn = getattr(l, name)  # AttributeError if the symbol is missing
         fn.restype = C.c_int
         fn.argtypes = args

@@ -965,9 +965,10 @@ I64, I32 = torch.int64, torch.int32
 
 
 def _classify(who, entry, sizing, between, logits, labels, C, loss_out, pred, counters, bad_labels, dlogits, dbias, label_smoothing,
-              ignore_index, upstream, workspace):
-    """the checks and the call shared by classify_loss and classify_loss_mix; `between`: the (tensor, dtype, name) arguments the
-    entry point takes between `labels` and `B`"""
+              ignore_index, upstream, workspace, scalars=(), nullable=False):
+    """the checks and the call shared by classify_loss, classify_loss_mix and classify_bce; `between`: the (tensor, dtype, name)
+    arguments the entry point takes between `labels` and `B` (`nullable`: one that is None is passed on as NULL); `scalars`: those it
+    takes between the smoothing and `ignore_index`"""
     if logits is None or logits.dim() != 2 or not 2 <= int(C) <= logits.shape[1]:
         raise L.VitsslError(f"{who}: expected logits [B, ld] with 2 <= C = {C} <= ld, got {None if logits is None else tuple(logits.shape)}")
     B, ld = logits.shape
@@ -977,7 +978,7 @@ def _classify(who, entry, sizing, between, logits, labels, C, loss_out, pred, co
             raise L.VitsslError(f"{who}: dlogits must be [{B}, ld_out] with ld_out % 64 == 0 and ld_out >= {C}, got {tuple(dlogits.shape)}")
         ld_out = dlogits.shape[1]
     z, y = _chk(logits, F32, "logits"), _chk(labels, I64, "labels", (B,))
-    extra = [_chk(t, dtype, name, (B,)) for t, dtype, name in between]
+    extra = [(_opt if nullable else _chk)(t, dtype, name, (B,)) for t, dtype, name in between]
     lo, pr = _chk(loss_out, F32, "loss_out", (2,)), _chk(pred, I64, "pred", (B,))
     ct, bl = _chk(counters, I64, "counters", (2,)), _chk(bad_labels, I32, "bad_labels", (1,))
     dl, db = _opt(dlogits, BF16, "dlogits"), _opt(dbias, F32, "dbias", (C,))
@@ -985,7 +986,7 @@ def _classify(who, entry, sizing, between, logits, labels, C, loss_out, pred, co
     ws = _tn_workspace(logits.device, need) if workspace is None else workspace      # shared scratch: launches on one stream are ordered
     if workspace is not None:
         _chk(ws, F32, "workspace")
-    call(entry, z, y, *extra, B, int(C), ld, float(label_smoothing), int(ignore_index), float(upstream), lo, dl, ld_out, db,
+    call(entry, z, y, *extra, B, int(C), ld, float(label_smoothing), *scalars, int(ignore_index), float(upstream), lo, dl, ld_out, db,
          pr, ct, bl, _vp(ws), ws.numel(), _stream())
 
 
@@ -1025,3 +1026,21 @@ def classify_loss_mix(logits, labels, partner, lam, C, loss_out, pred, counters,
     _classify("classify_loss_mix", "vitssl_classify_loss_mix", "vitssl_classify_loss_mix_workspace_floats",
               ((partner, I32, "partner"), (lam, F32, "lam")), logits, labels, C, loss_out, pred, counters, bad_labels, dlogits, dbias,
               label_smoothing, ignore_index, upstream, workspace)
+
+
+# ---- binary cross-entropy (include/vitssl_bce.h) ----
+def classify_bce(logits, labels, C, loss_out, pred, counters, bad_labels, partner=None, lam=None, dlogits=None, dbias=None,
+                 smoothing=0.0, target_threshold=None, sum_classes=False, ignore_index=-100, upstream=1.0, workspace=None):
+    """timm's BinaryCrossEntropy (the DeiT III loss) with the arguments and the outputs of `classify_loss`: a sigmoid per class
+    against t = lam[i] s(labels[i]) + (1 - lam[i]) s(labels[partner[i]]) (s: the label-smoothed one-hot row; partner int32 [B]
+    and lam f32 [B] both None: one label per row), t = (t > target_threshold) with a threshold (None: the soft target); a
+    row's loss is the mean over its C classes, their sum with `sum_classes`.  Rows, counters and bad_labels as
+    `classify_loss` / `classify_loss_mix`."""
+    if (partner is None) != (lam is None):
+        raise L.VitsslError("classify_bce: partner and lam are either both None (one label per row) or both given")
+    thr = -1.0 if target_threshold is None else float(target_threshold)
+    if not thr >= 0.0 and target_threshold is not None:
+        raise L.VitsslError(f"classify_bce: target_threshold = {target_threshold!r} must be None or a number >= 0")
+    _classify("classify_bce", "vitssl_classify_bce", "vitssl_classify_bce_workspace_floats",
+              ((partner, I32, "partner"), (lam, F32, "lam")), logits, labels, C, loss_out, pred, counters, bad_labels, dlogits, dbias,
+              smoothing, ignore_index, upstream, workspace, scalars=(thr, int(bool(sum_classes))), nullable=True)
