@@ -4,7 +4,7 @@
  * Same library, same conventions as vitssl_hip.h (0 on success, <0 on error with vitssl_last_error() naming the offending
  * argument; no allocation; device pointers and workspaces owned by the caller; enqueued on `stream`, never synchronised).
  * Kept in a header of its own so that the symbol list of vitssl_hip.h and vitssl_version() stay what they are; the Python
- * mirror binds these through vitssl_hip._lib.PROTOTYPES_ATTENTION_HD.
+ * mirror binds these through vitssl_hip._lib.REGISTRY["attention_hd"].
  *
  * The attention entry points of vitssl_hip.h serve dh = 64 and refuse every other head dim; these two serve
  *   8 <= dh <= 128, dh % 8 == 0   (a head's slice of a row is a whole number of 16-byte chunks; dh = 64 included)

@@ -7,7 +7,7 @@
  * device pointers and workspaces owned by the caller; enqueued on `stream`, never synchronised; every check is made before
  * anything is launched).  Kept in a header of its own so that the symbol lists of vitssl_hip.h, vitssl_classify.h and
  * vitssl_mixup.h, vitssl_version(), vitssl_classify_loss and vitssl_classify_loss_mix stay what they are; the Python mirror
- * binds it through vitssl_hip._lib.PROTOTYPES_BCE.
+ * binds it through vitssl_hip._lib.REGISTRY["bce"].
  */
 #ifndef VITSSL_BCE_H
 #define VITSSL_BCE_H

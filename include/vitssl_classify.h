@@ -5,7 +5,7 @@
  * Same library, same conventions as vitssl_hip.h (0 on success, <0 on error with vitssl_last_error(); no allocation;
  * device pointers and workspaces owned by the caller; enqueued on `stream`, never synchronised).  Kept in a header of its
  * own so that the symbol list of vitssl_hip.h, vitssl_version() and vitssl_cross_entropy stay what they are; the Python
- * mirror binds it through vitssl_hip._lib.PROTOTYPES_CLASSIFY.
+ * mirror binds it through vitssl_hip._lib.REGISTRY["classify"].
  */
 #ifndef VITSSL_CLASSIFY_H
 #define VITSSL_CLASSIFY_H

@@ -6,7 +6,7 @@
  * Same library, same conventions as vitssl_hip.h (0 on success, <0 on error with vitssl_last_error(); no allocation;
  * device pointers and workspaces owned by the caller; enqueued on `stream`, never synchronised; every check is made before
  * anything is launched).  Kept in a header of its own so that vitssl_hip.h, vitssl_gemm_t and vitssl_version() stay what they
- * are; the Python mirror binds it through vitssl_hip._lib.PROTOTYPES_DROPPATH.
+ * are; the Python mirror binds it through vitssl_hip._lib.REGISTRY["droppath"].
  *
  * Semantics (timm's DropPath, per sample, scale_by_keep): in training mode a residual branch of block i is multiplied, for
  * every sample b of the batch, by s[b] = keep[b] ? 1 / (1 - r_eff) : 0, with r_eff = round(r * 65536) / 65536 (the dropout

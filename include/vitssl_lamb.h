@@ -5,7 +5,7 @@
  * Same library, same conventions as vitssl_hip.h (0 on success, <0 on error with vitssl_last_error() naming the offending
  * argument; no allocation; device pointers and workspaces owned by the caller; enqueued on `stream`, never synchronised).
  * Kept in a header of its own so that the symbol lists of the other headers stay what they are; the Python mirror binds these
- * through vitssl_hip._lib.PROTOTYPES_LAMB.  Nothing of vitssl_optim.h changes: the table is the image vitssl_optim_table_build
+ * through vitssl_hip._lib.REGISTRY["lamb"].  Nothing of vitssl_optim.h changes: the table is the image vitssl_optim_table_build
  * writes (same vitssl_optim_segment_t, same units of 1024 floats that never straddle a segment), and THE CALLER'S CONTRACT of
  * that header holds here too: `table` is the device copy of an image the builder accepted, `nseg` the nseg it was built with.
  *

@@ -7,7 +7,7 @@
  * Same library, same conventions as vitssl_hip.h (0 on success, <0 on error with vitssl_last_error(); no allocation;
  * device pointers and workspaces owned by the caller; enqueued on `stream`, never synchronised; every check is made before
  * anything is launched).  Kept in a header of its own so that vitssl_hip.h, vitssl_gemm_t, vitssl_droppath.h and
- * vitssl_version() stay what they are; the Python mirror binds it through vitssl_hip._lib.PROTOTYPES_LAYERSCALE.
+ * vitssl_version() stay what they are; the Python mirror binds it through vitssl_hip._lib.REGISTRY["layerscale"].
  *
  * Semantics (timm's order, x + drop_path(ls(branch))), in every mode:
  *   x_out = aux + s[row] * gamma[col] * u,      u = drop(acc + bias)       (element dropout: keep ? (acc + bias) / (1 - p) : 0)

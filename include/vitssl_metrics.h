@@ -4,7 +4,7 @@
  * Same library, same conventions as vitssl_hip.h (0 on success, <0 on error with vitssl_last_error(); no allocation;
  * device pointers and workspaces owned by the caller; enqueued on `stream`, never synchronised).  Kept in a header of its
  * own so that the symbol list of vitssl_hip.h and vitssl_version() stay what they are; the Python mirror binds these
- * through vitssl_hip._lib.PROTOTYPES_METRICS.
+ * through vitssl_hip._lib.REGISTRY["metrics"].
  *
  * Both entry points are single-pass reductions without float atomics: every workgroup stores its fp64 partials in a slot
  * of the caller's workspace and ONE reduce launch adds the slots in a fixed order, so the same inputs give the same bits

@@ -6,7 +6,7 @@
  * device pointers and workspaces owned by the caller; enqueued on `stream`, never synchronised; every check is made before
  * anything is launched).  Kept in a header of its own so that the symbol lists of vitssl_hip.h and vitssl_classify.h,
  * vitssl_version() and vitssl_classify_loss stay what they are; the Python mirror binds it through
- * vitssl_hip._lib.PROTOTYPES_MIXUP.
+ * vitssl_hip._lib.REGISTRY["mixup"].
  */
 #ifndef VITSSL_MIXUP_H
 #define VITSSL_MIXUP_H

@@ -5,7 +5,7 @@
  * Same library, same conventions as vitssl_hip.h (0 on success, <0 on error with vitssl_last_error() naming the offending
  * argument; no allocation; device pointers and workspaces owned by the caller; enqueued on `stream`, never synchronised).
  * Kept in a header of its own so that the symbol list of vitssl_hip.h and vitssl_version() stay what they are; the Python
- * mirror binds these through vitssl_hip._lib.PROTOTYPES_OPTIM.  vitssl_adamw of vitssl_hip.h is untouched.
+ * mirror binds these through vitssl_hip._lib.REGISTRY["optim"].  vitssl_adamw of vitssl_hip.h is untouched.
  *
  * The segment table.  A flat fp32 store (parameters p, gradient g, moments m and v, each `numel` floats) is described by
  * `nseg` segments in ascending order, one per parameter that takes part in the step:

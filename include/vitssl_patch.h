@@ -4,7 +4,7 @@
  * Same library, same conventions as vitssl_hip.h (0 on success, <0 on error with vitssl_last_error() naming the offending
  * argument; no allocation; device pointers and workspaces owned by the caller; enqueued on `stream`, never synchronised;
  * every limit is checked before anything is launched).  Kept in a header of its own so that the symbol list of vitssl_hip.h
- * and vitssl_version() stay what they are; the Python mirror binds these through vitssl_hip._lib.PROTOTYPES_PATCH.
+ * and vitssl_version() stay what they are; the Python mirror binds these through vitssl_hip._lib.REGISTRY["patch"].
  *
  * vitssl_patchify_bf16 / vitssl_gather_patches_f32 of vitssl_hip.h serve patch sides that are multiples of 4, and the bf16
  * GEMMs take a contraction length that is a multiple of 64 and an output width that is a multiple of 4.  A patch width

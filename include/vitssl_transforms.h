@@ -4,7 +4,7 @@
  * Same library, same conventions as vitssl_hip.h (0 on success, <0 on error with vitssl_last_error(); no allocation;
  * device pointers owned by the caller; enqueued on `stream`, never synchronised).  Kept in a header of its own so that
  * the symbol list of vitssl_hip.h and vitssl_version() stay what they are; the Python mirror binds these through
- * vitssl_hip._lib.PROTOTYPES_TRANSFORMS.
+ * vitssl_hip._lib.REGISTRY["transforms"].
  */
 #ifndef VITSSL_TRANSFORMS_H
 #define VITSSL_TRANSFORMS_H

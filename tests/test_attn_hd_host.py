@@ -35,19 +35,20 @@ def test_header_is_bound_and_exported(built):
     from vitssl_hip import _lib, ops
     protos = _prototypes()
     assert set(protos) == {"vitssl_attn_hd_fwd", "vitssl_attn_hd_bwd"}
-    assert set(_lib.attention_hd_header_symbols()) == set(protos) == set(_lib.PROTOTYPES_ATTENTION_HD)
+    table = {n: a for n, (r, a) in _lib.REGISTRY["attention_hd"].items()}
+    assert set(_lib.header_symbols("attention_hd")) == set(protos) == set(table)
     raw = ctypes.CDLL(built.LIB_PATH)
     lib = built.lib()
-    for n, args in _lib.PROTOTYPES_ATTENTION_HD.items():
+    for n, args in table.items():
         assert hasattr(raw, n), f"{n} declared in include/vitssl_attention_hd.h but not exported"
         assert re.search(r"void\s*\*\s*stream", protos[n]), n
         assert len(args) == len([a for a in protos[n].split(",") if a.strip()]), n
         assert getattr(lib, n).argtypes == args and getattr(lib, n).restype is ctypes.c_int
     # same argument lists as the dh = 64 entry points
-    assert _lib.PROTOTYPES_ATTENTION_HD["vitssl_attn_hd_fwd"] == _lib.PROTOTYPES["vitssl_attn_fwd"]
-    assert _lib.PROTOTYPES_ATTENTION_HD["vitssl_attn_hd_bwd"] == _lib.PROTOTYPES["vitssl_attn_bwd"]
+    assert _lib.REGISTRY["attention_hd"]["vitssl_attn_hd_fwd"] == _lib.REGISTRY["hip"]["vitssl_attn_fwd"]
+    assert _lib.REGISTRY["attention_hd"]["vitssl_attn_hd_bwd"] == _lib.REGISTRY["hip"]["vitssl_attn_bwd"]
     # the ABI of include/vitssl_hip.h is what it was
-    assert not set(protos) & set(_lib.header_symbols()) and not set(protos) & set(_lib.PROTOTYPES)
+    assert not set(protos) & set(_lib.header_symbols()) and not set(protos) & set(_lib.REGISTRY["hip"])
     assert set(_lib.header_symbols()) >= {"vitssl_attn_fwd", "vitssl_attn_bwd"} and lib.vitssl_version() == _lib.ABI_VERSION == 3
     assert callable(ops.attn_hd_fwd) and callable(ops.attn_hd_bwd)
     import __graft_entry__ as ge

@@ -39,19 +39,19 @@ def test_bce_header_is_bound_and_exported(built):
     from vitssl_hip import _lib
     protos = _prototypes()
     sizing = {"vitssl_classify_bce_workspace_floats"}
-    assert set(_lib.bce_header_symbols()) == set(protos) == set(_lib.PROTOTYPES_BCE) | sizing
+    launching = {n: a for n, (r, a) in _lib.REGISTRY["bce"].items() if r is ctypes.c_int}
+    assert set(_lib.header_symbols("bce")) == set(protos) == set(_lib.REGISTRY["bce"]) == set(launching) | sizing
     raw, lib = ctypes.CDLL(built.LIB_PATH), built.lib()
     for n in protos:
         assert hasattr(raw, n), f"{n} declared in include/vitssl_bce.h but not exported"
-    for n, args in _lib.PROTOTYPES_BCE.items():
+    for n, args in launching.items():
         assert len(args) == len([a for a in protos[n].split(",") if a.strip()]), n
         assert getattr(lib, n).argtypes == args and getattr(lib, n).restype is ctypes.c_int
     assert lib.vitssl_classify_bce_workspace_floats.restype is ctypes.c_int64
-    others = (set(_lib.header_symbols()) | set(_lib.classify_header_symbols()) | set(_lib.mixup_header_symbols())
-              | set(_lib.metrics_header_symbols()) | set(_lib.optim_header_symbols()) | set(_lib.lamb_header_symbols()))
+    others = {n for key in _lib.HEADERS if key != "bce" for n in _lib.header_symbols(key)}
     assert not set(protos) & others                                          # disjoint from every other header ...
-    assert set(_lib.classify_header_symbols()) == {"vitssl_classify_loss", "vitssl_classify_loss_workspace_floats"}      # ... which are what they were
-    assert set(_lib.mixup_header_symbols()) == {"vitssl_mix_batch", "vitssl_classify_loss_mix", "vitssl_classify_loss_mix_workspace_floats"}
+    assert set(_lib.header_symbols("classify")) == {"vitssl_classify_loss", "vitssl_classify_loss_workspace_floats"}      # ... which are what they were
+    assert set(_lib.header_symbols("mixup")) == {"vitssl_mix_batch", "vitssl_classify_loss_mix", "vitssl_classify_loss_mix_workspace_floats"}
     assert lib.vitssl_version() == _lib.ABI_VERSION == 3
 
 

@@ -39,19 +39,20 @@ def test_classify_header_is_bound_and_exported(built):
     from vitssl_hip import _lib
     protos = _prototypes()
     sizing = {"vitssl_classify_loss_workspace_floats"}
-    assert set(_lib.classify_header_symbols()) == set(protos) == set(_lib.PROTOTYPES_CLASSIFY) | sizing
-    assert {n for n, a in protos.items() if re.search(r"void\s*\*\s*stream", a)} == set(_lib.PROTOTYPES_CLASSIFY)
+    launching = {n: a for n, (r, a) in _lib.REGISTRY["classify"].items() if r is ctypes.c_int}
+    assert set(_lib.header_symbols("classify")) == set(protos) == set(_lib.REGISTRY["classify"]) == set(launching) | sizing
+    assert {n for n, a in protos.items() if re.search(r"void\s*\*\s*stream", a)} == set(launching)
     raw = ctypes.CDLL(built.LIB_PATH)
     lib = built.lib()
     for n in protos:
         assert hasattr(raw, n), f"{n} declared in include/vitssl_classify.h but not exported"
-    for n, args in _lib.PROTOTYPES_CLASSIFY.items():
+    for n, args in launching.items():
         assert len(args) == len([a for a in protos[n].split(",") if a.strip()]), n
         assert getattr(lib, n).argtypes == args and getattr(lib, n).restype is ctypes.c_int
     assert lib.vitssl_classify_loss_workspace_floats.restype is ctypes.c_int64
     # the ABI of include/vitssl_hip.h is what it was, vitssl_cross_entropy included
-    assert not set(protos) & set(_lib.header_symbols()) and not set(protos) & set(_lib.PROTOTYPES)
-    assert "vitssl_cross_entropy" in _lib.PROTOTYPES and lib.vitssl_version() == _lib.ABI_VERSION == 3
+    assert not set(protos) & set(_lib.header_symbols()) and not set(protos) & set(_lib.REGISTRY["hip"])
+    assert "vitssl_cross_entropy" in _lib.REGISTRY["hip"] and lib.vitssl_version() == _lib.ABI_VERSION == 3
     import __graft_entry__ as ge
     assert "classify.hip" in ge.SOURCES
 

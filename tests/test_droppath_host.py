@@ -139,7 +139,7 @@ def test_sites_are_disjoint_from_every_dropout_site(built):
         drop = {base + 3 * i + w for i in range(64) for w in range(3)}
         path = {DP.site(i, br, base) for i in range(64) for br in (0, 1)}
         assert len(path) == 128 and not (drop & path) and all(s >> 31 == 1 for s in path) and all(s >> 31 == 0 for s in drop)
-    txt = open(L.DROPPATH_HEADER_PATH).read()
+    txt = open(L.HEADERS["droppath"]).read()
     assert "VITSSL_DROPPATH_SITE_BIT 0x80000000u" in txt and "site_base + 3 * block + which" in txt      # the rule is documented
 
 
@@ -147,14 +147,14 @@ def test_sites_are_disjoint_from_every_dropout_site(built):
 def test_header_declares_the_four_entry_points_and_the_library_exports_them(built):
     from vitssl_hip import _lib as L
     want = {"vitssl_droppath_table", "vitssl_gemm_bf16_nt_rows", "vitssl_layernorm_bwd_rows", "vitssl_grad_mask_cast_rows"}
-    assert set(L.droppath_header_symbols()) == want == set(L.PROTOTYPES_DROPPATH)
+    assert set(L.header_symbols("droppath")) == want == set(L.REGISTRY["droppath"])
     raw = ctypes.CDLL(built.LIB_PATH)
     for s in want:
         assert hasattr(raw, s), f"{s} declared in include/vitssl_droppath.h but not exported"
     # vitssl_hip.h keeps its symbol list, its structs and its version
-    assert not want & set(L.header_symbols()) and not want & set(L.PROTOTYPES)
+    assert not want & set(L.header_symbols()) and not want & set(L.REGISTRY["hip"])
     assert built.lib().vitssl_version() == L.ABI_VERSION == 3
-    txt = re.sub(r"/\*.*?\*/", "", open(L.DROPPATH_HEADER_PATH).read(), flags=re.S)
+    txt = re.sub(r"/\*.*?\*/", "", open(L.HEADERS["droppath"]).read(), flags=re.S)
     assert re.search(r"const float\* scale;\s*int64_t groups;\s*int rows_per_group;", txt)
     assert ctypes.sizeof(L.RowScale) == 24
 

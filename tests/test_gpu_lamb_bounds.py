@@ -41,16 +41,14 @@ def test_every_launching_function_has_a_case():
 
 def test_prototypes_match_the_header():
     from vitssl_hip import _lib as L
-    assert set(L.lamb_header_symbols()) == set(L.PROTOTYPES_LAMB)
-    txt = re.sub(r"/\*.*?\*/", "", open(L.LAMB_HEADER_PATH).read(), flags=re.S)
-    ctype = {"float*": C.c_void_p, "const float*": C.c_void_p, "void*": C.c_void_p, "const void*": C.c_void_p, "int": C.c_int,
-             "float": C.c_float, "int64_t": C.c_int64, "const vitssl_optim_segment_t*": C.POINTER(L.OptimSegment)}
-    for name, argtypes in L.PROTOTYPES_LAMB.items():
-        args = re.search(r"\b" + name + r"\s*\(([^)]*)\)\s*;", txt).group(1)
-        declared = [ctype[re.sub(r"\s*\b\w+$", "", a.strip()).replace(" *", "*")] for a in args.split(",")]
-        assert declared == argtypes, name
+    from _abi_mirror import mismatches
+    declared = L.declarations("lamb")
+    assert set(declared) == set(L.REGISTRY["lamb"]) == {"vitssl_lamb_workspace_bytes", "vitssl_lamb_segments"}
+    for name, bound in L.REGISTRY["lamb"].items():
+        assert not mismatches(name, declared[name], bound, L.STRUCTS), mismatches(name, declared[name], bound, L.STRUCTS)
+    assert L.REGISTRY["lamb"]["vitssl_lamb_workspace_bytes"] == (C.c_int64, [C.POINTER(L.OptimSegment), C.c_int])      # the table is typed
     raw = C.CDLL(L.LIB_PATH)
-    for name in L.PROTOTYPES_LAMB:
+    for name in L.REGISTRY["lamb"]:
         assert hasattr(raw, name), f"{name} declared in include/vitssl_lamb.h but not exported"
 
 

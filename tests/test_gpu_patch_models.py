@@ -277,7 +277,7 @@ def test_native_geometry_launches_nothing_of_the_patch_header(monkeypatch):
     opt = FusedAdamW(model.flat_store(), lr=1e-3, weight_decay=0.0)
     assert torch.isfinite(model.train_step(torch.rand(3, 3, 32, 32).to(DEV), opt))
     assert "vitssl_patchify_bf16" in launched and "vitssl_cast_transpose_batch" in launched and "vitssl_l1_loss" in launched
-    assert not set(launched) & set(_lib.PROTOTYPES_PATCH), set(launched) & set(_lib.PROTOTYPES_PATCH)
+    assert not set(launched) & set(_lib.REGISTRY["patch"]), set(launched) & set(_lib.REGISTRY["patch"])
     pred = model.last_pred
     assert pred.is_contiguous() and model.last_targets.is_contiguous()
 

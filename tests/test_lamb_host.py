@@ -225,5 +225,5 @@ def test_state_dict_round_trip_and_adamw_state_loads():
 
 def test_header_symbols_are_the_bound_prototypes():
     from vitssl_hip import _lib
-    assert set(_lib.lamb_header_symbols()) == set(_lib.PROTOTYPES_LAMB) == {"vitssl_lamb_workspace_bytes", "vitssl_lamb_segments"}
+    assert set(_lib.header_symbols("lamb")) == set(_lib.REGISTRY["lamb"]) == {"vitssl_lamb_workspace_bytes", "vitssl_lamb_segments"}
     assert _lib.LAMB_ALWAYS_ADAPT == 1 and _lib.LAMB_TRUST_CLIP == 2

@@ -202,14 +202,14 @@ def test_freeze_backbone_freezes_the_gammas(built):
 def test_header_symbols_equal_the_prototypes_and_the_library_exports_them(built):
     from vitssl_hip import _lib as L
     want = {"vitssl_gemm_bf16_nt_ls", "vitssl_layernorm_bwd_ls", "vitssl_grad_mask_cast_ls", "vitssl_layerscale_workspace_floats"}
-    assert set(L.layerscale_header_symbols()) == want == set(L.PROTOTYPES_LAYERSCALE)
+    assert set(L.header_symbols("layerscale")) == want == set(L.REGISTRY["layerscale"])
     raw = ctypes.CDLL(built.LIB_PATH)
     for s in want:
         assert hasattr(raw, s), f"{s} declared in include/vitssl_layerscale.h but not exported"
     # the other headers keep their symbol lists, vitssl_hip.h its version
-    assert not want & set(L.header_symbols()) and not want & set(L.PROTOTYPES) and not want & set(L.droppath_header_symbols())
+    assert not want & set(L.header_symbols()) and not want & set(L.REGISTRY["hip"]) and not want & set(L.header_symbols("droppath"))
     assert built.lib().vitssl_version() == L.ABI_VERSION == 3
-    txt = re.sub(r"/\*.*?\*/", "", open(L.LAYERSCALE_HEADER_PATH).read(), flags=re.S)
+    txt = re.sub(r"/\*.*?\*/", "", open(L.HEADERS["layerscale"]).read(), flags=re.S)
     assert re.search(r"typedef struct \{\s*const float\* gamma;\s*int cols;\s*\} vitssl_colscale_t;", txt)
     assert ctypes.sizeof(L.ColScale) == 16
 

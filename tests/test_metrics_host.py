@@ -130,19 +130,20 @@ def test_metrics_header_is_bound_and_exported(built):
     from vitssl_hip import _lib
     protos = _prototypes()
     sizing = {"vitssl_recon_metrics_workspace_floats", "vitssl_dino_stats_workspace_floats"}
-    assert set(_lib.metrics_header_symbols()) == set(protos) == set(_lib.PROTOTYPES_METRICS) | sizing
-    assert {n for n, a in protos.items() if re.search(r"void\s*\*\s*stream", a)} == set(_lib.PROTOTYPES_METRICS)
+    launching = {n: a for n, (r, a) in _lib.REGISTRY["metrics"].items() if r is ctypes.c_int}
+    assert set(_lib.header_symbols("metrics")) == set(protos) == set(_lib.REGISTRY["metrics"]) == set(launching) | sizing
+    assert {n for n, a in protos.items() if re.search(r"void\s*\*\s*stream", a)} == set(launching)
     raw = ctypes.CDLL(built.LIB_PATH)
     lib = built.lib()
     for n in protos:
         assert hasattr(raw, n), f"{n} declared in include/vitssl_metrics.h but not exported"
-    for n, args in _lib.PROTOTYPES_METRICS.items():
+    for n, args in launching.items():
         assert len(args) == len([a for a in protos[n].split(",") if a.strip()]), n
         assert getattr(lib, n).argtypes == args and getattr(lib, n).restype is ctypes.c_int
     for n in sizing:
         assert getattr(lib, n).restype is ctypes.c_int64
     # the ABI of include/vitssl_hip.h is what it was
-    assert not set(protos) & set(_lib.header_symbols()) and not set(protos) & set(_lib.PROTOTYPES)
+    assert not set(protos) & set(_lib.header_symbols()) and not set(protos) & set(_lib.REGISTRY["hip"])
     assert lib.vitssl_version() == _lib.ABI_VERSION == 3
     # the header cites what it replaces
     txt = open(HEADER).read()

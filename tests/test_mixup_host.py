@@ -38,21 +38,20 @@ def test_mixup_header_is_bound_and_exported(built):
     from vitssl_hip import _lib
     protos = _prototypes()
     sizing = {"vitssl_classify_loss_mix_workspace_floats"}
-    assert set(_lib.mixup_header_symbols()) == set(protos) == set(_lib.PROTOTYPES_MIXUP) | sizing
-    assert {n for n, a in protos.items() if re.search(r"void\s*\*\s*stream", a)} == set(_lib.PROTOTYPES_MIXUP)
+    launching = {n: a for n, (r, a) in _lib.REGISTRY["mixup"].items() if r is ctypes.c_int}
+    assert set(_lib.header_symbols("mixup")) == set(protos) == set(_lib.REGISTRY["mixup"]) == set(launching) | sizing
+    assert {n for n, a in protos.items() if re.search(r"void\s*\*\s*stream", a)} == set(launching)
     raw = ctypes.CDLL(built.LIB_PATH)
     lib = built.lib()
     for n in protos:
         assert hasattr(raw, n), f"{n} declared in include/vitssl_mixup.h but not exported"
-    for n, args in _lib.PROTOTYPES_MIXUP.items():
+    for n, args in launching.items():
         assert len(args) == len([a for a in protos[n].split(",") if a.strip()]), n
         assert getattr(lib, n).argtypes == args and getattr(lib, n).restype is ctypes.c_int
     assert lib.vitssl_classify_loss_mix_workspace_floats.restype is ctypes.c_int64
-    others = (set(_lib.header_symbols()) | set(_lib.transforms_header_symbols()) | set(_lib.metrics_header_symbols())
-              | set(_lib.classify_header_symbols()) | set(_lib.attention_hd_header_symbols()) | set(_lib.patch_header_symbols())
-              | set(_lib.optim_header_symbols()))
+    others = {n for key in _lib.HEADERS if key != "mixup" for n in _lib.header_symbols(key)}
     assert not set(protos) & others                                          # disjoint from every other header ...
-    assert set(_lib.classify_header_symbols()) == {"vitssl_classify_loss", "vitssl_classify_loss_workspace_floats"}      # ... which are what they were
+    assert set(_lib.header_symbols("classify")) == {"vitssl_classify_loss", "vitssl_classify_loss_workspace_floats"}      # ... which are what they were
     assert lib.vitssl_version() == _lib.ABI_VERSION == 3
     import __graft_entry__ as ge
     assert "mixup.hip" in ge.SOURCES

@@ -1,6 +1,8 @@
 """Host side of the per-parameter optimizer settings: the layer-id and no-weight-decay rules over the real parameter names of
 the three models, the three config keys of make_optimizer, and FusedAdamW's state_dict with them set.  No kernel runs: the
 stores are built on the CPU."""
+import ctypes
+
 import pytest
 import torch
 
@@ -145,7 +147,8 @@ def test_state_dict_round_trip_with_the_keys_set():
 def test_header_symbols_are_the_bound_prototypes():
     from vitssl_hip import _lib
     sizing = {"vitssl_optim_table_bytes", "vitssl_grad_sumsq_workspace_bytes"}
-    assert set(_lib.optim_header_symbols()) == set(_lib.PROTOTYPES_OPTIM) | sizing
+    status = {n for n, (r, a) in _lib.REGISTRY["optim"].items() if r is ctypes.c_int}
+    assert set(_lib.header_symbols("optim")) == set(_lib.REGISTRY["optim"]) == status | sizing and not status & sizing
     l = _lib.lib()
     for name in sizing:
         assert getattr(l, name).restype is not None and getattr(l, name)(0) == 0 and getattr(l, name)(3) > 0

@@ -20,12 +20,12 @@ def lib():
 
 def test_exports_every_symbol_of_the_patch_header(lib):
     from vitssl_hip import _lib
-    syms = _lib.patch_header_symbols()
+    syms = _lib.header_symbols("patch")
     assert len(syms) == 5
     raw = ctypes.CDLL(_lib.LIB_PATH)
     for s in syms:
         assert hasattr(raw, s), f"{s} declared in include/vitssl_patch.h but not exported"
-    assert set(syms) == set(_lib.PROTOTYPES_PATCH), "Python prototypes out of sync with the header"
+    assert set(syms) == set(_lib.REGISTRY["patch"]), "Python prototypes out of sync with the header"
     assert not set(syms) & set(_lib.header_symbols()), "vitssl_hip.h keeps its symbol list"
     assert lib.vitssl_version() == _lib.ABI_VERSION == 3
 

@@ -209,25 +209,26 @@ def test_transforms_header_is_bound_exported_and_covered(built):
     import test_gpu_transforms_bounds as T
     from vitssl_hip import _lib
     protos = _prototypes()
-    assert "vitssl_tf_resized_crop_to_tensor" in protos and set(protos) == set(_lib.transforms_header_symbols())
+    assert "vitssl_tf_resized_crop_to_tensor" in protos and set(protos) == set(_lib.header_symbols("transforms")) == set(_lib.REGISTRY["transforms"])
     launching = {n for n, args in protos.items() if re.search(r"void\s*\*\s*stream", args)}
     assert launching == {"vitssl_tf_resized_crop_to_tensor"}
-    assert launching == set(_lib.PROTOTYPES_TRANSFORMS)
+    table = {n: _lib.REGISTRY["transforms"][n][1] for n in launching}
+    assert launching | {"vitssl_debug_tf_tile_rows"} == set(_lib.REGISTRY["transforms"])      # the getter returns a count
     for n in launching:                                                      # one ctypes argument per C parameter
-        assert len(_lib.PROTOTYPES_TRANSFORMS[n]) == len([a for a in protos[n].split(",") if a.strip()]), n
+        assert len(table[n]) == len([a for a in protos[n].split(",") if a.strip()]), n
     raw = ctypes.CDLL(built.LIB_PATH)
     for n in protos:
         assert hasattr(raw, n), f"{n} declared in include/vitssl_transforms.h but not exported"
     lib = built.lib()
     for n in launching:
-        assert getattr(lib, n).argtypes == _lib.PROTOTYPES_TRANSFORMS[n] and getattr(lib, n).restype is ctypes.c_int
+        assert getattr(lib, n).argtypes == table[n] and getattr(lib, n).restype is ctypes.c_int
     covered = {c.entry for c in T.CASES}
     assert not (launching - covered), f"entry points without a case in tests/test_gpu_transforms_bounds.py: {sorted(launching - covered)}"
     assert not (covered - launching), f"cases of unknown entry points: {sorted(covered - launching)}"
     assert all(c.bar for c in T.CASES) and len({c.id for c in T.CASES}) == len(T.CASES) >= 4
     # the ABI of include/vitssl_hip.h is what it was: no symbol of the new header in it, its table or its version
-    assert not set(protos) & set(_lib.header_symbols()) and not set(protos) & set(_lib.PROTOTYPES)
-    assert lib.vitssl_version() == _lib.ABI_VERSION and set(_lib.PROTOTYPES) <= set(_lib.header_symbols())
+    assert not set(protos) & set(_lib.header_symbols()) and not set(protos) & set(_lib.REGISTRY["hip"])
+    assert lib.vitssl_version() == _lib.ABI_VERSION and set(_lib.REGISTRY["hip"]) == set(_lib.header_symbols())
 
 
 def test_tile_plan_and_argument_errors(built):

@@ -59,7 +59,7 @@ def parent_adamw_segments(path):
     """ops.adamw_segments through another build of the library (same ABI, same table image)"""
     lib = C.CDLL(path)
     fn = lib.vitssl_adamw_segments
-    fn.restype, fn.argtypes = C.c_int, L.PROTOTYPES_OPTIM["vitssl_adamw_segments"]
+    fn.restype, fn.argtypes = L.REGISTRY["optim"]["vitssl_adamw_segments"]
     P = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)      # noqa: E731
 
     def call(p, g, m, v, plan, lr, b1, b2, eps, step, gscale=1.0, sumsq=None, max_norm=0.0):

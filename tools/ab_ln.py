@@ -19,7 +19,7 @@ def load(name):
     lib = C.CDLL(path)
     lib.vitssl_last_error.restype = C.c_char_p
     for fn in ("vitssl_layernorm_fwd", "vitssl_layernorm_bwd"):
-        getattr(lib, fn).argtypes = L.PROTOTYPES[fn]
+        getattr(lib, fn).argtypes = L.REGISTRY["hip"][fn][1]
         getattr(lib, fn).restype = C.c_int
     return lib
 

@@ -35,8 +35,8 @@ def main():
     from vitssl_hip import _lib as L
     lib = C.CDLL(LIB)
     lib.vitssl_last_error.restype = C.c_char_p
-    lib.vitssl_attn_fwd.argtypes = L.PROTOTYPES["vitssl_attn_fwd"]
-    lib.vitssl_attn_bwd.argtypes = L.PROTOTYPES["vitssl_attn_bwd"]
+    lib.vitssl_attn_fwd.argtypes = L.REGISTRY["hip"]["vitssl_attn_fwd"][1]
+    lib.vitssl_attn_bwd.argtypes = L.REGISTRY["hip"]["vitssl_attn_bwd"][1]
     lib.vitssl_debug_attn_stamps.argtypes = [C.c_void_p]
     dev = torch.device("cuda:0")
     Bn, N, H, dh = int(os.environ.get("B", 256)), int(os.environ.get("N", 196)), 12, 64

@@ -35,7 +35,7 @@ def main():
     from vitssl_hip import _lib as L
     lib = C.CDLL(LIB)
     lib.vitssl_last_error.restype = C.c_char_p
-    lib.vitssl_gemm_bf16_tn.argtypes = L.PROTOTYPES["vitssl_gemm_bf16_tn"]
+    lib.vitssl_gemm_bf16_tn.argtypes = L.REGISTRY["hip"]["vitssl_gemm_bf16_tn"][1]
     lib.vitssl_gemm_bf16_tn.restype = C.c_int
     lib.vitssl_gemm_tn_workspace_floats.restype = C.c_int64
     lib.vitssl_gemm_tn_workspace_floats.argtypes = [C.c_int64, C.c_int, C.c_int]

@@ -553,9 +553,11 @@ def cast_transpose_bf16(src, dst, dst_t):
          R, Cn, _stream())
 
 
-class CastPlan:
-    """Device-resident job table for `cast_transpose_batch`: built once per set of
-    (source, destination) pointers, re-uploaded only when a pointer or shape changes."""
+class _JobTablePlan:
+    """Device-resident job table of a batched (source -> image, transposed image) launch: built once per set of
+    (source, destination) pointers, re-uploaded only when a pointer or shape changes.  A plan names its record struct (`Job`,
+    the mirror of the C struct: the host records take their layout from it), its entry point and the dtype of its destinations."""
+    Job = entry = dst_dtype = None
 
     def __init__(self):
         self.key = None
@@ -565,17 +567,30 @@ class CastPlan:
         self.total = 0
         self.keep = None
 
+    def _record(self, s, d, t):
+        """one job as the fields of `Job`, in order; the tuple of all records is the key of the uploaded table"""
+        return (s.data_ptr(), 0 if d is None else d.data_ptr(), 0 if t is None else t.data_ptr(), s.shape[0], s.shape[1])
+
+    def _check(self, s, d, t):
+        R, Cn = s.shape
+        _chk(s, F32, "src"); _opt(d, self.dst_dtype, "dst", (R, Cn)); _opt(t, self.dst_dtype, "dst_t", (Cn, R))
+
+    def _rebuilt(self, dev):
+        """per-table device state behind the job table (none here)"""
+
+    def _extra(self):
+        """launch arguments between total_tiles and the stream (none here)"""
+        return ()
+
     def run(self, jobs):
-        """jobs: list of (src f32 [R,C], dst bf16 [R,C] | None, dst_t bf16 [C,R] | None)."""
+        """jobs: list of (src f32 [R,C], dst [R,C] | None, dst_t [C,R] | None)."""
         import numpy as np
-        key = tuple((s.data_ptr(), 0 if d is None else d.data_ptr(), 0 if t is None else t.data_ptr(), s.shape[0], s.shape[1])
-                    for s, d, t in jobs)
+        key = tuple(self._record(s, d, t) for s, d, t in jobs)
         if key != self.key:
             for s, d, t in jobs:
-                R, Cn = s.shape
-                _chk(s, F32, "src"); _opt(d, BF16, "dst", (R, Cn)); _opt(t, BF16, "dst_t", (Cn, R))
+                self._check(s, d, t)
             dev = jobs[0][0].device
-            rec = np.zeros(len(jobs), dtype=np.dtype([("src", "<u8"), ("dst", "<u8"), ("dst_t", "<u8"), ("R", "<i4"), ("C", "<i4")]))
+            rec = np.zeros(len(jobs), dtype=np.dtype(self.Job))
             starts = np.zeros(len(jobs) + 1, dtype=np.int32)
             for i, k in enumerate(key):
                 rec[i] = k
@@ -583,9 +598,15 @@ class CastPlan:
             self.jobs_dev = torch.from_numpy(rec.view(np.uint8).copy()).to(dev)
             self.starts_dev = torch.from_numpy(starts).to(dev)
             self.njobs, self.total, self.key = len(jobs), int(starts[-1]), key
+            self._rebuilt(dev)
         self.keep = jobs        # the sources must outlive the launch
-        call("vitssl_cast_transpose_batch", C.c_void_p(self.jobs_dev.data_ptr()), C.c_void_p(self.starts_dev.data_ptr()),
-             self.njobs, self.total, _stream())
+        call(self.entry, C.c_void_p(self.jobs_dev.data_ptr()), C.c_void_p(self.starts_dev.data_ptr()), self.njobs, self.total,
+             *self._extra(), _stream())
+
+
+class CastPlan(_JobTablePlan):
+    """Job table of `vitssl_cast_transpose_batch`: dst bf16 [R,C], dst_t bf16 [C,R]."""
+    Job, entry, dst_dtype = L.CastJob, "vitssl_cast_transpose_batch", BF16
 
 
 # ---- the patch path for any patch side and channel count (include/vitssl_patch.h) ----
@@ -652,67 +673,35 @@ class CastPlanLd(CastPlan):
     """CastPlan whose destinations may be wider / taller than the source (`vitssl_cast_transpose_batch_ld`): dst bf16
     [>= R, ld >= C], dst_t bf16 [>= C, ld >= R].  Only the image of the source is written; the destinations are allocated
     zeroed, so their pad stays zero through every refresh."""
+    Job, entry = L.CastLdJob, "vitssl_cast_transpose_batch_ld"
 
-    def run(self, jobs):
-        import numpy as np
-        key = tuple((s.data_ptr(), 0 if d is None else d.data_ptr(), 0 if t is None else t.data_ptr(), s.shape[0], s.shape[1],
-                     0 if d is None else d.shape[1], 0 if t is None else t.shape[1]) for s, d, t in jobs)
-        if key != self.key:
-            for s, d, t in jobs:
-                R, Cn = s.shape
-                _chk(s, F32, "src"); _opt(d, BF16, "dst"); _opt(t, BF16, "dst_t")
-                if d is not None and (d.dim() != 2 or d.shape[0] < R or d.shape[1] < Cn):
-                    raise L.VitsslError(f"cast plan: dst {tuple(d.shape)} does not hold the [{R}, {Cn}] source")
-                if t is not None and (t.dim() != 2 or t.shape[0] < Cn or t.shape[1] < R):
-                    raise L.VitsslError(f"cast plan: dst_t {tuple(t.shape)} does not hold the transposed [{R}, {Cn}] source")
-            dev = jobs[0][0].device
-            rec = np.zeros(len(jobs), dtype=np.dtype([("src", "<u8"), ("dst", "<u8"), ("dst_t", "<u8"), ("R", "<i4"), ("C", "<i4"),
-                                                      ("ld_dst", "<i4"), ("ld_dst_t", "<i4")]))
-            starts = np.zeros(len(jobs) + 1, dtype=np.int32)
-            for i, k in enumerate(key):
-                rec[i] = k
-                starts[i + 1] = starts[i] + ((k[3] + 63) // 64) * ((k[4] + 63) // 64)
-            self.jobs_dev = torch.from_numpy(rec.view(np.uint8).copy()).to(dev)
-            self.starts_dev = torch.from_numpy(starts).to(dev)
-            self.njobs, self.total, self.key = len(jobs), int(starts[-1]), key
-        self.keep = jobs        # the sources must outlive the launch
-        call("vitssl_cast_transpose_batch_ld", C.c_void_p(self.jobs_dev.data_ptr()), C.c_void_p(self.starts_dev.data_ptr()),
-             self.njobs, self.total, _stream())
+    def _record(self, s, d, t):
+        return super()._record(s, d, t) + (0 if d is None else d.shape[1], 0 if t is None else t.shape[1])
+
+    def _check(self, s, d, t):
+        R, Cn = s.shape
+        _chk(s, F32, "src"); _opt(d, BF16, "dst"); _opt(t, BF16, "dst_t")
+        if d is not None and (d.dim() != 2 or d.shape[0] < R or d.shape[1] < Cn):
+            raise L.VitsslError(f"cast plan: dst {tuple(d.shape)} does not hold the [{R}, {Cn}] source")
+        if t is not None and (t.dim() != 2 or t.shape[0] < Cn or t.shape[1] < R):
+            raise L.VitsslError(f"cast plan: dst_t {tuple(t.shape)} does not hold the transposed [{R}, {Cn}] source")
 
 
-class Fp8WeightPlan:
-    """Device-resident job table for `vitssl_fp8_quantize_weights` (per-tensor power-of-two scales computed on the
-    device, no host synchronisation): `alpha` holds one dequantisation factor per job."""
+class Fp8WeightPlan(_JobTablePlan):
+    """Job table of `vitssl_fp8_quantize_weights` (per-tensor power-of-two scales computed on the device, no host
+    synchronisation): dst e4m3 [R,C], dst_t e4m3 [C,R]; `alpha` holds one dequantisation factor per job."""
+    Job, entry, dst_dtype = L.Fp8WeightJob, "vitssl_fp8_quantize_weights", FP8
 
     def __init__(self):
-        self.key = None
-        self.jobs_dev = self.starts_dev = self.amax = self.alpha = None
-        self.njobs = self.total = 0
-        self.keep = None
+        super().__init__()
+        self.amax = self.alpha = None
 
-    def run(self, jobs):
-        """jobs: list of (src f32 [R,C], dst e4m3 [R,C] | None, dst_t e4m3 [C,R] | None)."""
-        import numpy as np
-        key = tuple((s.data_ptr(), 0 if d is None else d.data_ptr(), 0 if t is None else t.data_ptr(), s.shape[0], s.shape[1])
-                    for s, d, t in jobs)
-        if key != self.key:
-            for s, d, t in jobs:
-                R, Cn = s.shape
-                _chk(s, F32, "src"); _opt(d, FP8, "dst", (R, Cn)); _opt(t, FP8, "dst_t", (Cn, R))
-            dev = jobs[0][0].device
-            rec = np.zeros(len(jobs), dtype=np.dtype([("src", "<u8"), ("dst", "<u8"), ("dst_t", "<u8"), ("R", "<i4"), ("C", "<i4")]))
-            starts = np.zeros(len(jobs) + 1, dtype=np.int32)
-            for i, k in enumerate(key):
-                rec[i] = k
-                starts[i + 1] = starts[i] + ((k[3] + 63) // 64) * ((k[4] + 63) // 64)
-            self.jobs_dev = torch.from_numpy(rec.view(np.uint8).copy()).to(dev)
-            self.starts_dev = torch.from_numpy(starts).to(dev)
-            self.amax = torch.zeros(len(jobs), dtype=F32, device=dev)
-            self.alpha = torch.ones(len(jobs), dtype=F32, device=dev)
-            self.njobs, self.total, self.key = len(jobs), int(starts[-1]), key
-        self.keep = jobs
-        call("vitssl_fp8_quantize_weights", C.c_void_p(self.jobs_dev.data_ptr()), C.c_void_p(self.starts_dev.data_ptr()),
-             self.njobs, self.total, C.c_void_p(self.amax.data_ptr()), C.c_void_p(self.alpha.data_ptr()), _stream())
+    def _rebuilt(self, dev):
+        self.amax = torch.zeros(self.njobs, dtype=F32, device=dev)
+        self.alpha = torch.ones(self.njobs, dtype=F32, device=dev)
+
+    def _extra(self):
+        return C.c_void_p(self.amax.data_ptr()), C.c_void_p(self.alpha.data_ptr())
 
 
 def adamw(p, g, m, v, lr, beta1, beta2, eps, wd, step, gscale=1.0):
