@@ -16,7 +16,7 @@ Design (MI355X-first, not a translation of the reference's eager module graph):
 from __future__ import annotations
 
 import re
-from typing import Callable, Dict, List, Optional, Tuple
+from typing import Callable, Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 from torch import nn
@@ -512,6 +512,17 @@ def drop_path_rates(rate: float, layers: int) -> List[float]:
     return [rate * i / (layers - 1) for i in range(layers)]
 
 
+class _GradOperand(NamedTuple):
+    """A gradient tensor that GEMMs read.  bf16 operands: the bf16 image x.  fp8 operands: the e4m3 image x8 = e4m3(value * scale)
+    with 1-element views of the slot's delayed-scaling state (amax receives max |value|, inv = 1 / scale); x exists only in the
+    self-calibrating first backward of a slot."""
+    x: Optional[torch.Tensor]
+    x8: Optional[torch.Tensor] = None
+    scale: Optional[torch.Tensor] = None
+    amax: Optional[torch.Tensor] = None
+    inv: Optional[torch.Tensor] = None
+
+
 class EncoderStack:
     """L pre-LN transformer blocks (vit_core/encoder_block.py:40-53) on a flat store.
 
@@ -530,6 +541,7 @@ class EncoderStack:
             raise AssertionError(f"d_model({D}) must be cleanly divisible by num_heads({H})!")
         self.store = store
         self.bp = list(block_prefixes)     # e.g. ["encoder_blocks.0.", ...] or [""] for a lone block
+        self._spans = [store.prefix_span(b) for b in self.bp]      # what the backward hands to the reducer, block by block
         self.L, self.D, self.H, self.F = len(self.bp), D, H, F
         self.dh = D // H
         self.p = float(p_drop)
@@ -589,7 +601,7 @@ class EncoderStack:
         return self.bp[i] + leaf
 
     def block_span(self, i) -> Tuple[int, int]:
-        return self.store.prefix_span(self.bp[i])
+        return self._spans[i]
 
     def _drop(self, i, which, seed, training):
         if not training or self.p <= 0.0:
@@ -627,11 +639,90 @@ class EncoderStack:
         if T > MAX_TOKENS:
             raise L.VitsslError(f"sequence length {T} > {MAX_TOKENS} unsupported by the attention kernels")
 
+    # what differs between the operand kinds ------------------------------------------
+    # bf16: every GEMM reads bf16 images.  fp8: every GEMM reads e4m3 images, which the producer of a tensor writes next to (forward:
+    # instead of) the bf16 one; the gradient images carry a per-tensor scale (_GradOperand).  The schedules below are written once
+    # and go through these launches; drop path and LayerScale exist with bf16 operands only, so _scaled() is empty with fp8.
+    def _scaled(self, dp, T, i, k, branch=None, dls=False):
+        """Keyword arguments of the launch that emits branch k (1: attention, 2: MLP) of block i, forward or backward: rows= of the
+        drop-path table `dp` (a block whose rate is 0 -- the first one of every schedule -- keeps the plain launches: its rows of
+        the table are ones); cols= of LayerScale's gamma with branch= (its bf16 image: written by a saving forward, read by the
+        backward) and, if `dls`, dls= (the slot of gamma's gradient)."""
+        kw = {}
+        if dp is not None and self.drop_path[i] > 0.0:
+            kw["rows"] = (dp[2 * i + k - 1], T)
+        if self.layer_scale:
+            name = self._n(i, f"layer_scale{k}.gamma")
+            kw["cols"] = self.store.view(name)
+            if branch is not None:
+                kw["branch"] = branch
+            if dls:
+                kw["dls"] = self.store.gview(name)
+        return kw
+
+    def _ln_fwd(self, x, i, leaf, y, mean, rstd):
+        """y = the operand image of LayerNorm `leaf` of block i over x (fp8: no bf16 image, nothing reads it)"""
+        gamma, beta = self.store.view(self._n(i, leaf + ".weight")), self.store.view(self._n(i, leaf + ".bias"))
+        if self.fp8:
+            ops.layernorm_fwd_fp8(x, gamma, beta, None, y, mean, rstd)
+        else:
+            ops.layernorm_fwd(x, gamma, beta, y, mean, rstd)
+
+    def _gemm(self, A, i, leaf, out, epilogue, dgrad=False, image=None, **kw):
+        """out = A @ W^T (dgrad: A @ W) of weight `leaf` of block i with the fused epilogue; `image`: the operand image of the
+        epilogue's second result (EPI_GELU: out1 in bf16, or its e4m3 image; EPI_DGELU with fp8 operands: the e4m3 image of out)."""
+        name = self._n(i, leaf)
+        if self.fp8:
+            w, alpha = (self.store.w8t if dgrad else self.store.w8)(name)
+            ops.gemm_fp8_nt(A, w, out, epilogue, alpha=alpha, out_fp8=image, **kw)
+        else:
+            ops.gemm_nt(A, self.store.w(name + ".T" if dgrad else name), out, epilogue, out1=image, **kw)
+
+    def _attn_fwd(self, qkv, att, att_op, lse, B, T, probs):
+        if self.fp8:
+            ops.attn_fwd(qkv, att, lse, B, T, self.H, self.dh, probs=probs, out_fp8=att_op)
+        else:
+            ops.attn_fwd_any(qkv, att, lse, B, T, self.H, self.dh, probs=probs)
+
+    def _attn_bwd(self, s, dout, q, delta, B, T):
+        """the gradient operand q = dQKV of the block saved as s"""
+        if self.fp8:
+            ops.attn_bwd(s["qkv"], s["att"], dout, s["lse"], q.x, delta, B, T, self.H, self.dh, dqkv_fp8=q.x8, scale=q.scale, amax=q.amax)
+            self._settle(q)
+        else:
+            ops.attn_bwd_any(s["qkv"], s["att"], dout, s["lse"], q.x, delta, B, T, self.H, self.dh)
+
+    def _dgrad(self, q, i, leaf, out, epilogue=L.EPI_BF16, emits=None, **kw):
+        """input-gradient GEMM of weight `leaf` of block i on the gradient operand q; `emits`: the gradient operand the EPI_DGELU
+        epilogue writes (out is its bf16 image)"""
+        if self.fp8:
+            kw["alpha2"] = q.inv
+            if emits is not None:
+                kw.update(image=emits.x8, out_scale=emits.scale, out_amax=emits.amax)
+        self._gemm(q.x8 if self.fp8 else q.x, i, leaf, out, epilogue, dgrad=True, **kw)
+        if self.fp8 and emits is not None:
+            self._settle(emits)
+
+    def _ln_bwd(self, ln, g, q, gm_colsum, drop, **scaled):
+        """The producer of the masked gradient operand q: LayerNorm backward, ln = (dy, x, mean, rstd, block, leaf), adding into
+        the residual gradient g in place, or (ln = None) the mask + cast of g at the top of the chain.  gm_colsum: the bias
+        gradient q sums to."""
+        f8 = (q.x8, q.scale, q.amax) if self.fp8 else ()
+        if ln is None:
+            (ops.grad_mask_cast_fp8 if self.fp8 else ops.grad_mask_cast)(g, q.x, *f8, gm_colsum, drop, **scaled)
+        else:
+            *head, i, leaf = ln
+            w, b = self._n(i, leaf + ".weight"), self._n(i, leaf + ".bias")
+            (ops.layernorm_bwd_fp8 if self.fp8 else ops.layernorm_bwd)(*head, self.store.view(w), g, g, q.x, *f8, self.store.gview(w),
+                                                                       self.store.gview(b), gm_colsum, drop, **scaled)
+        if self.fp8:
+            self._settle(q)
+
     # forward ----------------------------------------------------------------
     def forward(self, x: torch.Tensor, B: int, T: int, training: bool, seed: int, save: bool, slot: str = "a",
                 return_attn: bool = False):
         """x: fp32 [B*T, D] (left untouched).  Returns (x_out fp32 [B*T, D], probs or None)."""
-        st, D, H, F, dh = self.store, self.D, self.H, self.F, self.dh
+        st, D, H, F = self.store, self.D, self.H, self.F
         self.check_tokens(T)
         M = B * T
         dev = x.device
@@ -643,68 +734,40 @@ class EncoderStack:
         if training and self.drop_path is not None:
             dp = ops.droppath_table(self.drop_path_sites(), B, seed, g(f"{slot}.dp" if save else f"{slot}.tmp.dp", (2 * self.L, B), F32, dev))
         rec["dp"] = dp
-        # (a block whose rate is 0 -- the first one of every schedule -- keeps the plain launches: its rows of the table are ones)
-        rows = lambda i, br: (dp[2 * i + br], T) if dp is not None and self.drop_path[i] > 0.0 else None      # noqa: E731
-        # LayerScale: both residual launches of every block take the column-scaled entry; only a saving forward writes the branches
-        ls = lambda i, k, branch: dict(cols=st.view(self._n(i, f"layer_scale{k}.gamma")), branch=branch) if self.layer_scale else {}   # noqa: E731
         cur = x
         for i in range(self.L):
             tag = f"{slot}.{i}." if save else f"{slot}.tmp."
+            # the operand images of the block's four GEMM inputs, kept for the weight gradients: bf16, or e4m3 (one byte per element)
+            img = lambda n, n8, cols: g(tag + (n8 if self.fp8 else n), (M, cols), FP8 if self.fp8 else BF16, dev)   # noqa: E731
+            h1, h2, a = img("h1", "h1_8", D), img("h2", "h2_8", D), img("a", "a8", F)
+            att = g(tag + "att", (M, D), BF16, dev)      # the attention backward reads the bf16 image with either kind
+            att_op = img("att", "att8", D) if self.fp8 else att
+            # LayerScale: both residual launches of every block take the column-scaled entry; only a saving forward writes the branches
             ls1 = g(tag + "ls1", (M, D), BF16, dev) if self.layer_scale and save else None
             ls2 = g(tag + "ls2", (M, D), BF16, dev) if self.layer_scale and save else None
-            h1 = None if self.fp8 else g(tag + "h1", (M, D), BF16, dev)
-            mean1 = g(tag + "mean1", (M,), F32, dev)
-            rstd1 = g(tag + "rstd1", (M,), F32, dev)
+            mean1, rstd1 = g(tag + "mean1", (M,), F32, dev), g(tag + "rstd1", (M,), F32, dev)
+            mean2, rstd2 = g(tag + "mean2", (M,), F32, dev), g(tag + "rstd2", (M,), F32, dev)
             qkv = g(tag + "qkv", (M, 3 * D), BF16, dev)
-            att = g(tag + "att", (M, D), BF16, dev)
             lse = g(tag + "lse", (B, H, T), F32, dev)
             xmid = g(tag + "xmid", (M, D), F32, dev)
-            h2 = None if self.fp8 else g(tag + "h2", (M, D), BF16, dev)
-            mean2 = g(tag + "mean2", (M,), F32, dev)
-            rstd2 = g(tag + "rstd2", (M,), F32, dev)
             u = g(tag + "u", (M, F), BF16, dev)
-            a = None if self.fp8 else g(tag + "a", (M, F), BF16, dev)
             # block output: a fresh buffer per block when saving (it is the next block's
             # LN input), otherwise ping-pong
             xout = g(f"{slot}.{i}.xout" if save else f"{slot}.tmp.xout{i & 1}", (M, D), F32, dev)
 
             if return_attn and i == self.L - 1:
                 probs = torch.empty(B, H, T, T, dtype=F32, device=dev)
-            ln1 = (cur, st.view(self._n(i, "layer_norm1.weight")), st.view(self._n(i, "layer_norm1.bias")))
-            ln2 = (xmid, st.view(self._n(i, "layer_norm2.weight")), st.view(self._n(i, "layer_norm2.bias")))
             b1, b2 = st.view(self._n(i, "feed_forward.linear_in.bias")), st.view(self._n(i, "feed_forward.linear_out.bias"))
-            if self.fp8:
-                # products on e4m3 operands: every producer also writes the e4m3 image of its output, kept per block for
-                # the weight-gradient GEMMs of the backward (one byte per element next to the bf16 images)
-                h1_8 = g(tag + "h1_8", (M, D), FP8, dev)
-                att8 = g(tag + "att8", (M, D), FP8, dev)
-                h2_8 = g(tag + "h2_8", (M, D), FP8, dev)
-                a8 = g(tag + "a8", (M, F), FP8, dev)
-                (wq, aq), (wo, ao), (w1, a1), (w2, a2) = (st.w8(self._n(i, k)) for k in ("wqkv", "wo", "w1", "w2"))
-                ops.layernorm_fwd_fp8(*ln1, None, h1_8, mean1, rstd1)     # (no bf16 images of h1 / h2 / a: nothing reads them)
-                ops.gemm_fp8_nt(h1_8, wq, qkv, L.EPI_BF16, alpha=aq)
-                ops.attn_fwd(qkv, att, lse, B, T, H, dh, probs=probs if i == self.L - 1 else None, out_fp8=att8)
-                ops.gemm_fp8_nt(att8, wo, xmid, L.EPI_RESID, alpha=ao, aux=cur, drop=self._drop(i, 0, seed, training))
-                ops.layernorm_fwd_fp8(*ln2, None, h2_8, mean2, rstd2)
-                ops.gemm_fp8_nt(h2_8, w1, u, L.EPI_GELU, alpha=a1, bias=b1, out_fp8=a8, drop=self._drop(i, 1, seed, training))
-                ops.gemm_fp8_nt(a8, w2, xout, L.EPI_RESID, alpha=a2, bias=b2, aux=xmid, drop=self._drop(i, 2, seed, training))
-            else:
-                ops.layernorm_fwd(*ln1, h1, mean1, rstd1)
-                ops.gemm_nt(h1, st.w(self._n(i, "wqkv")), qkv, L.EPI_BF16)
-                ops.attn_fwd_any(qkv, att, lse, B, T, H, dh, probs=probs if i == self.L - 1 else None)
-                ops.gemm_nt(att, st.w(self._n(i, "wo")), xmid, L.EPI_RESID, aux=cur, drop=self._drop(i, 0, seed, training), rows=rows(i, 0),
-                            **ls(i, 1, ls1))
-                ops.layernorm_fwd(*ln2, h2, mean2, rstd2)
-                ops.gemm_nt(h2, st.w(self._n(i, "w1")), u, L.EPI_GELU, bias=b1, out1=a, drop=self._drop(i, 1, seed, training))
-                ops.gemm_nt(a, st.w(self._n(i, "w2")), xout, L.EPI_RESID, bias=b2, aux=xmid, drop=self._drop(i, 2, seed, training),
-                            rows=rows(i, 1), **ls(i, 2, ls2))
+            self._ln_fwd(cur, i, "layer_norm1", h1, mean1, rstd1)
+            self._gemm(h1, i, "wqkv", qkv, L.EPI_BF16)
+            self._attn_fwd(qkv, att, att_op, lse, B, T, probs if i == self.L - 1 else None)
+            self._gemm(att_op, i, "wo", xmid, L.EPI_RESID, aux=cur, drop=self._drop(i, 0, seed, training), **self._scaled(dp, T, i, 1, branch=ls1))
+            self._ln_fwd(xmid, i, "layer_norm2", h2, mean2, rstd2)
+            self._gemm(h2, i, "w1", u, L.EPI_GELU, bias=b1, image=a, drop=self._drop(i, 1, seed, training))
+            self._gemm(a, i, "w2", xout, L.EPI_RESID, bias=b2, aux=xmid, drop=self._drop(i, 2, seed, training), **self._scaled(dp, T, i, 2, branch=ls2))
             if save:
-                rec["blocks"].append(dict(xin=cur, h1=h1, mean1=mean1, rstd1=rstd1, qkv=qkv, att=att, lse=lse, xmid=xmid,
-                                          h2=h2, mean2=mean2, rstd2=rstd2, u=u, a=a))
-                if self.fp8:
-                    rec["blocks"][-1].update(h1_8=h1_8, att8=att8, h2_8=h2_8, a8=a8)
-                if self.layer_scale:
-                    rec["blocks"][-1].update(ls1=ls1, ls2=ls2)
+                rec["blocks"].append(dict(xin=cur, h1=h1, mean1=mean1, rstd1=rstd1, qkv=qkv, att=att, att_op=att_op, lse=lse, xmid=xmid,
+                                          h2=h2, mean2=mean2, rstd2=rstd2, u=u, a=a, ls1=ls1, ls2=ls2))
             cur = xout
         if save:
             self._saved[slot] = rec
@@ -721,81 +784,81 @@ class EncoderStack:
         `input_grad_only` (bf16 operands; every block parameter frozen): the input-gradient chain runs as always, no
         weight-gradient GEMM is launched and no block range is handed to the reducer.  The per-column sums the chain's kernels
         write anyway (bias and LayerNorm gradients) still land in the blocks' slots of the gradient buffer; nothing applies
-        them.  With fp8 operands the full schedule runs."""
-        if self.fp8:
-            return self._backward_fp8(g, slot, reducer, scale_key or slot)
-        st, D, H, F, dh = self.store, self.D, self.H, self.F, self.dh
+        them.  With fp8 operands the full schedule runs.
+
+        With fp8 operands all eight backward GEMMs of every block run on e4m3 operands: the transposed weight images of the
+        store, the activation images saved by the forward, and gradient images written by the producers of the gradients
+        (LayerNorm backward, the dGELU epilogue, the attention backward's store phase)."""
+        st, D, H, F = self.store, self.D, self.H, self.F
         rec = self._saved[slot]
-        B, T, seed, training = rec["B"], rec["T"], rec["seed"], rec["training"]
+        B, T, seed, training, dp = rec["B"], rec["T"], rec["seed"], rec["training"], rec.get("dp")
         M = B * T
         dev = g.device
         w = self.ws.get
         bw = f"bwd{M}."     # keyed by the row count: slots of different sizes (DINO local / global crops) keep their own buffers
-        gm = w(bw + "gm", (M, D), BF16, dev)
-        du = w(bw + "du", (M, F), BF16, dev)
-        dh_ = w(bw + "dh", (M, D), BF16, dev)
-        dqkv = w(bw + "dqkv", (M, 3 * D), BF16, dev)
-        delta = w(bw + "delta", (B, H, T), F32, dev)
         gv = st.gview
         last = self.L - 1
-        # The four weight gradients of a block run as ONE launch at the end of the block's backward (ops.gemm_tn_batch: one split
-        # count and one reduce pass for all their tiles instead of four rounds of the CUs with 66 MB of partial tiles each).  Their
-        # gradient operands must then all be alive at that point: the LayerNorm-2 backward writes its bf16 image into a second
-        # buffer (gm2) instead of over gm.  VITSSL_TN_BATCH=0: one launch per gradient, as before.
-        batch = _os.environ.get("VITSSL_TN_BATCH", "1") != "0"
-        wgrad = not input_grad_only
-        dp = rec.get("dp")      # drop path: the forward's table; the masked operand of a branch takes the branch's row of it
-        rows = lambda i, br: (dp[2 * i + br], T) if dp is not None and self.drop_path[i] > 0.0 else None      # noqa: E731
-        gm2 = w(bw + "gm2", (M, D), BF16, dev) if batch and wgrad else gm
+        wgrad = self.fp8 or not input_grad_only
+        gs = self._grad_scale_state(dev, scale_key or slot) if self.fp8 else None
+        jit = self.fp8 and not gs["valid"]
+        # The four gradient operands of a block: 0 d(FFN out), 1 d(FFN hidden), 2 d(attention out), 3 dQKV.  The four weight
+        # gradients of a block run as ONE launch at the end of the block's backward (ops.gemm_tn_batch: one split count and one reduce
+        # pass for all their tiles instead of four rounds of the CUs with 66 MB of partial tiles each), so all four operands must be
+        # alive there: the LayerNorm-2 backward writes operand 2 into a second buffer (gm2 / gm8b) instead of over operand 0.
+        # fp8: the bf16 images exist only in the self-calibrating first backward (_settle re-quantises from them); afterwards
+        # every consumer reads the e4m3 image and the producers skip the bf16 store.
+        kinds = (("gm", "gm8", D), ("du", "du8", F), ("gm2" if wgrad and not self.fp8 else "gm", "gm8b", D), ("dqkv", "dq8", 3 * D))
+        x = [w(bw + n, (M, cols), BF16, dev) if not self.fp8 or jit else None for n, _, cols in kinds]
+        x8 = [w(bw + n8, (M, cols), FP8, dev) if self.fp8 else None for _, n8, cols in kinds]
+        dh_ = w(bw + "dh", (M, D), BF16, dev)
+        delta = w(bw + "delta", (B, H, T), F32, dev)
 
-        def ls(i, k):
-            """LayerScale arguments of the kernel that emits the masked operand of branch k of block i: gamma, and (unless the
-            blocks are frozen) the saved branch and the slot of gamma's gradient."""
-            if not self.layer_scale:
-                return {}
-            name = self._n(i, f"layer_scale{k}.gamma")
-            if not wgrad:
-                return dict(cols=st.view(name))
-            return dict(cols=st.view(name), branch=rec["blocks"][i][f"ls{k}"], dls=gv(name))
+        plain = [_GradOperand(t) for t in x]
+
+        def grad(i, t):
+            """gradient operand t of block i: with fp8 operands every (i, t) has its own scale"""
+            if not self.fp8:
+                return plain[t]
+            return _GradOperand(x[t], x8[t], gs["scale"][i, t:t + 1], gs["amax"][i, t:t + 1], gs["inv"][i, t:t + 1])
+
+        def scaled(i, k):
+            """_scaled() of the producer of the masked operand of branch k of block i (LayerScale: gamma's gradient needs the saved
+            branch; not with frozen blocks)"""
+            return self._scaled(dp, T, i, k, branch=rec["blocks"][i][f"ls{k}"] if wgrad else None, dls=wgrad)
 
         # top of the chain: dropout-mask + cast of g, and the last block's linear_out bias grad
-        ops.grad_mask_cast(g, gm, gv(self._n(last, "feed_forward.linear_out.bias")), self._drop(last, 2, seed, training),
-                           rows=rows(last, 1), **ls(last, 2))
+        gm = grad(last, 0)
+        self._ln_bwd(None, g, gm, gv(self._n(last, "feed_forward.linear_out.bias")), self._drop(last, 2, seed, training), **scaled(last, 2))
         for i in range(last, -1, -1):
             s = rec["blocks"][i]
             a_ = self.bp[i] + "self_attention."
+            du, gm2, dqkv = grad(i, 1), grad(i, 2), grad(i, 3)
             # MLP
-            wgrads = [(gm, s["a"], gv(self._n(i, "feed_forward.linear_out.weight"), (D, F))),
-                      (du, s["h2"], gv(self._n(i, "feed_forward.linear_in.weight"), (F, D))),
-                      (gm2, s["att"], gv(a_ + "final_linear.weight", (D, D))),
-                      (dqkv, s["h1"], st.span_view(a_ + "w_query.weight", a_ + "w_value.weight", (3 * D, D), grad=True))]
-            ops.gemm_nt(gm, st.w(self._n(i, "w2") + ".T"), du, L.EPI_DGELU, aux=s["u"],
+            self._dgrad(gm, i, "w2", du.x, L.EPI_DGELU, emits=du, aux=s["u"],
                         colsum=gv(self._n(i, "feed_forward.linear_in.bias")))   # s["u"] holds g' = keep*scale*gelu'(u)
-            if wgrad and not batch:
-                ops.gemm_tn(*wgrads[0])
-            ops.gemm_nt(du, st.w(self._n(i, "w1") + ".T"), dh_, L.EPI_BF16)
-            if wgrad and not batch:
-                ops.gemm_tn(*wgrads[1])
-            ops.layernorm_bwd(dh_, s["xmid"], s["mean2"], s["rstd2"], st.view(self._n(i, "layer_norm2.weight")), g, g, gm2,
-                              gv(self._n(i, "layer_norm2.weight")), gv(self._n(i, "layer_norm2.bias")), None,
-                              self._drop(i, 0, seed, training), rows=rows(i, 0), **ls(i, 1))
+            self._dgrad(du, i, "w1", dh_)
+            self._ln_bwd((dh_, s["xmid"], s["mean2"], s["rstd2"], i, "layer_norm2"), g, gm2, None, self._drop(i, 0, seed, training),
+                         **scaled(i, 1))
             # attention
-            ops.gemm_nt(gm2, st.w(self._n(i, "wo") + ".T"), dh_, L.EPI_BF16)
-            if wgrad and not batch:
-                ops.gemm_tn(*wgrads[2])
-            ops.attn_bwd_any(s["qkv"], s["att"], dh_, s["lse"], dqkv, delta, B, T, H, dh)
-            ops.gemm_nt(dqkv, st.w(self._n(i, "wqkv") + ".T"), dh_, L.EPI_BF16)
-            if wgrad and batch:
-                ops.gemm_tn_batch(wgrads)      # before the LayerNorm-1 backward below overwrites gm for the next block
-            elif wgrad:
-                ops.gemm_tn(*wgrads[3])
+            self._dgrad(gm2, i, "wo", dh_)
+            self._attn_bwd(s, dh_, dqkv, delta, B, T)
+            self._dgrad(dqkv, i, "wqkv", dh_)
+            if wgrad:      # before the LayerNorm-1 backward below overwrites operand 0 for the next block
+                jobs = [(gm, s["a"], gv(self._n(i, "feed_forward.linear_out.weight"), (D, F))),
+                        (du, s["h2"], gv(self._n(i, "feed_forward.linear_in.weight"), (F, D))),
+                        (gm2, s["att_op"], gv(a_ + "final_linear.weight", (D, D))),
+                        (dqkv, s["h1"], st.span_view(a_ + "w_query.weight", a_ + "w_value.weight", (3 * D, D), grad=True))]
+                if self.fp8:
+                    ops.gemm_fp8_tn_batch([(q.x8, act, dw, None, q.inv) for q, act, dw in jobs])
+                else:
+                    ops.gemm_tn_batch([(q.x, act, dw) for q, act, dw in jobs])
+            ln1 = (dh_, s["xin"], s["mean1"], s["rstd1"])
             if i > 0:
-                ops.layernorm_bwd(dh_, s["xin"], s["mean1"], s["rstd1"], st.view(self._n(i, "layer_norm1.weight")), g, g, gm,
-                                  gv(self._n(i, "layer_norm1.weight")), gv(self._n(i, "layer_norm1.bias")),
-                                  gv(self._n(i - 1, "feed_forward.linear_out.bias")), self._drop(i - 1, 2, seed, training),
-                                  rows=rows(i - 1, 1), **ls(i - 1, 2))
-            else:
-                ops.layernorm_bwd(dh_, s["xin"], s["mean1"], s["rstd1"], st.view(self._n(i, "layer_norm1.weight")), g, g, None,
+                gm = grad(i - 1, 0)
+                self._ln_bwd(ln1 + (i, "layer_norm1"), g, gm, gv(self._n(i - 1, "feed_forward.linear_out.bias")),
+                             self._drop(i - 1, 2, seed, training), **scaled(i - 1, 2))
+            else:      # nothing reads a masked operand below the first block: the plain launch with either kind
+                ops.layernorm_bwd(*ln1, st.view(self._n(i, "layer_norm1.weight")), g, g, None,
                                   gv(self._n(i, "layer_norm1.weight")), gv(self._n(i, "layer_norm1.bias")), None, ops.NO_DROP)
             if reducer is not None and wgrad:
                 # every gradient of block i is final, except linear_out.bias of block i-1,
@@ -805,9 +868,15 @@ class EncoderStack:
                 # of block i - 1, which like its linear_out.bias belongs to the next range.)
                 lo, hi = self.block_span(i)
                 reducer.ready(lo, hi)
+        if self.fp8:
+            # scales of the NEXT backward: this step's max |value| with one bit of headroom
+            gs["used"].copy_(gs["scale"])
+            self._rescale(gs["scale"], gs["inv"], gs["amax"], margin=1)
+            gs["amax"].zero_()
+            gs["valid"] = True
         return g
 
-    # fp8 input-gradient GEMMs ----------------------------------------------------
+    # fp8 gradient operands: delayed scaling ------------------------------------------
     @staticmethod
     def _scale_from_amax(amax: torch.Tensor, margin: int) -> torch.Tensor:
         """2^(floor(log2(448 / amax)) - margin) on the binary representation (the rule of csrc/fp8.hip)."""
@@ -825,15 +894,19 @@ class EncoderStack:
         self._gs = gs
         return gs
 
-    def _rescale(self, sel, margin: int):
-        """scale / inv of the selected entries of the running slot from their recorded max |value| (left alone where that is 0
-        or not finite)."""
-        gs = self._gs
-        a = gs["amax"][sel]
-        ok = (a > 0) & torch.isfinite(a)
-        new = torch.where(ok, self._scale_from_amax(torch.where(ok, a, torch.ones_like(a)), margin), gs["scale"][sel])
-        gs["scale"][sel] = new
-        gs["inv"][sel] = 1.0 / new
+    def _rescale(self, scale, inv, amax, margin: int):
+        """scale / inv (views of the slot's state) from the recorded max |value| (left alone where that is 0 or not finite)."""
+        ok = (amax > 0) & torch.isfinite(amax)
+        new = torch.where(ok, self._scale_from_amax(torch.where(ok, amax, torch.ones_like(amax)), margin), scale)
+        scale.copy_(new)
+        inv.copy_(1.0 / new)
+
+    def _settle(self, q):
+        """first fp8 backward of a slot only (q has both images): the producer of q has just recorded max |q|; take the scale from
+        it and quantise again"""
+        if q.x is not None and q.x8 is not None:
+            self._rescale(q.scale, q.inv, q.amax, margin=0)
+            ops.quantize_fp8(q.x, q.x8, scale=q.scale)
 
     def fp8_grad_scales(self, slot: Optional[str] = None) -> torch.Tensor:
         """[L, 4] scales the last backward (of `slot`, default: whichever ran last) quantised its gradient operands with
@@ -845,92 +918,3 @@ class EncoderStack:
         """Derive the gradient scales from the tensors themselves in the next backward of every slot (as the first one does)."""
         for gs in self._gs_by_slot.values():
             gs["valid"] = False
-
-    def _backward_fp8(self, g: torch.Tensor, slot: str, reducer: Optional[GradReducer], scale_key: str) -> torch.Tensor:
-        """The schedule of backward() with all eight backward GEMMs of every block on e4m3 operands: the transposed
-        weight images of the store, the activation images saved by the forward, and gradient images written by the
-        producers of the gradients (LayerNorm backward, the dGELU epilogue, the attention backward's store phase)."""
-        st, D, H, F, dh = self.store, self.D, self.H, self.F, self.dh
-        rec = self._saved[slot]
-        B, T, seed, training = rec["B"], rec["T"], rec["seed"], rec["training"]
-        M = B * T
-        dev = g.device
-        w = self.ws.get
-        bw = f"bwd{M}."     # keyed by the row count: slots of different sizes (DINO local / global crops) keep their own buffers
-        gm8, du8, dq8 = w(bw + "gm8", (M, D), FP8, dev), w(bw + "du8", (M, F), FP8, dev), w(bw + "dq8", (M, 3 * D), FP8, dev)
-        batch = _os.environ.get("VITSSL_TN_BATCH", "1") != "0"       # as in backward(): the block's four weight gradients in one launch
-        gm8b = w(bw + "gm8b", (M, D), FP8, dev) if batch else gm8
-        dh_ = w(bw + "dh", (M, D), BF16, dev)
-        delta = w(bw + "delta", (B, H, T), F32, dev)
-        gv = st.gview
-        gs = self._grad_scale_state(dev, scale_key)
-        sc = lambda i, t: gs["scale"][i, t:t + 1]   # noqa: E731
-        inv = lambda i, t: gs["inv"][i, t:t + 1]    # noqa: E731
-        am = lambda i, t: gs["amax"][i, t:t + 1]    # noqa: E731
-        jit = not gs["valid"]
-        # bf16 images of the gradient operands exist only in the self-calibrating first backward (settle() re-quantises
-        # from them); afterwards every consumer reads the e4m3 image and the producers skip the bf16 store
-        gm = w(bw + "gm", (M, D), BF16, dev) if jit else None
-        du = w(bw + "du", (M, F), BF16, dev) if jit else None
-        dqkv = w(bw + "dqkv", (M, 3 * D), BF16, dev) if jit else None
-
-        def settle(i, t, x, x8):
-            """first backward only: the producer has just recorded max|x|; take the scale from it and quantise again"""
-            if jit:
-                self._rescale((slice(i, i + 1), slice(t, t + 1)), margin=0)
-                ops.quantize_fp8(x, x8, scale=sc(i, t))
-
-        last = self.L - 1
-        ops.grad_mask_cast_fp8(g, gm, gm8, sc(last, 0), am(last, 0), gv(self._n(last, "feed_forward.linear_out.bias")),
-                               self._drop(last, 2, seed, training))
-        settle(last, 0, gm, gm8)
-        for i in range(last, -1, -1):
-            s = rec["blocks"][i]
-            a_ = self.bp[i] + "self_attention."
-            (w2t, a2), (w1t, a1), (wot, ao), (wqt, aq) = (st.w8t(self._n(i, k)) for k in ("w2", "w1", "wo", "wqkv"))
-            # MLP
-            ops.gemm_fp8_nt(gm8, w2t, du, L.EPI_DGELU, alpha=a2, alpha2=inv(i, 0), aux=s["u"],
-                            colsum=gv(self._n(i, "feed_forward.linear_in.bias")), out_fp8=du8, out_scale=sc(i, 1), out_amax=am(i, 1))
-            settle(i, 1, du, du8)
-            wgrads = [(gm8, s["a8"], gv(self._n(i, "feed_forward.linear_out.weight"), (D, F)), None, inv(i, 0)),
-                      (du8, s["h2_8"], gv(self._n(i, "feed_forward.linear_in.weight"), (F, D)), None, inv(i, 1)),
-                      (gm8b, s["att8"], gv(a_ + "final_linear.weight", (D, D)), None, inv(i, 2)),
-                      (dq8, s["h1_8"], st.span_view(a_ + "w_query.weight", a_ + "w_value.weight", (3 * D, D), grad=True), None, inv(i, 3))]
-            single = lambda j: ops.gemm_fp8_tn(wgrads[j][0], wgrads[j][1], wgrads[j][2], alpha2=wgrads[j][4])   # noqa: E731
-            if not batch:
-                single(0)
-            ops.gemm_fp8_nt(du8, w1t, dh_, L.EPI_BF16, alpha=a1, alpha2=inv(i, 1))
-            if not batch:
-                single(1)
-            ops.layernorm_bwd_fp8(dh_, s["xmid"], s["mean2"], s["rstd2"], st.view(self._n(i, "layer_norm2.weight")), g, g, gm, gm8b,
-                                  sc(i, 2), am(i, 2), gv(self._n(i, "layer_norm2.weight")), gv(self._n(i, "layer_norm2.bias")), None,
-                                  self._drop(i, 0, seed, training))
-            settle(i, 2, gm, gm8b)
-            # attention
-            ops.gemm_fp8_nt(gm8b, wot, dh_, L.EPI_BF16, alpha=ao, alpha2=inv(i, 2))
-            if not batch:
-                single(2)
-            ops.attn_bwd(s["qkv"], s["att"], dh_, s["lse"], dqkv, delta, B, T, H, dh, dqkv_fp8=dq8, scale=sc(i, 3), amax=am(i, 3))
-            settle(i, 3, dqkv, dq8)
-            ops.gemm_fp8_nt(dq8, wqt, dh_, L.EPI_BF16, alpha=aq, alpha2=inv(i, 3))
-            if batch:
-                ops.gemm_fp8_tn_batch(wgrads)      # before the LayerNorm-1 backward below overwrites gm8 for the next block
-            else:
-                single(3)
-            if i > 0:
-                ops.layernorm_bwd_fp8(dh_, s["xin"], s["mean1"], s["rstd1"], st.view(self._n(i, "layer_norm1.weight")), g, g, gm, gm8,
-                                      sc(i - 1, 0), am(i - 1, 0), gv(self._n(i, "layer_norm1.weight")), gv(self._n(i, "layer_norm1.bias")),
-                                      gv(self._n(i - 1, "feed_forward.linear_out.bias")), self._drop(i - 1, 2, seed, training))
-                settle(i - 1, 0, gm, gm8)
-            else:
-                ops.layernorm_bwd(dh_, s["xin"], s["mean1"], s["rstd1"], st.view(self._n(i, "layer_norm1.weight")), g, g, None,
-                                  gv(self._n(i, "layer_norm1.weight")), gv(self._n(i, "layer_norm1.bias")), None, ops.NO_DROP)
-            if reducer is not None:
-                lo, hi = self.block_span(i)
-                reducer.ready(lo, hi)
-        # scales of the NEXT backward: this step's max |value| with one bit of headroom
-        gs["used"].copy_(gs["scale"])
-        self._rescale((slice(None), slice(None)), margin=1)
-        gs["amax"].zero_()
-        gs["valid"] = True
-        return g

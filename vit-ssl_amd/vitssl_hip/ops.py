@@ -213,6 +213,35 @@ def grad_mask_cast_fp8(g, gm, gm8, scale, amax, gm_colsum=None, drop=NO_DROP):
 _OUT0_DTYPE = {L.EPI_BF16: BF16, L.EPI_F32: F32, L.EPI_GELU: BF16, L.EPI_RESID: F32, L.EPI_DGELU: BF16, L.EPI_EMBED: F32}
 
 
+def _nt_desc(who, sfx, dtype, A, B, epilogue, bias, set_out0, aux, dgelu_aux, out1, colsum, drop, epilogues=None):
+    """The vitssl_gemm_t of gemm_nt / gemm_fp8_nt: operands of `dtype` (named "A" + sfx, "B" + sfx in error texts), M / N / K, bias,
+    out0 (set_out0(g, M, N): the entry points' rules differ), aux by epilogue, out1, colsum with its workspace, dropout.
+    -> (g, M, N, K)"""
+    M, K = A.shape
+    N, K2 = B.shape
+    if K != K2:
+        raise L.VitsslError(f"{who}: K mismatch {K} vs {K2}")
+    if epilogues is not None and epilogue not in epilogues:
+        raise L.VitsslError(f"{who}: epilogue {epilogue} has no fp8-operand form")
+    g = Gemm()
+    g.A = _chk(A, dtype, "A" + sfx)
+    g.B = _chk(B, dtype, "B" + sfx)
+    g.M, g.N, g.K = M, N, K
+    g.epilogue = epilogue
+    g.bias = _opt(bias, F32, "bias", (N,))
+    set_out0(g, M, N)
+    if epilogue == L.EPI_RESID:
+        g.aux = _chk(aux, F32, "aux(residual)", (M, N))
+    elif epilogue == L.EPI_DGELU:
+        g.aux = _chk(aux, BF16, dgelu_aux, (M, N))
+    g.out1 = _opt(out1, BF16, "out1", (M, N))
+    g.colsum = _opt(colsum, F32, "colsum", (N,))
+    if colsum is not None:
+        g.workspace, g.workspace_floats = _sum_ws(colsum.device, M, N)
+    g.drop = drop
+    return g, M, N, K
+
+
 def gemm_nt(A, B, out0, epilogue, bias=None, aux=None, out1=None, colsum=None, drop=NO_DROP, embed=None, rows=None, cols=None,
             branch=None):
     """out = A[M,K] @ B[N,K]^T with the fused epilogue (see include/vitssl_hip.h).  rows=(scale, rows_per_group) selects
@@ -220,17 +249,10 @@ def gemm_nt(A, B, out0, epilogue, bias=None, aux=None, out1=None, colsum=None, d
     cols=gamma f32 [N] selects vitssl_gemm_bf16_nt_ls (EPI_RESID only; LayerScale, composes with rows=):
     out0 = aux + scale[row // rows_per_group] * gamma[col] * drop(acc + bias), and branch= (bf16 [M, N], optional) receives
     drop(acc + bias), what the backward multiplies gamma's gradient from."""
-    M, K = A.shape
-    N, K2 = B.shape
-    if K != K2:
-        raise L.VitsslError(f"gemm_nt: K mismatch {K} vs {K2}")
-    g = Gemm()
-    g.A = _chk(A, BF16, "A")
-    g.B = _chk(B, BF16, "B")
-    g.M, g.N, g.K = M, N, K
-    g.epilogue = epilogue
-    g.bias = _opt(bias, F32, "bias", (N,))
-    if epilogue == L.EPI_EMBED:
+    def set_out0(g, M, N):
+        if epilogue != L.EPI_EMBED:
+            g.out0 = _chk(out0, _OUT0_DTYPE[epilogue], "out0", (M, N))
+            return
         if embed is None:
             raise L.VitsslError("gemm_nt: EPI_EMBED needs embed=(mask, mask_token, pos, tokens, out_tokens, tok_offset)")
         mask, mask_token, pos, tokens, out_tokens, tok_offset = embed
@@ -243,17 +265,8 @@ def gemm_nt(A, B, out0, epilogue, bias=None, aux=None, out1=None, colsum=None, d
         e.tokens, e.out_tokens, e.tok_offset = tokens, out_tokens, tok_offset
         g.embed = e
         g.out0 = _chk(out0, F32, "out0", ((M // tokens) * out_tokens, N))
-    else:
-        g.out0 = _chk(out0, _OUT0_DTYPE[epilogue], "out0", (M, N))
-    if epilogue == L.EPI_RESID:
-        g.aux = _chk(aux, F32, "aux(residual)", (M, N))
-    elif epilogue == L.EPI_DGELU:
-        g.aux = _chk(aux, BF16, "aux(u)", (M, N))
-    g.out1 = _opt(out1, BF16, "out1", (M, N))
-    g.colsum = _opt(colsum, F32, "colsum", (N,))
-    if colsum is not None:
-        g.workspace, g.workspace_floats = _sum_ws(colsum.device, M, N)
-    g.drop = drop
+
+    g, M, N, K = _nt_desc("gemm_nt", "", BF16, A, B, epilogue, bias, set_out0, aux, "aux(u)", out1, colsum, drop)
     ev = _prof_begin()
     if cols is not None:
         if epilogue != L.EPI_RESID:
@@ -277,30 +290,13 @@ def gemm_fp8_nt(A8, B8, out0, epilogue, alpha=None, bias=None, aux=None, out1=No
     `alpha2` 1-element device tensors (dequantisation factors of the two operands).  `out_fp8`: optional e4m3 image of
     out1 (EPI_GELU) or of out0 (EPI_DGELU), written as e4m3(value * out_scale) with max|value| recorded in out_amax.
     Forward and input-gradient GEMMs (include/vitssl_hip.h)."""
-    M, K = A8.shape
-    N, K2 = B8.shape
-    if K != K2:
-        raise L.VitsslError(f"gemm_fp8_nt: K mismatch {K} vs {K2}")
-    if epilogue not in (L.EPI_BF16, L.EPI_F32, L.EPI_GELU, L.EPI_RESID, L.EPI_DGELU):
-        raise L.VitsslError(f"gemm_fp8_nt: epilogue {epilogue} has no fp8-operand form")
-    g = Gemm()
-    g.A = _chk(A8, FP8, "A8")
-    g.B = _chk(B8, FP8, "B8")
-    g.M, g.N, g.K = M, N, K
-    g.epilogue = epilogue
-    g.bias = _opt(bias, F32, "bias", (N,))
-    if out0 is None and not (epilogue == L.EPI_DGELU and out_fp8 is not None):
-        raise L.VitsslError("gemm_fp8_nt: out0 may only be omitted for EPI_DGELU with out_fp8")
-    g.out0 = _opt(out0, _OUT0_DTYPE[epilogue], "out0", (M, N))
-    if epilogue == L.EPI_RESID:
-        g.aux = _chk(aux, F32, "aux(residual)", (M, N))
-    elif epilogue == L.EPI_DGELU:
-        g.aux = _chk(aux, BF16, "aux(g')", (M, N))
-    g.out1 = _opt(out1, BF16, "out1", (M, N))
-    g.colsum = _opt(colsum, F32, "colsum", (N,))
-    if colsum is not None:
-        g.workspace, g.workspace_floats = _sum_ws(colsum.device, M, N)
-    g.drop = drop
+    def set_out0(g, M, N):
+        if out0 is None and not (epilogue == L.EPI_DGELU and out_fp8 is not None):
+            raise L.VitsslError("gemm_fp8_nt: out0 may only be omitted for EPI_DGELU with out_fp8")
+        g.out0 = _opt(out0, _OUT0_DTYPE[epilogue], "out0", (M, N))
+
+    g, M, N, K = _nt_desc("gemm_fp8_nt", "8", FP8, A8, B8, epilogue, bias, set_out0, aux, "aux(g')", out1, colsum, drop,
+                          epilogues=(L.EPI_BF16, L.EPI_F32, L.EPI_GELU, L.EPI_RESID, L.EPI_DGELU))
     q = Fp8Gemm()
     q.alpha = _scalar(alpha, "alpha")
     q.alpha2 = _scalar(alpha2, "alpha2")
