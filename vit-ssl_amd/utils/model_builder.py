@@ -8,6 +8,7 @@ import torch
 
 from vit_core.vit import ViT
 from vit_core.ssl.dino.model import DINOViT
+from vit_core.ssl.mae.model import MAEViT
 from vit_core.ssl.simmim.model import SimMIMViT
 
 from ._config import cfg_get
@@ -17,20 +18,45 @@ logger = logging.getLogger(__name__)
 
 _COMPILE_PREFIX = "_orig_mod."                 # key prefix of checkpoints saved from a torch.compile-wrapped model
 _SSL_ONLY = ("simmim_head", "mask_token")      # tensors that exist only while pre-training
+_MAE_MARK = "decoder_pred.weight"              # a checkpoint that holds it is an MAEViT's (`_place`, mae=True)
 
 
 def strip_compile_prefix(state_dict):
     return {k.removeprefix(_COMPILE_PREFIX): v for k, v in state_dict.items()}
 
 
-def _place(key, tensor, target):
+def _place_mae(key, tensor, target, fits):
+    """`_place` for a tensor of an MAEViT checkpoint going into a ViT: the patch projection is the embedder's convolution (the
+    unfold order is (c, kh, kw), so the reshape is the same linear map), CLS token and position table carry over, the encoder
+    blocks keep their keys; the final norm, the mask token and the decoder exist only while pre-training."""
+    conv = "patch_embedding.conv.weight"
+    if key == "projection.weight" and conv in target:
+        slot = target[conv]
+        if tensor.dim() == 2 and tensor.shape[0] == slot.shape[0] and tensor.shape[1] == slot[0].numel():
+            return conv, tensor.reshape(slot.shape)
+        return None, f"projection {tuple(tensor.shape)} cannot seed the convolution {tuple(slot.shape)}"
+    moved = {"projection.bias": "patch_embedding.conv.bias", "cls_token": "patch_embedding.cls_token",
+             "pos_embed": "patch_embedding.positional_embedding"}
+    if key in moved and moved[key] in target:
+        return fits(moved[key], tensor)
+    if key == "mask_token" or key.startswith(("norm.", "decoder_")):
+        return None, "pre-training-only tensor"
+    if key in target:
+        return fits(key, tensor)
+    return None, "no such parameter in the model"
+
+
+def _place(key, tensor, target, mae=False):
     """Where a checkpoint tensor goes in a model with state `target`.
-    Returns (destination key, tensor) or (None, reason)."""
+    Returns (destination key, tensor) or (None, reason).  `mae`: the checkpoint is an MAEViT's (it holds decoder_pred.weight)
+    and the model is not one; every other placement is untouched by it."""
     def fits(dst_key, t):
         if t.shape == target[dst_key].shape:
             return dst_key, t
         return None, f"shape {tuple(t.shape)} != model's {tuple(target[dst_key].shape)} for {dst_key}"
 
+    if mae:
+        return _place_mae(key, tensor, target, fits)
     if key in target:
         return fits(key, tensor)
     embedded = f"patch_embedding.{key}"
@@ -59,8 +85,9 @@ def load_weights(model, checkpoint_path: str):
     source = strip_compile_prefix(payload.get("model_state_dict", payload))
     target = model.state_dict()
     accepted, skipped = {}, {}
+    mae = _MAE_MARK in source and _MAE_MARK not in target      # MAE pre-training weights into another model (see `_place_mae`)
     for key, tensor in source.items():
-        dst_key, result = _place(key, tensor, target)
+        dst_key, result = _place(key, tensor, target, mae=mae)
         if dst_key is None:
             skipped[key] = result
         else:
@@ -93,6 +120,17 @@ def _resolve_mode(config) -> str:
     return mode.lower()
 
 
+def _make_mae(m, backbone):
+    """MAEViT from the backbone keys and the MAE keys under `model` (mask_ratio, decoder_embed_dim, decoder_blocks,
+    decoder_heads, decoder_mlp_dim, norm_pix_loss), each optional (absent: MAEViT's own default).  The model takes no dropout
+    (absent counts as 0), drop path or LayerScale: it raises ValueError for them."""
+    extra = [k for k in ("drop_path_rate", "layer_scale_init") if k in backbone]
+    if extra:
+        raise ValueError(f"mode 'mae': model.{extra[0]} is not built for MAEViT; remove the key")
+    keys = ("mask_ratio", "decoder_embed_dim", "decoder_blocks", "decoder_heads", "decoder_mlp_dim", "norm_pix_loss")
+    return MAEViT(**{**backbone, "dropout": backbone["dropout"] or 0.0}, **{k: m(k) for k in keys if m(k) is not None})
+
+
 def build_model(config):
     """config -> module, by mode (reference: utils/model_builder.py:104-184)."""
     mode = _resolve_mode(config)
@@ -110,6 +148,7 @@ def build_model(config):
         "supervised": lambda: ViT(num_classes=m("num_classes"), **backbone),
         "simmim": lambda: SimMIMViT(mask_ratio=m("mask_ratio"), **backbone),
         "dino": lambda: DINOViT(output_dim=m("output_dim"), center_momentum=m("center_momentum"), **backbone),
+        "mae": lambda: _make_mae(m, backbone),
     }
     makers["finetune"], makers["eval_dino"] = makers["supervised"], makers["dino"]
     if mode not in makers:

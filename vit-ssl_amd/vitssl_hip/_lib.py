@@ -12,6 +12,10 @@ _INCLUDE = os.path.normpath(os.path.join(_HERE, "..", "..", "include"))
 HEADERS = {key: os.path.join(_INCLUDE, f"vitssl_{key}.h")
            for key in ("hip", "transforms", "metrics", "classify", "attention_hd", "patch", "optim", "mixup", "droppath", "layerscale",
                        "lamb", "bce")}
+# extension tables: entry points of the same library declared outside include/ (HEADERS, REGISTRY and STRUCTS above stay the
+# twelve-header ABI); EXT_REGISTRY below has one table per key
+_INCLUDE_EXT = os.path.normpath(os.path.join(_HERE, "..", "..", "include_ext"))
+EXT_HEADERS = {"mae": os.path.join(_INCLUDE_EXT, "vitssl_mae.h")}
 
 
 class VitsslError(RuntimeError):
@@ -241,6 +245,22 @@ _ABI = {
 # header key -> function name -> (restype, argtypes)
 REGISTRY = {key: {name: p if isinstance(p, tuple) else (C.c_int, p) for name, p in table.items()} for key, table in _ABI.items()}
 
+_EXT_ABI = {
+    # include_ext/vitssl_mae.h: MAE token assembly, un-shuffle, normalised-pixel MSE loss, rows by index
+    "mae": {
+        "vitssl_mae_tokens_fwd": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
+        "vitssl_mae_tokens_bwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i64, _vp],
+        "vitssl_mae_unshuffle_fwd": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
+        "vitssl_mae_unshuffle_bwd": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i64, _vp],
+        "vitssl_mae_loss": [_vp, _i64, _vp, _vp, _vp, _i64, _i, _i, _i, _f, _vp, _i64, _vp],
+        "vitssl_mae_gather_rows_bf16": [_vp, _vp, _vp, _i64, _i, _vp],
+        "vitssl_mae_gather_rows_f32": [_vp, _vp, _vp, _i64, _i, _vp],
+        "vitssl_mae_scatter_rows_f32": [_vp, _vp, _vp, _i64, _i, _vp],
+    },
+}
+# extension key -> function name -> (restype, argtypes), the form of REGISTRY
+EXT_REGISTRY = {key: {name: p if isinstance(p, tuple) else (C.c_int, p) for name, p in table.items()} for key, table in _EXT_ABI.items()}
+
 DROPPATH_SITE_BIT = 0x80000000          # VITSSL_DROPPATH_SITE_BIT
 DROPPATH_MAX_SITES = 128                # VITSSL_DROPPATH_MAX_SITES
 LAMB_ALWAYS_ADAPT, LAMB_TRUST_CLIP = 1, 2          # VITSSL_LAMB_ALWAYS_ADAPT, VITSSL_LAMB_TRUST_CLIP
@@ -248,9 +268,14 @@ LAMB_ALWAYS_ADAPT, LAMB_TRUST_CLIP = 1, 2          # VITSSL_LAMB_ALWAYS_ADAPT, V
 _lib = None
 
 
+def header_path(key):
+    """include/vitssl_<key>.h, or include_ext/vitssl_<key>.h for an extension key."""
+    return HEADERS[key] if key in HEADERS else EXT_HEADERS[key]
+
+
 def header_text(key):
     """The header without its block comments, line comments and preprocessor lines: what is left are declarations."""
-    with open(HEADERS[key]) as f:
+    with open(header_path(key)) as f:
         txt = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)        # the comments name functions of other headers in running text
     return re.sub(r"//.*$|^\s*#.*$", "", txt, flags=re.M)            # and so do the macros
 
@@ -290,7 +315,7 @@ def lib():
     if l.vitssl_version() != ABI_VERSION:        # int vitssl_version(void): ctypes' defaults call it right before anything is bound
         raise VitsslError(f"{LIB_PATH} implements C-ABI version {l.vitssl_version()}, these bindings expect {ABI_VERSION}: "
                           "rebuild it (python __graft_entry__.py)")
-    for table in REGISTRY.values():
+    for table in list(REGISTRY.values()) + list(EXT_REGISTRY.values()):      # the extension tables after the registry
         for name, (restype, argtypes) in table.items():
             fn = getattr(l, name)  # AttributeError if the symbol is missing
             fn.restype, fn.argtypes = restype, argtypes

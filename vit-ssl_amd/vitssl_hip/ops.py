@@ -1029,3 +1029,90 @@ def classify_bce(logits, labels, C, loss_out, pred, counters, bad_labels, partne
     _classify("classify_bce", "vitssl_classify_bce", "vitssl_classify_bce_workspace_floats",
               ((partner, I32, "partner"), (lam, F32, "lam")), logits, labels, C, loss_out, pred, counters, bad_labels, dlogits, dbias,
               smoothing, ignore_index, upstream, workspace, scalars=(thr, int(bool(sum_classes))), nullable=True)
+
+
+# ---- MAE token plumbing and loss (include_ext/vitssl_mae.h) ----
+def _mae_shape(who, B, N, K, D):
+    B, N, K, D = int(B), int(N), int(K), int(D)
+    if B <= 0 or N <= 0 or D <= 0 or D % 4 != 0:
+        raise L.VitsslError(f"{who}: B={B}, N={N} must be positive and the width {D} a positive multiple of 4")
+    if not 1 <= K <= N - 1:
+        raise L.VitsslError(f"{who}: K={K} kept patches outside [1, N-1] with N={N}")
+    return B, N, K, D
+
+
+def mae_tokens_fwd(xk, keep, pos, cls, out, B, N, K):
+    """out f32 [B*(K+1), D]: row (b, 0) = cls + pos[0], row (b, 1+j) = xk[b, j] + pos[1 + keep[b, j]]; keep int32 [B, K]"""
+    B, N, K, D = _mae_shape("mae_tokens_fwd", B, N, K, xk.shape[-1])
+    call("vitssl_mae_tokens_fwd", _chk(xk, F32, "xk", (B * K, D)), _chk(keep, I32, "keep", (B, K)), _chk(pos, F32, "pos", (N + 1, D)),
+         _chk(cls, F32, "cls", (D,)), _chk(out, F32, "out", (B * (K + 1), D)), B, N, K, D, _stream())
+
+
+def mae_tokens_bwd(g, dproj, dbias, dcls, B, N, K):
+    """g f32 [B*(K+1), D] -> dproj bf16 [B*K, D] (the patch rows), dbias += their f32 column sum, dcls += that of the CLS rows"""
+    B, N, K, D = _mae_shape("mae_tokens_bwd", B, N, K, g.shape[-1])
+    call("vitssl_mae_tokens_bwd", _chk(g, F32, "g", (B * (K + 1), D)), _chk(dproj, BF16, "dproj", (B * K, D)), _chk(dbias, F32, "dbias", (D,)),
+         _chk(dcls, F32, "dcls", (D,)), B, N, K, D, *_sum_ws(g.device, B * (K + 1), D), _stream())
+
+
+def mae_unshuffle_fwd(y, restore, mask_token, dpos, out, B, N, K):
+    """out f32 [B*(N+1), Dd]: row (b, 0) = y[b, 0] + dpos[0], row (b, 1+n) = (y[b, 1 + restore[b, n]] if restore[b, n] < K else
+    mask_token) + dpos[1+n]; restore int32 [B, N]"""
+    B, N, K, D = _mae_shape("mae_unshuffle_fwd", B, N, K, y.shape[-1])
+    call("vitssl_mae_unshuffle_fwd", _chk(y, F32, "y", (B * (K + 1), D)), _chk(restore, I32, "restore", (B, N)),
+         _chk(mask_token, F32, "mask_token", (D,)), _chk(dpos, F32, "dpos", (N + 1, D)), _chk(out, F32, "out", (B * (N + 1), D)),
+         B, N, K, D, _stream())
+
+
+def mae_unshuffle_bwd(g, restore, dy, dbias, dmask_token, B, N, K):
+    """g f32 [B*(N+1), Dd] -> dy bf16 [B*(K+1), Dd] (CLS and kept rows, in shuffle order), dbias += their f32 column sum,
+    dmask_token += the column sum of the masked rows"""
+    B, N, K, D = _mae_shape("mae_unshuffle_bwd", B, N, K, g.shape[-1])
+    call("vitssl_mae_unshuffle_bwd", _chk(g, F32, "g", (B * (N + 1), D)), _chk(restore, I32, "restore", (B, N)),
+         _chk(dy, BF16, "dy", (B * (K + 1), D)), _chk(dbias, F32, "dbias", (D,)), _chk(dmask_token, F32, "dmask_token", (D,)),
+         B, N, K, D, *_sum_ws(g.device, B * (N + 1), D), _stream())
+
+
+def mae_loss(pred, target, loss_sum, dpred=None, gscale=0.0, norm_pix=True):
+    """MSE of pred f32 [Mm, Pd] (contiguous or the column prefix of a wider matrix) against target f32 [Mm, Pd] (contiguous);
+    norm_pix: target is first normalised per row, in place ((t - mean) / sqrt(var + 1e-6), unbiased var).  loss_sum f32 [1] += the
+    sum of the row means; dpred bf16 [Mm, Pdp >= Pd] = 2 (pred - t) gscale / Pd, zeros behind column Pd."""
+    if pred is None or pred.dim() != 2:
+        raise L.VitsslError(f"mae_loss: pred must be a matrix, got {None if pred is None else tuple(pred.shape)}")
+    rows, cols = pred.shape
+    pp, ld = _chk_ld(pred, F32, "pred", rows, cols)
+    Pdp = 0
+    if dpred is not None:
+        if dpred.dim() != 2 or dpred.shape[0] != rows or dpred.shape[1] < cols or dpred.shape[1] % 4 != 0:
+            raise L.VitsslError(f"mae_loss: dpred must be [{rows}, Pdp >= {cols}] with Pdp % 4 == 0, got {tuple(dpred.shape)}")
+        Pdp = dpred.shape[1]
+    if norm_pix and cols < 2:
+        raise L.VitsslError("mae_loss: norm_pix needs at least two columns (the unbiased variance of one value is undefined)")
+    call("vitssl_mae_loss", pp, ld, _chk(target, F32, "target", (rows, cols)), _chk(loss_sum, F32, "loss_sum", (1,)),
+         _opt(dpred, BF16, "dpred"), rows, cols, Pdp, int(bool(norm_pix)), float(gscale), *_sum_ws(pred.device, rows, cols), _stream())
+
+
+def _mae_rows(entry, dtype, per, src, idx, out, scatter):
+    if src is None or src.dim() != 2 or out is None or out.dim() != 2 or src.shape[1] != out.shape[1] or out.shape[1] % per != 0:
+        raise L.VitsslError(f"{entry}: src / out must be matrices of one width that is a multiple of {per}, got "
+                            f"{None if src is None else tuple(src.shape)} / {None if out is None else tuple(out.shape)}")
+    rows, cols = out.shape
+    if rows == 0 or (scatter and src.shape[0] == 0):
+        raise L.VitsslError(f"{entry}: empty operand")
+    call("vitssl_" + entry, _chk(src, dtype, "src"), _chk(idx, I32, "inv" if scatter else "idx", (rows,)), _chk(out, dtype, "out"),
+         rows, cols, _stream())
+
+
+def mae_gather_rows_bf16(src, idx, out):
+    """out bf16 [n, cols] = rows idx[i] of src bf16 [*, cols] (cols % 8 == 0)"""
+    _mae_rows("mae_gather_rows_bf16", BF16, 8, src, idx, out, False)
+
+
+def mae_gather_rows_f32(src, idx, out):
+    """out f32 [n, cols] = rows idx[i] of src f32 [*, cols] (cols % 4 == 0)"""
+    _mae_rows("mae_gather_rows_f32", F32, 4, src, idx, out, False)
+
+
+def mae_scatter_rows_f32(src, inv, g):
+    """g f32 [rows, cols]: row r = row inv[r] of src f32 [*, cols] where inv[r] >= 0, else zeros"""
+    _mae_rows("mae_scatter_rows_f32", F32, 4, src, inv, g, True)
