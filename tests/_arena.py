@@ -32,6 +32,7 @@ class Arena:
         self.device = self.buf.device
         self.top = 0            # first byte not yet promised to a tensor or to the guard behind one
         self.regions = []       # (name, start, end, guard) in address order
+        self.dtypes = []        # regions[i]'s element type: what a poison byte there means (NaN as a float, an index as an int)
 
     # ---- carving
     def guard_bytes(self, shape, dtype):
@@ -53,6 +54,7 @@ class Arena:
         if end + g > self.buf.numel():
             raise ArenaError(f"arena of {self.buf.numel()} bytes is too small for {name} {shape} ({end + g} bytes needed)")
         self.regions.append((name, start, end, g))
+        self.dtypes.append(dtype)
         self.top = end + g
         t = self.buf[start:end].view(dtype).view(shape)
         assert t.is_contiguous() and t.data_ptr() % ALIGN == 0

@@ -12,7 +12,9 @@ Per case of CASES, in this order:
      function, and every output and guard byte is still 0xFF (nothing was launched).
 
 The two controls at the end show that the harness can fail.  All their accesses stay inside the arena's one allocation.
-tests/test_abi_arena.py (no GPU) checks that every entry point of the header has a case here."""
+test_abi_case_off_stream runs the same body with a side stream current, behind a gate and through a captured graph
+(tests/_offstream.py).  tests/test_abi_arena.py (no GPU) checks that every entry point of the header has a case here, on the
+default stream and off it."""
 import ctypes as C
 import math
 import zlib
@@ -21,6 +23,7 @@ import pytest
 import torch
 
 from _arena import Arena, ArenaError
+from _offstream import MAX_ARENA_MIB, offstream, twin_of  # noqa: F401  (offstream is a fixture)
 from _util import rel_l2, max_abs
 
 DEV = torch.device("cuda:0")
@@ -1238,6 +1241,18 @@ def test_abi_case(c, reserve):
             torch.cuda.synchronize()
             a.check()
             s.verify()
+
+
+# The same body off the default stream (tests/_offstream.py).  Left out: arenas above MAX_ARENA_MIB (the fixture clones the arena
+# at every call) and the cases that change the reserved CUs; tests/test_abi_arena.py checks that no entry point loses its last case.
+OFF_STREAM_CASES = [c for c in CASES if c.mib <= MAX_ARENA_MIB and not c.reserve]
+
+
+@gpu
+@pytest.mark.parametrize("mode", ["gate", "graph"])
+@pytest.mark.parametrize("c", OFF_STREAM_CASES, ids=lambda c: c.id)
+def test_abi_case_off_stream(c, mode, reserve, offstream):
+    offstream(mode, test_abi_case, c, reserve)
 
 
 # ============================================================================================ controls

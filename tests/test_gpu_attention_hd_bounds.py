@@ -12,6 +12,7 @@ import torch
 
 import _attn_hd as A
 from _arena import Arena
+from _offstream import offstream, twin_of  # noqa: F401  (offstream is a fixture)
 
 DEV = torch.device("cuda:0")
 F32, BF16 = torch.float32, torch.bfloat16
@@ -63,3 +64,9 @@ def test_on_the_arena(dh, N):
     torch.cuda.synchronize()
     a.check()
     assert torch.equal(out.view(torch.int16), out2.view(torch.int16))
+
+
+# ============================================================================================ off the default stream (tests/_offstream.py)
+@twin_of(test_on_the_arena)
+def test_on_the_arena_off_stream(dh, N, mode, offstream):
+    offstream(mode, test_on_the_arena, dh, N)

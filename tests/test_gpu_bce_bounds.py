@@ -12,6 +12,7 @@ import torch
 
 import _bce_ref as Bc
 from _arena import Arena
+from _offstream import offstream, twin_of  # noqa: F401  (offstream is a fixture)
 from test_gpu_bce import check
 
 DEV = torch.device("cuda:0")
@@ -84,3 +85,9 @@ def test_classify_bce_on_the_arena(B, Cn, ld, ld_out, two, grad):
     assert torch.equal(zd.cpu().view(torch.int32), torch.from_numpy(z).view(torch.int32)) and torch.equal(yd.cpu(), torch.from_numpy(y))
     if two:
         assert torch.equal(pd.cpu(), torch.from_numpy(partner)) and torch.equal(ld_.cpu().view(torch.int32), torch.from_numpy(lam).view(torch.int32))
+
+
+# ============================================================================================ off the default stream (tests/_offstream.py)
+@twin_of(test_classify_bce_on_the_arena)
+def test_classify_bce_on_the_arena_off_stream(B, Cn, ld, ld_out, two, grad, mode, offstream):
+    offstream(mode, test_classify_bce_on_the_arena, B, Cn, ld, ld_out, two, grad)

@@ -9,6 +9,7 @@ import torch
 
 import _classify_ref as R
 from _arena import Arena
+from _offstream import offstream, twin_of  # noqa: F401  (offstream is a fixture)
 from test_gpu_classify import check_against
 
 DEV = torch.device("cuda:0")
@@ -60,3 +61,9 @@ def test_classify_loss_on_the_arena(B, Cn, grad):
         assert torch.equal(results[0][k].view(torch.uint8), results[1][k].view(torch.uint8)), f"{k}: bits depend on what the workspace held"
     check_against(R.reference(z, y, Cn, 0.1), results[0], z, y, Cn, 0.1, grad=grad)
     assert torch.equal(zd.cpu().view(torch.int32), torch.from_numpy(z).view(torch.int32)) and torch.equal(yd.cpu(), torch.from_numpy(y))
+
+
+# ============================================================================================ off the default stream (tests/_offstream.py)
+@twin_of(test_classify_loss_on_the_arena)
+def test_classify_loss_on_the_arena_off_stream(B, Cn, grad, mode, offstream):
+    offstream(mode, test_classify_loss_on_the_arena, B, Cn, grad)

@@ -11,6 +11,7 @@ import torch
 
 import _droppath_ref as DP
 from _arena import Arena
+from _offstream import offstream, twin_of  # noqa: F401  (offstream is a fixture)
 
 DEV = torch.device("cuda:0")
 F32, BF16 = torch.float32, torch.bfloat16
@@ -198,3 +199,24 @@ def test_grad_mask_cast_rows_on_the_arena(B, T, cols, p):
     assert float((results[0][0].float() - want).abs().max()) <= 2.0 ** -7 * float(want.abs().max()) + 1e-30
     assert float((results[0][1].double() - want.double().sum(0)).norm()) <= 1e-2 * float(want.double().sum(0).norm()) + 1e-30
     assert same_bits(g, torch.randn(M, cols, generator=torch.Generator().manual_seed(M)))
+
+
+# ============================================================================================ off the default stream (tests/_offstream.py)
+@twin_of(test_table_on_the_arena)
+def test_table_on_the_arena_off_stream(sites, B, mode, offstream):
+    offstream(mode, test_table_on_the_arena, sites, B)
+
+
+@twin_of(test_gemm_rows_on_the_arena)
+def test_gemm_rows_on_the_arena_off_stream(B, T, N, K, p, mode, offstream):
+    offstream(mode, test_gemm_rows_on_the_arena, B, T, N, K, p)
+
+
+@twin_of(test_layernorm_bwd_rows_on_the_arena)
+def test_layernorm_bwd_rows_on_the_arena_off_stream(B, T, cols, p, mode, offstream):
+    offstream(mode, test_layernorm_bwd_rows_on_the_arena, B, T, cols, p)
+
+
+@twin_of(test_grad_mask_cast_rows_on_the_arena)
+def test_grad_mask_cast_rows_on_the_arena_off_stream(B, T, cols, p, mode, offstream):
+    offstream(mode, test_grad_mask_cast_rows_on_the_arena, B, T, cols, p)

@@ -13,6 +13,7 @@ import torch
 import _lamb_ref as R
 import _optim_cases as K
 from _arena import Arena
+from _offstream import offstream, twin_of  # noqa: F401  (offstream is a fixture)
 
 DEV = torch.device("cuda:0")
 F32 = torch.float32
@@ -189,3 +190,9 @@ def test_refusals_launch_nothing():
     launch()                                                   # the unchanged arguments are accepted
     torch.cuda.synchronize()
     assert m[:100].any() and p[:100].any() and not p[100:128].any() and bool((trust != 7.0).all())
+
+
+# ============================================================================================ off the default stream (tests/_offstream.py)
+@twin_of(test_on_the_arena)
+def test_on_the_arena_off_stream(name, mode, offstream):
+    offstream(mode, test_on_the_arena, name)

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from _arena import Arena
+from _offstream import offstream, twin_of  # noqa: F401  (offstream is a fixture)
 from test_gpu_droppath_bounds import P, S, _ln_case, mixed_scales, same_bits
 
 DEV = torch.device("cuda:0")
@@ -168,3 +169,19 @@ def test_grad_mask_cast_ls_on_the_arena(B, T, cols, p, with_rows):
     wls = (rows.double() * g.cpu().double() * br.cpu().double()).sum(0)
     assert float((got[2].double() - wls).norm()) <= 1e-4 * float(wls.norm()) + 1e-30
     assert same_bits(g, torch.randn(M, cols, generator=torch.Generator().manual_seed(M)))
+
+
+# ============================================================================================ off the default stream (tests/_offstream.py)
+@twin_of(test_gemm_ls_on_the_arena)
+def test_gemm_ls_on_the_arena_off_stream(B, T, N, K, p, with_rows, mode, offstream):
+    offstream(mode, test_gemm_ls_on_the_arena, B, T, N, K, p, with_rows)
+
+
+@twin_of(test_layernorm_bwd_ls_on_the_arena)
+def test_layernorm_bwd_ls_on_the_arena_off_stream(B, T, cols, p, with_rows, mode, offstream):
+    offstream(mode, test_layernorm_bwd_ls_on_the_arena, B, T, cols, p, with_rows)
+
+
+@twin_of(test_grad_mask_cast_ls_on_the_arena)
+def test_grad_mask_cast_ls_on_the_arena_off_stream(B, T, cols, p, with_rows, mode, offstream):
+    offstream(mode, test_grad_mask_cast_ls_on_the_arena, B, T, cols, p, with_rows)

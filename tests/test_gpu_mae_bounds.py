@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from _arena import Arena
+from _offstream import offstream, twin_of  # noqa: F401  (offstream is a fixture)
 from vit_core.ssl.mae import masking as Mk
 
 pytestmark = pytest.mark.gpu
@@ -212,3 +213,19 @@ def test_rows_by_index_on_the_arena(B, N, K, D):
     want = torch.zeros(B * (N + 1), D)
     want[m] = tokens.cpu()[m]
     assert torch.equal(back.cpu(), want)
+
+
+# ============================================================================================ off the default stream (tests/_offstream.py)
+@twin_of(test_token_kernels_on_the_arena)
+def test_token_kernels_on_the_arena_off_stream(B, N, K, D, mode, offstream):
+    offstream(mode, test_token_kernels_on_the_arena, B, N, K, D)
+
+
+@twin_of(test_loss_on_the_arena)
+def test_loss_on_the_arena_off_stream(Mm, Pd, ld, Pdp, norm_pix, mode, offstream):
+    offstream(mode, test_loss_on_the_arena, Mm, Pd, ld, Pdp, norm_pix)
+
+
+@twin_of(test_rows_by_index_on_the_arena)
+def test_rows_by_index_on_the_arena_off_stream(B, N, K, D, mode, offstream):
+    offstream(mode, test_rows_by_index_on_the_arena, B, N, K, D)

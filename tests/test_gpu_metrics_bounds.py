@@ -10,6 +10,7 @@ import torch
 
 import _metrics_ref as R
 from _arena import Arena
+from _offstream import offstream, twin_of  # noqa: F401  (offstream is a fixture)
 from test_gpu_metrics import DINO_TOL, RECON_BAR, close, dino_inputs
 
 DEV = torch.device("cuda:0")
@@ -77,3 +78,14 @@ def test_dino_stats_on_the_arena(G, V, B, K):
     for name, tol in DINO_TOL.items():
         assert close(got[name], want[name], tol), name
     assert torch.equal(t.cpu(), teacher) and torch.equal(s.cpu(), student)
+
+
+# ============================================================================================ off the default stream (tests/_offstream.py)
+@twin_of(test_recon_metrics_on_the_arena)
+def test_recon_metrics_on_the_arena_off_stream(Pp, Cc, n, mode, offstream):
+    offstream(mode, test_recon_metrics_on_the_arena, Pp, Cc, n)
+
+
+@twin_of(test_dino_stats_on_the_arena)
+def test_dino_stats_on_the_arena_off_stream(G, V, B, K, mode, offstream):
+    offstream(mode, test_dino_stats_on_the_arena, G, V, B, K)

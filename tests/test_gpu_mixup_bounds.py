@@ -11,6 +11,7 @@ import torch
 
 import _mixup_ref as M
 from _arena import Arena
+from _offstream import offstream, twin_of  # noqa: F401  (offstream is a fixture)
 from test_gpu_classify_mix import check_mix
 from test_gpu_mixup import check
 
@@ -101,3 +102,14 @@ def test_classify_loss_mix_on_the_arena(B, Cn, grad):
     check_mix(ref, results[0], z, y, partner, lam, Cn, 0.1, grad=grad, dbias0=0.0, bad0=0)
     assert torch.equal(zd.cpu().view(torch.int32), torch.from_numpy(z).view(torch.int32)) and torch.equal(yd.cpu(), torch.from_numpy(y))
     assert torch.equal(pd.cpu(), torch.from_numpy(partner)) and torch.equal(ld_.cpu().view(torch.int32), torch.from_numpy(lam).view(torch.int32))
+
+
+# ============================================================================================ off the default stream (tests/_offstream.py)
+@twin_of(test_mix_batch_on_the_arena)
+def test_mix_batch_on_the_arena_off_stream(B, Cn, H, W, mode, offstream):
+    offstream(mode, test_mix_batch_on_the_arena, B, Cn, H, W)
+
+
+@twin_of(test_classify_loss_mix_on_the_arena)
+def test_classify_loss_mix_on_the_arena_off_stream(B, Cn, grad, mode, offstream):
+    offstream(mode, test_classify_loss_mix_on_the_arena, B, Cn, grad)

@@ -387,7 +387,8 @@ def test_edge_batches_against_oracle(B, img, patch, D, H, F, tol):
     # the bf16-emulating oracle with autograd's attention backward, and with the flash-style one of csrc/attention.hip
     # (oracle sdpa(): delta from the bf16 output): within 2e-2 of the nearer, 5e-2 of both, for the same d(loss)/d(pred) (_util.py).
     # The single 4-token image keeps the 5e-2 bar: its smallest gradient (query weights of block 0, |g| 30x below the others)
-    # sits 2-3 % away, varying from run to run with the order of the column-sum atomics.
+    # sits 2-3 % away (measured while the column sums were float atomics; they are slot-row reduces added in a fixed order now,
+    # DESIGN §5, and tests/test_gpu_step_streams.py asserts that fused steps give the same bits run to run).
     dist = {}
     for mode in ("autograd", "flash"):
         leaves = {k: v.clone().requires_grad_(True) for k, v in sd.items()}

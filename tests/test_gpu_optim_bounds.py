@@ -12,6 +12,7 @@ import torch
 
 import _optim_cases as K
 from _arena import Arena
+from _offstream import offstream, twin_of  # noqa: F401  (offstream is a fixture)
 
 DEV = torch.device("cuda:0")
 F32 = torch.float32
@@ -83,3 +84,9 @@ def test_on_the_arena(name):
             pad = torch.zeros(lay.numel - n)
             err = max(float((x.double() - y).abs().max()) for x, y in zip(lay.gather(torch.cat([tc, pad])), r))
             assert err < bar, f"{what}: {err:.3e} from torch float64, bar {bar:.3e}"
+
+
+# ============================================================================================ off the default stream (tests/_offstream.py)
+@twin_of(test_on_the_arena)
+def test_on_the_arena_off_stream(name, mode, offstream):
+    offstream(mode, test_on_the_arena, name)

@@ -12,6 +12,7 @@ import torch
 
 import _patch_cases as PC
 from _arena import Arena
+from _offstream import offstream, twin_of  # noqa: F401  (offstream is a fixture)
 from oracle import vit_oracle as O
 
 DEV = torch.device("cuda:0")
@@ -113,3 +114,19 @@ def test_padded_cast_on_the_arena():
         want, want_t = torch.zeros(d.shape, dtype=BF16), torch.zeros(dt.shape, dtype=BF16)
         want[:R, :Cn], want_t[:Cn, :R] = s.to(BF16), s.t().to(BF16)
         assert torch.equal(PC.bits16(d), PC.bits16(want)) and torch.equal(PC.bits16(dt), PC.bits16(want_t))
+
+
+# ============================================================================================ off the default stream (tests/_offstream.py)
+@twin_of(test_patchify_and_gather_on_the_arena)
+def test_patchify_and_gather_on_the_arena_off_stream(C_, P_, H, W, B, mode, offstream):
+    offstream(mode, test_patchify_and_gather_on_the_arena, C_, P_, H, W, B)
+
+
+@twin_of(test_l1_and_accumulate_on_the_arena)
+def test_l1_and_accumulate_on_the_arena_off_stream(rows, cols, ld_p, ld_d, mode, offstream):
+    offstream(mode, test_l1_and_accumulate_on_the_arena, rows, cols, ld_p, ld_d)
+
+
+@twin_of(test_padded_cast_on_the_arena)
+def test_padded_cast_on_the_arena_off_stream(mode, offstream):
+    offstream(mode, test_padded_cast_on_the_arena)

@@ -16,6 +16,7 @@ import pytest
 import torch
 
 from _arena import Arena
+from _offstream import offstream, twin_of  # noqa: F401  (offstream is a fixture)
 from oracle import augment_oracle as AO
 
 DEV = torch.device("cuda:0")
@@ -123,3 +124,9 @@ def test_transforms_abi_case(c):
     torch.cuda.synchronize()
     a.check()
     assert Arena.untouched(out), "a refused call wrote to its output"
+
+
+# ============================================================================================ off the default stream (tests/_offstream.py)
+@twin_of(test_transforms_abi_case)
+def test_transforms_abi_case_off_stream(c, mode, offstream):
+    offstream(mode, test_transforms_abi_case, c)

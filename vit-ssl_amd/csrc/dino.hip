@@ -429,19 +429,31 @@ __global__ void bicubic_fwd_kernel(const float* __restrict__ src, float* __restr
   }
 }
 
-// dsrc[tap] += wy * wx * ddst (atomics: 16 taps per output token, a few hundred tokens)
+// dsrc[tap] += wy * wx * ddst as a gather: one block per SOURCE token, threads over D.  Every thread walks the output tokens in
+// row-major order and adds the taps that land on its source token in tap order (border clamping can put several taps of one
+// output token on it), then adds the sum to dsrc once: one fixed order of additions, the same bits in every run.  A few hundred
+// tokens times D: the walk costs nothing that shows in a step.
 __global__ void bicubic_bwd_kernel(const float* __restrict__ ddst, float* __restrict__ dsrc, int gh0, int gw0, int gh, int gw, int D) {
-  const int y = blockIdx.x / gw, x = blockIdx.x - y * gw;
-  int iy[4], ix[4];
-  float cy[4], cx[4];
-  cubic_site(y, gh0, gh, iy, cy);
-  cubic_site(x, gw0, gw, ix, cx);
+  const int sy = blockIdx.x / gw0, sx = blockIdx.x - sy * gw0;
   for (int d = threadIdx.x; d < D; d += blockDim.x) {
-    const float g = ddst[(long long)blockIdx.x * D + d];
+    float acc = 0.f;
+    for (int y = 0; y < gh; ++y) {
+      int iy[4], ix[4];
+      float cy[4], cx[4];
+      cubic_site(y, gh0, gh, iy, cy);
+      if (iy[0] != sy && iy[1] != sy && iy[2] != sy && iy[3] != sy) continue;
+      for (int x = 0; x < gw; ++x) {
+        cubic_site(x, gw0, gw, ix, cx);
+        if (ix[0] != sx && ix[1] != sx && ix[2] != sx && ix[3] != sx) continue;
+        const float g = ddst[((long long)y * gw + x) * D + d];
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
+        for (int i = 0; i < 4; ++i)
 #pragma unroll
-      for (int j = 0; j < 4; ++j) atomicAdd(dsrc + ((long long)iy[i] * gw0 + ix[j]) * D + d, g * cy[i] * cx[j]);
+          for (int j = 0; j < 4; ++j)
+            if (iy[i] == sy && ix[j] == sx) acc += g * cy[i] * cx[j];
+      }
+    }
+    dsrc[(long long)blockIdx.x * D + d] += acc;
   }
 }
 
@@ -555,7 +567,7 @@ extern "C" int vitssl_bicubic_resize_fwd(const float* src, float* dst, int gh0, 
 
 extern "C" int vitssl_bicubic_resize_bwd(const float* ddst, float* dsrc, int gh0, int gw0, int gh, int gw, int D, void* stream) {
   VS_CHECK_ARG(ddst && dsrc && gh0 > 0 && gw0 > 0 && gh > 0 && gw > 0 && D > 0, "bicubic_resize_bwd: bad args");
-  hipLaunchKernelGGL(bicubic_bwd_kernel, dim3(gh * gw), dim3(256), 0, (hipStream_t)stream, ddst, dsrc, gh0, gw0, gh, gw, D);
+  hipLaunchKernelGGL(bicubic_bwd_kernel, dim3(gh0 * gw0), dim3(256), 0, (hipStream_t)stream, ddst, dsrc, gh0, gw0, gh, gw, D);
   VS_CHECK_LAUNCH("bicubic_resize_bwd");
   return VITSSL_OK;
 }
