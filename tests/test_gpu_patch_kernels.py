@@ -109,42 +109,58 @@ def test_padded_cast_plan_keeps_the_pad_at_zero():
         w.mul_(1.5)
 
 
-@pytest.mark.parametrize("C,P,H,W", [(3, 4, 16, 16), (3, 5, 15, 15), (3, 14, 42, 42)], ids=str)
-def test_padded_gemm_chain_is_exact(C, P, H, W):
-    """Patch projection forward, its weight gradient, head forward, head input gradient and head weight / bias gradients at
-    Pd = 48, 75, 588 through the SimMIM runtime's own buffers, every workspace poisoned beforehand, on integer operands:
-    all elements as bits against the integer reference."""
-    from vit_core.ssl.simmim import SimMIMViT
-    from vitssl_hip import _lib as L, ops
+def _chain_runtime(kind, C, P, H, W, D):
+    """-> (model, its runtime, the head's nn.Linear, its name in the store): one block per stack, D = Dd"""
+    if kind == "simmim":
+        from vit_core.ssl.simmim import SimMIMViT
+        model = SimMIMViT(num_blocks=1, input_shape=(C, H, W), embed_dim=D, patch_size=P, num_heads=1, mlp_dim=64, dropout=0.0).to(DEV)
+        return model, model.runtime(DEV), model.simmim_head, "simmim_head"
+    from vit_core.ssl.mae import MAEViT
+    model = MAEViT(num_blocks=1, input_shape=(C, H, W), embed_dim=D, patch_size=P, num_heads=1, mlp_dim=64, decoder_embed_dim=D,
+                   decoder_blocks=1, decoder_heads=1, decoder_mlp_dim=64).to(DEV)
+    return model, model.runtime(DEV), model.decoder_pred, "decoder_pred"
+
+
+@pytest.mark.parametrize("C,P,H,W", [(3, 4, 16, 16), (3, 5, 15, 15), (3, 14, 42, 42), (3, 8, 16, 16)], ids=str)
+@pytest.mark.parametrize("kind", ["simmim", "mae"])
+def test_padded_gemm_chain_is_exact(kind, C, P, H, W):
+    """Patch projection forward (SimMIM's embed; MAE embeds gathered rows, tests/test_gpu_mae_models.py), its weight gradient, and
+    the three methods of the runtime's own engine.PatchHead -- forward, input gradient, weight / bias gradients -- at Pd = 48
+    (Np = Pd, Pdp 64), 75 (Np = Pdp = 128), 588 (Np = Pd, Pdp 640) and the native 192, every workspace poisoned beforehand, on
+    integer operands: all elements as bits against the integer reference, pad columns and rows exactly zero."""
     B, D = 2, 64
     Pd, N = C * P * P, (H // P) * (W // P)
-    model = SimMIMViT(num_blocks=1, input_shape=(C, H, W), embed_dim=D, patch_size=P, num_heads=1, mlp_dim=64, dropout=0.0).to(DEV)
-    rt = model.runtime(DEV)
-    st, geo = rt.store, rt.geo
-    assert not geo.native and rt.Pdp == PC.padded(Pd)
+    model, rt, head, hname = _chain_runtime(kind, C, P, H, W, D)
+    st, geo, key = rt.store, rt.geo, rt.head.key
+    assert rt.Pdp == PC.padded(Pd) and (rt.Pdp != Pd or (C, P) == (3, 8))
     with torch.no_grad():
         model.projection.weight.copy_(X.int_values((D, Pd), -2, 2, 1))
         model.projection.bias.copy_(X.int_values((D,), -3, 3, 2))
-        model.simmim_head.weight.copy_(X.int_values((Pd, D), -2, 2, 3))
-        model.simmim_head.bias.copy_(X.int_values((Pd,), -3, 3, 4))
-        model.positional_embedding.copy_(X.int_values((1, N, D), -4, 4, 5))
+        head.weight.copy_(X.int_values((Pd, D), -2, 2, 3))
+        head.bias.copy_(X.int_values((Pd,), -3, 3, 4))
+        if kind == "simmim":
+            model.positional_embedding.copy_(X.int_values((1, N, D), -4, 4, 5))
     x = X.int_values((B, C, H, W), -3, 3, 6)
     M = B * N
     st.refresh_weights()
-    for key in ("proj", "head", "head.T"):                       # the images: pad zero, body the integers
-        img = st.w(key).cpu().float()
-        src = {"proj": model.projection.weight, "head": model.simmim_head.weight, "head.T": model.simmim_head.weight.t()}[key].detach().cpu()
+    for k in ("proj", key, key + ".T"):                          # the images: pad zero, body the integers
+        img = st.w(k).cpu().float()
+        src = {"proj": model.projection.weight, key: head.weight, key + ".T": head.weight.t()}[k].detach().cpu()
         want = torch.zeros_like(img)
         want[:src.shape[0], :src.shape[1]] = src
-        assert torch.equal(img, want), key
+        assert torch.equal(img, want), k
     # --- forward of the projection, on poisoned workspaces
     for name, shape, dt in (("patches", (M, rt.Pdp), BF16), ("x0", (M, D), F32)):
         rt.ws.get(name, shape, dt, DEV).view(torch.int16 if dt == BF16 else torch.int32).fill_(-1)
-    x0, patches = rt.embed(x.to(DEV), None)
     pm = O.patchify(x, P).reshape(M, Pd)
-    want_x0 = pm.double() @ model.projection.weight.detach().cpu().double().t() + model.projection.bias.detach().cpu().double() \
-        + model.positional_embedding.detach().cpu().double()[0].repeat(B, 1)
-    X.check_exact(x0, X.to_f32_exact(want_x0), "projection forward")
+    if kind == "simmim":
+        x0, patches = rt.embed(x.to(DEV), None)
+        want_x0 = pm.double() @ model.projection.weight.detach().cpu().double().t() + model.projection.bias.detach().cpu().double() \
+            + model.positional_embedding.detach().cpu().double()[0].repeat(B, 1)
+        X.check_exact(x0, X.to_f32_exact(want_x0), "projection forward")
+    else:
+        patches = rt.ws.get("patches", (M, rt.Pdp), BF16, DEV)
+        geo.patchify(x.to(DEV), patches)
     # --- weight gradient of the projection
     dproj = X.int_values((M, D), -3, 3, 7).to(BF16)
     gw = st.gview("projection.weight", (D, Pd))
@@ -152,36 +168,46 @@ def test_padded_gemm_chain_is_exact(C, P, H, W):
     rt.ws.get("pad.proj_wgrad", (D, rt.Pdp), F32, DEV).fill_(float("nan"))
     geo.proj_wgrad(dproj.to(DEV), patches, gw, rt.ws)
     X.check_exact(gw, X.to_f32_exact(X.int_values((D, Pd), -5, 5, 8).double() + dproj.double().t() @ pm.double()), "projection wgrad")
-    # --- head forward / backward through runtime.forward's tail and runtime.backward's head
+    # --- the head: the methods runtime.forward and runtime.backward call, on poisoned workspaces
     Mm = 5
+    pads = {n: rt.ws.get(f"pad.{key}_{n}", shape, F32, DEV) for n, shape in (("bias", (rt.Np,)), ("bgrad", (1, rt.Pdp)), ("wgrad", (rt.Pdp, D)))}
     sel = X.int_values((Mm, D), -2, 2, 9).to(BF16)
-    hw, hb = model.simmim_head.weight.detach().cpu().double(), model.simmim_head.bias.detach().cpu().double()
-    if rt.Np == Pd:
-        pred = torch.full((Mm, Pd), float("nan"), device=DEV)
-        ops.gemm_nt(sel.to(DEV), st.w("head")[:Pd], pred, L.EPI_F32, bias=st.view("simmim_head.bias"))
-    else:
-        bias = torch.zeros(rt.Np, device=DEV)
-        bias[:Pd] = st.view("simmim_head.bias")
-        wide = torch.full((Mm, rt.Np), float("nan"), device=DEV)
-        ops.gemm_nt(sel.to(DEV), st.w("head"), wide, L.EPI_F32, bias=bias)
-        assert float(wide[:, Pd:].abs().max()) == 0.0, "pad columns of the prediction"
-        pred = wide[:, :Pd]
+    hw, hb = head.weight.detach().cpu().double(), head.bias.detach().cpu().double()
+    pads["bias"].fill_(float("nan"))
+    pred = rt.head.forward(sel.to(DEV))
+    assert pred.shape == (Mm, Pd) and pred.dtype == F32
+    if rt.Np != Pd:
+        assert pred._base.shape == (Mm, rt.Np) and float(pred._base[:, Pd:].abs().max()) == 0.0, "pad columns of the prediction"
     X.check_exact(pred.contiguous(), X.to_f32_exact(sel.double() @ hw.t() + hb), "head forward")
     dpred = torch.zeros(Mm, rt.Pdp, dtype=BF16)
     dpred[:, :Pd] = X.int_values((Mm, Pd), -2, 2, 10).to(BF16)
     dsel = torch.empty(Mm, D, dtype=BF16, device=DEV)
-    ops.gemm_nt(dpred.to(DEV), st.w("head.T"), dsel, L.EPI_BF16)
+    dsel.view(torch.int16).fill_(NAN_BF16)
+    rt.head.dgrad(dpred.to(DEV), dsel)
     X.check_exact(dsel, X.bf16_rne(dpred[:, :Pd].double() @ hw), "head input gradient")
-    # weight and bias gradient of the head exactly as runtime.backward forms them
     st.gflat.zero_()
-    for name, shape in (("pad.head_bgrad", (1, rt.Pdp)), ("pad.head_wgrad", (rt.Pdp, D))):
-        rt.ws.get(name, shape, F32, DEV).fill_(float("nan"))
-    hbg, hwg = rt.ws.get("pad.head_bgrad", (1, rt.Pdp), F32, DEV), rt.ws.get("pad.head_wgrad", (rt.Pdp, D), F32, DEV)
-    hbg.zero_(); hwg.zero_()
-    ops.colsum_bf16(dpred.to(DEV), hbg.view(rt.Pdp))
-    ops.gemm_tn(dpred.to(DEV), sel.to(DEV), hwg)
-    ops.accumulate_ld_f32(st.gview("simmim_head.bias", (1, Pd)), hbg)
-    ops.accumulate_ld_f32(st.gview("simmim_head.weight", (Pd, D)), hwg[:Pd])
-    X.check_exact(st.gview("simmim_head.weight", (Pd, D)), X.to_f32_exact(dpred[:, :Pd].double().t() @ sel.double()), "head wgrad")
-    X.check_exact(st.gview("simmim_head.bias", (1, Pd)), X.to_f32_exact(dpred[:, :Pd].double().sum(0, keepdim=True)), "head bias grad")
-    assert float(hwg[Pd:].abs().max()) == 0.0 and float(hbg[:, Pd:].abs().max()) == 0.0
+    pads["bgrad"].fill_(float("nan"))
+    pads["wgrad"].fill_(float("nan"))
+    rt.head.wgrad(dpred.to(DEV), sel.to(DEV))
+    X.check_exact(st.gview(hname + ".weight", (Pd, D)), X.to_f32_exact(dpred[:, :Pd].double().t() @ sel.double()), "head wgrad")
+    X.check_exact(st.gview(hname + ".bias", (1, Pd)), X.to_f32_exact(dpred[:, :Pd].double().sum(0, keepdim=True)), "head bias grad")
+    if rt.Pdp != Pd:
+        assert float(pads["wgrad"][Pd:].abs().max()) == 0.0 and float(pads["bgrad"][:, Pd:].abs().max()) == 0.0
+
+
+
+def test_widen_grad():
+    """PatchGeometry.widen_grad, the autograd bridges' way into the engine's backward: bf16 at the width Pdp, the body the
+    round-to-nearest image of the gradient, the pad columns +0; an empty gradient stays empty."""
+    from vitssl_hip.engine import PatchGeometry
+    for C, P in ((3, 5), (3, 8)):                                 # Pd 75 -> Pdp 128; the native 192
+        geo = PatchGeometry(C, P)
+        Pd, Pdp = geo.Pd, PC.padded(geo.Pd)
+        empty = geo.widen_grad(torch.empty(0, Pd, device=DEV))
+        assert empty.shape == (0, Pdp) and empty.dtype == BF16 and empty.device.type == "cuda"
+        x = torch.randn(7, Pd, generator=torch.Generator().manual_seed(P))
+        for src in (x, x.double(), x.t().contiguous().t()):       # f32, another dtype, not contiguous
+            got = geo.widen_grad(src.to(DEV))
+            assert got.shape == (7, Pdp) and got.dtype == BF16 and got.is_contiguous()
+            assert torch.equal(PC.bits16(got[:, :Pd]), PC.bits16(x.to(BF16))), "body"
+            assert Pdp == Pd or int(PC.bits16(got[:, Pd:]).abs().max()) == 0, "pad columns must be +0"

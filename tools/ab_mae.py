@@ -7,7 +7,7 @@
      step of the same encoder (ViT-B/16, batch 256, 224 x 224, mask ratio 0.6), alternating in one process.  By flop count the
      MAE step is about 0.55-0.6 of the SimMIM step.
 Every figure is the median over ROUNDS rounds of the mean of N back-to-back calls between two HIP events; the variants alternate
-inside a round.  Developer tool:  python tools/ab_mae.py [--out profiles/mae_ab.txt] [--skip-step]"""
+inside a round.  Developer tool:  python tools/ab_mae.py [--out profiles/mae_ab.txt] [--skip-step] [--skip-kernels]"""
 import argparse
 import contextlib
 import io
@@ -134,6 +134,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--skip-step", action="store_true", help="leave out the two ViT-B/16 steps")
+    ap.add_argument("--skip-kernels", action="store_true", help="leave out the copy-rate probe and the kernel table")
     args = ap.parse_args()
     lines = []
 
@@ -142,24 +143,25 @@ def main():
         lines.append(s)
 
     say(f"tools/ab_mae.py on {torch.cuda.get_device_name(0)}: median of {ROUNDS} rounds x N calls, variants alternating")
-    text, copy_rate = probe_copy_rate()
-    say()
-    say("0. tools/hbm_probe.py in this process")
-    for ln in text.strip().splitlines():
-        say("   " + ln)
-    say(f"   the yardstick below: the fp32 copy at 616 MB, {copy_rate:.2f} TB/s (read + write)")
+    if not args.skip_kernels:
+        text, copy_rate = probe_copy_rate()
+        say()
+        say("0. tools/hbm_probe.py in this process")
+        for ln in text.strip().splitlines():
+            say("   " + ln)
+        say(f"   the yardstick below: the fp32 copy at 616 MB, {copy_rate:.2f} TB/s (read + write)")
 
-    say()
-    say(f"1. kernels of include_ext/vitssl_mae.h at B = {B}, N = {N}, K = {K}, D = {D}, Dd = {DD}, Pd = {PD} "
-        f"(buffer sets rotate over more than {FOOTPRINT / 1e6:.0f} MB)")
-    ks = kernels()
-    med, spread = interleaved({k: fn for k, (fn, _) in ks.items()}, n=24)
-    for k, (_, nbytes) in ks.items():
-        rate = nbytes / (med[k] * 1e-6) / 1e12
-        say(f"   {k:24s} {med[k]:8.1f} us  [{spread[k][0]:.1f} .. {spread[k][1]:.1f}]   {nbytes / 1e6:7.1f} MB   {rate:5.2f} TB/s   "
-            f"{rate / copy_rate:5.2f} of the copy rate")
-    del ks
-    torch.cuda.empty_cache()
+        say()
+        say(f"1. kernels of include_ext/vitssl_mae.h at B = {B}, N = {N}, K = {K}, D = {D}, Dd = {DD}, Pd = {PD} "
+            f"(buffer sets rotate over more than {FOOTPRINT / 1e6:.0f} MB)")
+        ks = kernels()
+        med, spread = interleaved({k: fn for k, (fn, _) in ks.items()}, n=24)
+        for k, (_, nbytes) in ks.items():
+            rate = nbytes / (med[k] * 1e-6) / 1e12
+            say(f"   {k:24s} {med[k]:8.1f} us  [{spread[k][0]:.1f} .. {spread[k][1]:.1f}]   {nbytes / 1e6:7.1f} MB   {rate:5.2f} TB/s   "
+                f"{rate / copy_rate:5.2f} of the copy rate")
+        del ks
+        torch.cuda.empty_cache()
 
     if not args.skip_step:
         from vit_core.ssl.mae import MAEViT

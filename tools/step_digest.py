@@ -2,7 +2,10 @@
 """sha256 of the losses and of the flat parameter buffer after 4 seeded steps of tiny models, with the losses themselves to 9
 digits, one line per case: the three fused train_steps (ViT in its three backward schedules) and ViT through autograd, then
 SimMIM again with drop path, with LayerScale, with both, and with fp8 linear operands (the other forms of the LayerNorm
-backward launch).  Two commits that print the same lines compute the same thing bit for bit (dropout 0.1 included: its seeds
+backward launch), then the masked-image models' patch path: MAE fused and through autograd (nn.MSELoss, FusedAdamW.step, a
+fixed keep table), SimMIM through autograd (nn.L1Loss), both again at patch 5 on 30x30 (Pd = 75: projection, head and the
+gradient of the prediction run at the padded width 128) and SimMIM at patch 4 (Pd = 48: padded to 64 except for the head's
+output).  Two commits that print the same lines compute the same thing bit for bit (dropout 0.1 included: its seeds
 come from torch.manual_seed).
 
 usage: python tools/step_digest.py"""
@@ -36,18 +39,46 @@ def images(n, size, seed):
     return torch.rand(n, 3, size, size, generator=torch.Generator().manual_seed(seed)).to(DEV)
 
 
-def simmim(name="simmim", operands="bf16", **extra):
+def autograd_steps(m, opt, x, criterion, **fwd):
+    losses = []
+    for _ in range(STEPS):
+        opt.zero_grad(set_to_none=True)
+        losses.append(criterion(*m(x, **fwd)))
+        losses[-1].backward()
+        opt.step()
+    return losses
+
+
+def simmim(name="simmim", operands="bf16", autograd=False, **extra):
     from vit_core.ssl.simmim.model import SimMIMViT
     from vitssl_hip.engine import set_linear_operands
     from vitssl_hip.optim import FusedAdamW
     torch.manual_seed(1)
     set_linear_operands(operands)          # read when the model's encoder stack is built
     try:
-        m = SimMIMViT(**TINY, **extra).to(DEV).train()
-        opt, x = FusedAdamW(m.flat_store(), lr=1e-3, weight_decay=1e-2), images(8, 32, 2)
-        report(name, [m.train_step(x, opt) for _ in range(STEPS)], m.flat_store())
+        cfg = dict(TINY, **extra)
+        m = SimMIMViT(**cfg).to(DEV).train()
+        opt, x = FusedAdamW(m.flat_store(), lr=1e-3, weight_decay=1e-2), images(8, cfg["input_shape"][1], 2)
+        losses = autograd_steps(m, opt, x, nn.L1Loss()) if autograd else [m.train_step(x, opt) for _ in range(STEPS)]
+        report(name, losses, m.flat_store())
     finally:
         set_linear_operands("bf16")
+
+
+def mae(name="mae", autograd=False, **extra):
+    from vit_core.ssl.mae import MAEViT
+    from vit_core.ssl.mae.masking import draw_keep
+    from vitssl_hip.optim import FusedAdamW
+    torch.manual_seed(5)
+    cfg = dict(TINY, dropout=0.0, decoder_embed_dim=64, decoder_blocks=1, decoder_heads=2, **extra)
+    m = MAEViT(**cfg).to(DEV).train()
+    opt, x = FusedAdamW(m.flat_store(), lr=1e-3, weight_decay=1e-2), images(8, cfg["input_shape"][1], 6)
+    if autograd:
+        keep, _ = draw_keep(8, m.num_patches, m.num_kept, generator=torch.Generator().manual_seed(7))
+        losses = autograd_steps(m, opt, x, nn.MSELoss(), keep_cpu=keep)
+    else:
+        losses = [m.train_step(x, opt) for _ in range(STEPS)]
+    report(name, losses, m.flat_store())
 
 
 def dino():
@@ -98,3 +129,11 @@ if __name__ == "__main__":
     simmim("simmim layerscale", layer_scale_init=1e-5)
     simmim("simmim dp+ls", drop_path_rate=0.1, layer_scale_init=1e-5)
     simmim("simmim fp8", operands="fp8")
+    pad = dict(input_shape=(3, 30, 30), patch_size=5)
+    for case, kw in (("", {}), (" P=5", pad)):
+        mae("mae" + case, **kw)
+        mae("mae autograd" + case, autograd=True, **kw)
+    simmim("simmim autograd", autograd=True)
+    simmim("simmim P=5", **pad)
+    simmim("simmim autograd P=5", autograd=True, **pad)
+    simmim("simmim P=4", patch_size=4)

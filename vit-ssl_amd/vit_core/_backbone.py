@@ -22,11 +22,7 @@ class BackboneRuntime:
         blocks = [f"{prefix}encoder_blocks.{i}." for i in range(num_blocks)]
         self.stack = R.EncoderStack(store, blocks, D, H, Fd, p_drop, site_base=site_base, drop_path=drop_path, layer_scale=layer_scale)
         self.wkey = prefix + "patch_proj"
-        if self.geo.native:
-            store.register_weight(self.wkey, lambda: store.view(embed_names["weight"], (D, self.Pd)), transposed_too=False)
-        else:     # the projection image carries zero pad columns
-            store.register_padded_weight(self.wkey, lambda: store.view(embed_names["weight"], (D, self.Pd)), D, self.Pdp,
-                                         transposed_too=False)
+        self.geo.register_proj(store, self.wkey, lambda: store.view(embed_names["weight"], (D, self.Pd)), D)
         self.ws = R.Workspace()
         self.rec = {}
 

@@ -444,11 +444,7 @@ class _PatchEmbedFn(Function):
             raise L.VitsslError(f"patch embedding: weight has {Pd} input features, a {Cc}-channel patch of side {P} has {geo.Pd}")
         patches = _empty((Bn * tokens, geo.Pdp), BF16, img)
         geo.patchify(img, patches)
-        if geo.native:
-            wb, _ = weight_bf16(w, want_t=False)
-        else:     # zero pad columns in the weight image, as in the patches
-            wb = torch.zeros(D, geo.Pdp, dtype=BF16, device=img.device)
-            ops.CastPlanLd().run([(R.as_f32(w.detach()), wb, None)])
+        wb = geo.proj_image(R.as_f32(w.detach()))      # zero pad columns, as in the patches
         out = _empty((Bn * T, D), F32, img)
         posf = R.as_f32(pos.detach())
         ops.gemm_nt(patches, wb, out, L.EPI_EMBED, bias=R.as_f32(b.detach()), embed=(None, None, posf, tokens, T, 1))

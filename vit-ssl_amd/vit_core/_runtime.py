@@ -12,7 +12,8 @@ if _PKG not in sys.path:
 
 from vitssl_hip import _lib as L  # noqa: E402
 from vitssl_hip import ops  # noqa: E402
-from vitssl_hip.engine import EncoderStack, FlatStore, GradReducer, PatchGeometry, Workspace, _round_up, drop_path_rates  # noqa: E402,F401
+from vitssl_hip.engine import (EncoderStack, FlatStore, GradReducer, HostStage, PatchGeometry, PatchHead, Workspace, _round_up,  # noqa: E402,F401
+                               as_f32, drop_path_rates)
 
 BF16 = torch.bfloat16
 F32 = torch.float32
@@ -62,12 +63,6 @@ def model_runtime(model, who: str, cls, anchor: torch.Tensor, device=None):
         L.lib()
         object.__setattr__(model, "_rt", cls(model, device))
     return model._rt
-
-
-def as_f32(x: torch.Tensor) -> torch.Tensor:
-    if x.dtype != F32:
-        x = x.float()
-    return x.contiguous()
 
 
 def limit_host_threads(n=None):

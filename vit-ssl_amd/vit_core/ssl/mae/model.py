@@ -26,8 +26,6 @@ from ..._runtime import BF16, F32, L, ops
 from ...encoder_block import EncoderBlock
 from .masking import MAEIndices, bool_mask, draw_keep, num_kept, restore_from_keep
 
-I32 = torch.int32
-
 
 def sincos_1d(dim: int, pos: np.ndarray) -> np.ndarray:
     """[len(pos), dim]: sin then cos of pos / 10000^(2 i / dim), i < dim / 2 (fp64)"""
@@ -78,16 +76,12 @@ class _MAERuntime:
         self.dec = R.EncoderStack(st, [f"decoder_blocks.{i}." for i in range(len(model.decoder_blocks))], Dd, model.decoder_heads,
                                   model.decoder_mlp_dim, 0.0, site_base=3 * len(model.encoder_blocks))
         st.register_weight("dembed", lambda: st.view("decoder_embed.weight", (Dd, D)))
-        if self.geo.native:
-            st.register_weight("proj", lambda: st.view("projection.weight", (D, self.Pd)), transposed_too=False)
-            st.register_weight("dpred", lambda: st.view("decoder_pred.weight", (self.Pd, Dd)))
-        else:     # zero pad columns in the projection image, zero pad rows / columns in the head image and its transpose
-            st.register_padded_weight("proj", lambda: st.view("projection.weight", (D, self.Pd)), D, self.Pdp, transposed_too=False)
-            st.register_padded_weight("dpred", lambda: st.view("decoder_pred.weight", (self.Pd, Dd)), self.Pdp, Dd)
         self.ws = R.Workspace()
+        self.geo.register_proj(st, "proj", lambda: st.view("projection.weight", (D, self.Pd)), D)
+        self.head = R.PatchHead(st, self.geo, "dpred", "decoder_pred.weight", "decoder_pred.bias", Dd, self.ws)
+        self.stage = R.HostStage()
         self.rec = None
         self.save_gen = 0      # id of the forward whose activations `rec` / the stacks hold
-        self._stage_key = None
 
     def valid_for(self, device) -> bool:
         return device == self.device and self.store.is_attached()
@@ -103,35 +97,12 @@ class _MAERuntime:
 
     # ------------------------------------------------------------------ index tables
     def prepare(self, keep_cpu, restore_cpu, dev):
-        """Host tables -> dict of int32 device views (MAEIndices.NAMES) plus B, Mm.  All six tables travel as ONE copy from a
-        ring of persistent pinned buffers (as SimMIMViT.prepare_mask: a slot is reused only after the event behind its last
-        copy has completed)."""
+        """Host tables -> dict of int32 device views (MAEIndices.NAMES) plus B, Mm, staged as one copy through the runtime's ring
+        of pinned buffers (engine.HostStage: they stay valid until the fourth later call)."""
         idx = MAEIndices(keep_cpu, restore_cpu, self.K)
         if idx.N != self.N:
             raise L.VitsslError(f"MAEViT: index tables are for {idx.N} patches, the model has {self.N}")
-        tables = idx.tables()
-        offs, total = [], 0
-        for t in tables:
-            offs.append(total)
-            total = R._round_up(total + t.size, 64)
-        key = (idx.B, str(dev))
-        if self._stage_key != key:
-            self._stage = [dict(host=torch.empty(total, dtype=I32).pin_memory(), dev=torch.empty(total, dtype=I32, device=dev), ev=None)
-                           for _ in range(4)]
-            self._stage_pos, self._stage_key = 0, key
-        slot = self._stage[self._stage_pos % len(self._stage)]
-        self._stage_pos += 1
-        if slot["ev"] is not None:
-            slot["ev"].synchronize()
-        host = slot["host"].numpy()
-        for o, t in zip(offs, tables):
-            host[o:o + t.size] = t          # plain memcpy into the pinned pages (no torch CPU op)
-        slot["dev"].copy_(slot["host"], non_blocking=True)
-        slot["ev"] = torch.cuda.Event()
-        slot["ev"].record(torch.cuda.current_stream())
-        out = {n: slot["dev"][o:o + t.size] for n, o, t in zip(idx.NAMES, offs, tables)}
-        out.update(B=idx.B, Mm=idx.Mm)
-        return out
+        return dict(zip(idx.NAMES, self.stage.upload(idx.tables(), dev)), B=idx.B, Mm=idx.Mm)
 
     # ------------------------------------------------------------------ forward
     def forward(self, x, save: bool, keep_cpu=None, prepared=None, training: bool = True):
@@ -159,7 +130,7 @@ class _MAERuntime:
         g = lambda name, shape, dtype: ws.get(tag + name, shape, dtype, dev)      # noqa: E731
 
         targets = torch.empty(Mm, self.Pd, dtype=F32, device=dev)
-        (ops.gather_patches_f32 if self.geo.native else ops.gather_patches_any_f32)(x, p["midx"], targets, self.P)
+        self.geo.gather_targets(x, p["midx"], targets)
         # encoder on the visible patches
         patches = g("patches", (B * N, self.Pdp), BF16)
         self.geo.patchify(x, patches)
@@ -185,18 +156,7 @@ class _MAERuntime:
         hs = g("hs", (Mm, Dd), BF16)
         smean, srstd = g("smean", (Mm,), F32), g("srstd", (Mm,), F32)
         ops.layernorm_fwd(xs, st.view("decoder_norm.weight"), st.view("decoder_norm.bias"), hs, smean, srstd)
-        if self.Np == self.Pd:
-            pred = torch.empty(Mm, self.Pd, dtype=F32, device=dev)
-            ops.gemm_nt(hs, st.w("dpred")[:self.Pd], pred, L.EPI_F32, bias=st.view("decoder_pred.bias"))
-        else:
-            # Pd % 4 != 0: the head GEMM writes the padded width (zero weight rows and zero bias give zero pad columns); the
-            # public prediction is the column prefix of that buffer
-            bias = ws.get("pad.pred_bias", (self.Np,), F32, dev)
-            bias.zero_()
-            bias[:self.Pd].copy_(st.view("decoder_pred.bias"))
-            wide = torch.empty(Mm, self.Np, dtype=F32, device=dev)
-            ops.gemm_nt(hs, st.w("dpred"), wide, L.EPI_F32, bias=bias)
-            pred = wide[:, :self.Pd]
+        pred = self.head.forward(hs)
         if save:
             self.save_gen += 1
             self.rec = dict(B=B, Mm=Mm, p=p, kept=kept, xL=xL, h=h, mean=mean, rstd=rstd, xs=xs, hs=hs, smean=smean, srstd=srstd)
@@ -233,21 +193,10 @@ class _MAERuntime:
         gv = st.gview
         ready = (lambda *names: reducer.ready(*st.span(names[0], names[-1]))) if reducer is not None else (lambda *names: None)
         # prediction head
-        if self.geo.native:
-            ops.colsum_bf16(dpred_bf16, gv("decoder_pred.bias"))
-            ops.gemm_tn(dpred_bf16, rec["hs"], gv("decoder_pred.weight", (self.Pd, Dd)))
-        else:     # bias and weight gradients at the padded width, then their first Pd entries / rows into the flat buffer
-            hb = ws.get("pad.pred_bgrad", (1, self.Pdp), F32, dev)
-            hw = ws.get("pad.pred_wgrad", (self.Pdp, Dd), F32, dev)
-            hb.zero_()
-            hw.zero_()
-            ops.colsum_bf16(dpred_bf16, hb.view(self.Pdp))
-            ops.gemm_tn(dpred_bf16, rec["hs"], hw)
-            ops.accumulate_ld_f32(gv("decoder_pred.bias", (1, self.Pd)), hb)
-            ops.accumulate_ld_f32(gv("decoder_pred.weight", (self.Pd, Dd)), hw[:self.Pd])
+        self.head.wgrad(dpred_bf16, rec["hs"])
         ready("decoder_pred.weight", "decoder_pred.bias")
         dhs = ws.get("dhs", (Mm, Dd), BF16, dev)
-        ops.gemm_nt(dpred_bf16, st.w("dpred.T"), dhs, L.EPI_BF16)
+        self.head.dgrad(dpred_bf16, dhs)
         gxs = ws.get("gxs", (Mm, Dd), F32, dev)
         ops.layernorm_bwd(dhs, rec["xs"], rec["smean"], rec["srstd"], st.view("decoder_norm.weight"), None, gxs, None,
                           gv("decoder_norm.weight"), gv("decoder_norm.bias"))
@@ -294,18 +243,8 @@ class _MAEFn(Function):
     @staticmethod
     def backward(ctx, dpred, _dt, _dm):
         rt = ctx.rt
-
-        def run():
-            dp = R.as_f32(dpred)
-            dpb = torch.empty(dp.shape, dtype=BF16, device=dp.device)
-            ops.cast_bf16(dp, dpb)
-            if rt.Pdp != rt.Pd:      # the engine's backward reads the padded width
-                wide = torch.zeros(dp.shape[0], rt.Pdp, dtype=BF16, device=dp.device)
-                wide[:, :rt.Pd] = dpb
-                dpb = wide
-            rt.backward(dpb)
-
-        return (None, None, None, None, None, *R.backward_grads("MAEViT", ctx.gen, rt.save_gen, rt.store, run))
+        return (None, None, None, None, None, *R.backward_grads("MAEViT", ctx.gen, rt.save_gen, rt.store,
+                                                                lambda: rt.backward(rt.geo.widen_grad(dpred))))      # the engine reads the padded width
 
 
 class MAEViT(nn.Module):

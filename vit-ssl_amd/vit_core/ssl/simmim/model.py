@@ -44,14 +44,10 @@ class _SimMIMRuntime:
         self.stack = R.EncoderStack(st, prefixes, self.D, model.num_heads, model.mlp_dim, model.dropout_p,
                                     drop_path=R.drop_path_rates(model.drop_path_rate, len(prefixes)),
                                     layer_scale=model.layer_scale_init is not None)
-        if self.geo.native:
-            st.register_weight("proj", lambda: st.view("projection.weight", (self.D, self.Pd)), transposed_too=False)
-            st.register_weight("head", lambda: st.view("simmim_head.weight", (self.Pd, self.D)))
-        else:     # zero pad columns in the projection image, zero pad rows / columns in the head image and its transpose
-            st.register_padded_weight("proj", lambda: st.view("projection.weight", (self.D, self.Pd)), self.D, self.Pdp,
-                                      transposed_too=False)
-            st.register_padded_weight("head", lambda: st.view("simmim_head.weight", (self.Pd, self.D)), self.Pdp, self.D)
         self.ws = R.Workspace()
+        self.geo.register_proj(st, "proj", lambda: st.view("projection.weight", (self.D, self.Pd)), self.D)
+        self.head = R.PatchHead(st, self.geo, "head", "simmim_head.weight", "simmim_head.bias", self.D, self.ws)
+        self.stage = R.HostStage()
         self.rec = None
         self.save_gen = 0      # id of the forward whose activations `rec` / the stack hold
 
@@ -75,39 +71,9 @@ class _SimMIMRuntime:
         return x0, patches
 
     def prepare_mask(self, mask_cpu, dev):
-        """Host mask -> (idx, inv, mask_u8) device tensors.
-
-        Staging goes through a small RING of persistent pinned host buffers (one
-        hipHostMalloc per shape, ever): pinning fresh pages every step (`.pin_memory()`)
-        costs milliseconds and serialises with the launch queue on ROCm -- measured 15 ms
-        of GPU idle per step.  A slot is reused only after the event recorded behind its
-        last host-to-device copies has completed."""
-        idx, inv, mflat = mask_indices_np(mask_cpu.contiguous())
-        M, Mm = inv.size, idx.size
-        key = (M, Mm, str(dev))
-        if getattr(self, "_stage_key", None) != key:
-            nslots = 4
-            self._stage = [dict(idx=torch.empty(Mm, dtype=torch.int32).pin_memory(),
-                                inv=torch.empty(M, dtype=torch.int32).pin_memory(),
-                                mask=torch.empty(M, dtype=torch.uint8).pin_memory(), ev=None) for _ in range(nslots)]
-            self._stage_dev = [dict(idx=torch.empty(Mm, dtype=torch.int32, device=dev),
-                                    inv=torch.empty(M, dtype=torch.int32, device=dev),
-                                    mask=torch.empty(M, dtype=torch.uint8, device=dev)) for _ in range(nslots)]
-            self._stage_pos = 0
-            self._stage_key = key
-        k = self._stage_pos % len(self._stage)
-        self._stage_pos += 1
-        slot, d = self._stage[k], self._stage_dev[k]
-        if slot["ev"] is not None:
-            slot["ev"].synchronize()
-        slot["idx"].numpy()[:] = idx          # plain memcpy into the pinned pages (no torch CPU op)
-        slot["inv"].numpy()[:] = inv
-        slot["mask"].numpy()[:] = mflat
-        for name in ("idx", "inv", "mask"):
-            d[name].copy_(slot[name], non_blocking=True)
-        slot["ev"] = torch.cuda.Event()
-        slot["ev"].record(torch.cuda.current_stream())
-        return d["idx"], d["inv"], d["mask"]
+        """Host mask -> (idx, inv, mask_u8) device tensors, staged as one copy through the runtime's ring of pinned buffers
+        (engine.HostStage: they stay valid until the fourth later call)."""
+        return tuple(self.stage.upload(mask_indices_np(mask_cpu.contiguous()), dev))
 
     def forward(self, x, training: bool, save: bool, mask_cpu=None, prepared=None):
         st, ws = self.store, self.ws
@@ -135,27 +101,13 @@ class _SimMIMRuntime:
                 self.save_gen += 1
                 self.rec = dict(B=B, M=M, Mm=0)
             return torch.empty(0, self.Pd, dtype=F32, device=dev), targets, mask_d.view(B, self.N, 1).bool()
-        if self.geo.native:
-            ops.gather_patches_f32(x, idx_d, targets, self.P)
-        else:
-            ops.gather_patches_any_f32(x, idx_d, targets, self.P)
+        self.geo.gather_targets(x, idx_d, targets)
         tag = "" if save else "tmp."
         x0, patches = self.embed(x, mask_d, tag)
         xL, _ = self.stack.forward(x0, B, self.N, training, seed, save=save, slot="a")
         sel = ws.get(tag + "sel", (Mm, self.D), BF16, dev)
         ops.gather_rows_bf16(xL, idx_d, sel)
-        if self.Np == self.Pd:
-            pred = torch.empty(Mm, self.Pd, dtype=F32, device=dev)
-            ops.gemm_nt(sel, st.w("head")[:self.Pd], pred, L.EPI_F32, bias=st.view("simmim_head.bias"))
-        else:
-            # Pd % 4 != 0: the head GEMM writes the padded width (zero weight rows and zero bias give zero pad columns);
-            # the public prediction is the column prefix of that buffer
-            bias = ws.get("pad.head_bias", (self.Np,), F32, dev)
-            bias.zero_()
-            bias[:self.Pd].copy_(st.view("simmim_head.bias"))
-            wide = torch.empty(Mm, self.Np, dtype=F32, device=dev)
-            ops.gemm_nt(sel, st.w("head"), wide, L.EPI_F32, bias=bias)
-            pred = wide[:, :self.Pd]
+        pred = self.head.forward(sel)
         if save:
             self.save_gen += 1
             self.rec = dict(B=B, M=M, Mm=Mm, idx=idx_d, inv=inv_d, mask=mask_d, patches=patches, sel=sel)
@@ -173,21 +125,9 @@ class _SimMIMRuntime:
             return
         dev = dpred_bf16.device
         gv = st.gview
-        if self.geo.native:
-            ops.colsum_bf16(dpred_bf16, gv("simmim_head.bias"))
-            ops.gemm_tn(dpred_bf16, rec["sel"], gv("simmim_head.weight", (self.Pd, self.D)))
-        else:
-            # bias and weight gradients at the padded width, then their first Pd entries / rows into the flat buffer
-            hb = ws.get("pad.head_bgrad", (1, self.Pdp), F32, dev)
-            hw = ws.get("pad.head_wgrad", (self.Pdp, self.D), F32, dev)
-            hb.zero_()
-            hw.zero_()
-            ops.colsum_bf16(dpred_bf16, hb.view(self.Pdp))
-            ops.gemm_tn(dpred_bf16, rec["sel"], hw)
-            ops.accumulate_ld_f32(gv("simmim_head.bias", (1, self.Pd)), hb)
-            ops.accumulate_ld_f32(gv("simmim_head.weight", (self.Pd, self.D)), hw[:self.Pd])
+        self.head.wgrad(dpred_bf16, rec["sel"])
         dsel = ws.get("dsel", (Mm, self.D), BF16, dev)
-        ops.gemm_nt(dpred_bf16, st.w("head.T"), dsel, L.EPI_BF16)
+        self.head.dgrad(dpred_bf16, dsel)
         g = ws.get("g", (M, self.D), F32, dev)
         ops.scatter_rows_f32(dsel, rec["inv"], g)
         if reducer is not None:
@@ -213,19 +153,8 @@ class _SimMIMFn(Function):
     @staticmethod
     def backward(ctx, dpred, _dt, _dm):
         rt = ctx.rt
-
-        def run():
-            dp = R.as_f32(dpred)
-            dpb = torch.empty(dp.shape, dtype=BF16, device=dp.device)
-            if dp.numel() > 0:
-                ops.cast_bf16(dp, dpb)
-            if rt.Pdp != rt.Pd and dp.numel() > 0:      # the engine's backward reads the padded width
-                wide = torch.zeros(dp.shape[0], rt.Pdp, dtype=BF16, device=dp.device)
-                wide[:, :rt.Pd] = dpb
-                dpb = wide
-            rt.backward(dpb)
-
-        return (None, None, None, None, *R.backward_grads("SimMIMViT", ctx.gen, rt.save_gen, rt.store, run))
+        return (None, None, None, None, *R.backward_grads("SimMIMViT", ctx.gen, rt.save_gen, rt.store,
+                                                          lambda: rt.backward(rt.geo.widen_grad(dpred))))      # the engine reads the padded width
 
 
 class SimMIMViT(nn.Module):
@@ -319,10 +248,7 @@ class SimMIMViT(nn.Module):
                 rt.backward(pred, reducer)
             else:
                 dpb = rt.ws.get("dpred", (pred.shape[0], rt.Pdp), BF16, x.device)
-                if rt.geo.native:
-                    ops.l1_loss(pred, targets, loss_sum, dpb, gscale=1.0 / n)
-                else:
-                    ops.l1_loss_ld(pred, targets, loss_sum, dpb, gscale=1.0 / n)
+                rt.geo.l1_loss(pred, targets, loss_sum, dpb, gscale=1.0 / n)
                 rt.backward(dpb, reducer)
             apply()
             self.last_pred, self.last_targets = pred, targets

@@ -18,6 +18,7 @@ from __future__ import annotations
 import re
 from typing import Callable, Dict, List, NamedTuple, Optional, Tuple
 
+import numpy as np
 import torch
 from torch import nn
 
@@ -57,6 +58,12 @@ def _round_up(n: int, a: int) -> int:
     return (n + a - 1) // a * a
 
 
+def as_f32(x: torch.Tensor) -> torch.Tensor:
+    if x.dtype != F32:
+        x = x.float()
+    return x.contiguous()
+
+
 class PatchGeometry:
     """Widths of the patch path of one model.  Pd = C * P * P is the contraction length of the patch projection and of the SimMIM
     head's input-gradient GEMM, and the output width of the head.  A geometry the kernels of vitssl_hip.h take as it is
@@ -78,11 +85,27 @@ class PatchGeometry:
         # output width of the head GEMM (N % 4 == 0): Pd itself where it qualifies, else the padded width
         self.Np = self.Pd if self.Pd % 4 == 0 else self.Pdp
 
+    # Every choice between the entry points of vitssl_hip.h and those of vitssl_patch.h is made below: callers never ask which.
     def patchify(self, x, patches):
+        (ops.patchify_bf16 if self.native else ops.patchify_ld_bf16)(x, patches, self.P)
+
+    def register_proj(self, store: "FlatStore", key: str, src: Callable[[], torch.Tensor], D: int):
+        """The bf16 image [D, Pdp] of the patch projection weight src() [D, Pd] (zero pad columns); no transpose: nothing takes
+        the projection's input gradient."""
         if self.native:
-            ops.patchify_bf16(x, patches, self.P)
+            store.register_weight(key, src, transposed_too=False)
         else:
-            ops.patchify_ld_bf16(x, patches, self.P)
+            store.register_padded_weight(key, src, D, self.Pdp, transposed_too=False)
+
+    def proj_image(self, w):
+        """register_proj without a store: a fresh bf16 [D, Pdp] image of the f32 weight w [D, Pd] (D % 8 == 0)."""
+        if self.native:
+            wb = torch.empty(w.shape, dtype=BF16, device=w.device)
+            ops.cast_transpose_bf16(w, wb, None)
+        else:
+            wb = torch.zeros(w.shape[0], self.Pdp, dtype=BF16, device=w.device)
+            ops.CastPlanLd().run([(w, wb, None)])
+        return wb
 
     def proj_wgrad(self, dproj, patches, gw, ws: "Workspace"):
         """gw f32 [D, Pd] += dproj^T @ patches[:, :Pd]"""
@@ -93,6 +116,28 @@ class PatchGeometry:
         tmp.zero_()
         ops.gemm_tn(dproj, patches, tmp)
         ops.accumulate_ld_f32(gw, tmp)      # the column prefix of the padded result
+
+    def gather_targets(self, x, idx, out):
+        """out f32 [len(idx), Pd] = the patches idx (rows b * N + n) of the image x, bit for bit"""
+        (ops.gather_patches_f32 if self.native else ops.gather_patches_any_f32)(x, idx, out, self.P)
+
+    def l1_loss(self, pred, targets, loss_sum, dpred, gscale):
+        """loss_sum += sum |pred - targets|; dpred bf16 [Mm, Pdp] = gscale * sign(pred - targets), pad columns zero"""
+        (ops.l1_loss if self.native else ops.l1_loss_ld)(pred, targets, loss_sum, dpred, gscale=gscale)
+
+    def widen_grad(self, dpred):
+        """A gradient [Mm, Pd] handed in by autograd -> the bf16 [Mm, Pdp] the engine's backward reads (pad columns zero); an
+        empty one (SimMIM without a masked token) launches nothing."""
+        dp = as_f32(dpred)
+        if dp.numel() == 0:
+            return torch.empty(0, self.Pdp, dtype=BF16, device=dp.device)
+        dpb = torch.empty(dp.shape, dtype=BF16, device=dp.device)
+        ops.cast_bf16(dp, dpb)
+        if self.Pdp != self.Pd:
+            wide = torch.zeros(dp.shape[0], self.Pdp, dtype=BF16, device=dp.device)
+            wide[:, :self.Pd] = dpb
+            dpb = wide
+        return dpb
 
 
 class Workspace:
@@ -111,6 +156,93 @@ class Workspace:
 
     def clear(self):
         self._bufs.clear()
+
+
+class PatchHead:
+    """The Linear D -> Pd that predicts patch pixels (SimMIM's head, MAE's decoder_pred) on a flat store.  A native geometry runs
+    it as it is.  Any other keeps the weight images at [Pdp, D] / [D, Pdp] with zero pad (`key`, `key + '.T'`), takes the
+    gradient of the prediction at the width Pdp and forms the weight and bias gradients at that width in the workspaces
+    `pad.<key>_*` of `ws`; parameters, gradients and the prediction keep the reference's shapes."""
+
+    def __init__(self, store: "FlatStore", geo: PatchGeometry, key: str, weight_name: str, bias_name: str, D: int, ws: Workspace):
+        self.store, self.geo, self.key, self.wname, self.bname, self.D, self.ws = store, geo, key, weight_name, bias_name, int(D), ws
+        src = lambda: store.view(weight_name, (geo.Pd, self.D))      # noqa: E731
+        if geo.native:
+            store.register_weight(key, src)
+        else:
+            store.register_padded_weight(key, src, geo.Pdp, self.D)
+
+    def forward(self, h):
+        """h bf16 [Mm, D] -> pred f32 [Mm, Pd], a fresh tensor"""
+        st, Pd, Np = self.store, self.geo.Pd, self.geo.Np
+        if Np == Pd:
+            pred = torch.empty(h.shape[0], Pd, dtype=F32, device=h.device)
+            ops.gemm_nt(h, st.w(self.key)[:Pd], pred, L.EPI_F32, bias=st.view(self.bname))
+            return pred
+        # Pd % 4 != 0: the GEMM writes the padded width (zero weight rows and zero bias give zero pad columns); the prediction
+        # is the column prefix of that buffer
+        bias = self.ws.get(f"pad.{self.key}_bias", (Np,), F32, h.device)
+        bias.zero_()
+        bias[:Pd].copy_(st.view(self.bname))
+        wide = torch.empty(h.shape[0], Np, dtype=F32, device=h.device)
+        ops.gemm_nt(h, st.w(self.key), wide, L.EPI_F32, bias=bias)
+        return wide[:, :Pd]
+
+    def wgrad(self, dpred, h):
+        """the flat gradients of bias and weight += column sums of dpred bf16 [Mm, Pdp] (pad columns zero), dpred^T @ h"""
+        Pd, Pdp = self.geo.Pd, self.geo.Pdp
+        gb, gw = self.store.gview(self.bname, (1, Pd)), self.store.gview(self.wname, (Pd, self.D))
+        if self.geo.native:
+            ops.colsum_bf16(dpred, gb.view(Pd))
+            ops.gemm_tn(dpred, h, gw)
+            return
+        # at the padded width, then the first Pd entries / rows into the flat buffer
+        hb = self.ws.get(f"pad.{self.key}_bgrad", (1, Pdp), F32, h.device)
+        hw = self.ws.get(f"pad.{self.key}_wgrad", (Pdp, self.D), F32, h.device)
+        hb.zero_()
+        hw.zero_()
+        ops.colsum_bf16(dpred, hb.view(Pdp))
+        ops.gemm_tn(dpred, h, hw)
+        ops.accumulate_ld_f32(gb, hb)
+        ops.accumulate_ld_f32(gw, hw[:Pd])
+
+    def dgrad(self, dpred, out):
+        """out bf16 [Mm, D] = dpred @ W"""
+        ops.gemm_nt(dpred, self.store.w(self.key + ".T"), out, L.EPI_BF16)
+
+
+class HostStage:
+    """Host index tables -> device, through a ring of `slots` persistent pinned buffers: one hipHostMalloc per slot and size,
+    ever (pinning fresh pages every step costs milliseconds and serialises with the launch queue on ROCm: measured 15 ms of GPU
+    idle per step), and one copy per upload.  The views an upload returns are overwritten by the `slots`-th later upload."""
+
+    def __init__(self, slots: int = 4):
+        self.slots, self._ring, self._key, self._pos = int(slots), [], None, 0
+
+    def upload(self, arrays, dev) -> List[torch.Tensor]:
+        """NumPy arrays (1-D, contiguous, any dtypes) -> device views of the same dtypes and lengths: packed at 256-byte
+        aligned offsets into the next slot's pinned bytes and copied to the slot's device buffer on the current stream.  A slot
+        is reused only after the event recorded behind its last copy has completed."""
+        offs, total = [], 0
+        for a in arrays:
+            offs.append(total)
+            total = _round_up(total + a.nbytes, 256)
+        if self._key != (total, str(dev)):
+            self._ring = [[torch.empty(total, dtype=torch.uint8).pin_memory(), torch.empty(total, dtype=torch.uint8, device=dev), None]
+                          for _ in range(self.slots)]
+            self._key, self._pos = (total, str(dev)), 0
+        slot = self._ring[self._pos % self.slots]
+        self._pos += 1
+        host, d, ev = slot
+        if ev is not None:
+            ev.synchronize()
+        staged = host.numpy()
+        for o, a in zip(offs, arrays):
+            staged[o:o + a.nbytes] = a.view(np.uint8)          # plain memcpy into the pinned pages (no torch CPU op)
+        d.copy_(host, non_blocking=True)
+        slot[2] = torch.cuda.Event()
+        slot[2].record(torch.cuda.current_stream())
+        return [d[o:o + a.nbytes].view(torch.from_numpy(a[:0]).dtype) for o, a in zip(offs, arrays)]
 
 
 # ---- parameter names of the stores: what the optimizer's per-parameter settings are keyed by -------------------------------------
