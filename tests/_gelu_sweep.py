@@ -1,6 +1,6 @@
 """All 65536 bf16 inputs of the GELU epilogue: pattern sets, planted operands, a float64 reference and checkers (no GPU code).
 
-EPI_GELU (csrc/gemm_nt.hip, nt_epilogue) rounds u = acc + bias to bf16 and writes out1 = s gelu(u), out0 = s gelu'(u) as bf16 (s = the
+EPI_GELU (csrc/nt_epilogue.h, nt_epilogue) rounds u = acc + bias to bf16 and writes out1 = s gelu(u), out0 = s gelu'(u) as bf16 (s = the
 dropout scale), with fp8 operands also e4m3(s gelu(u) out_scale).  The ping-pong kernel reads the results from a table in LDS where
 its comment says it does,
 

@@ -16,6 +16,8 @@ is two seeds, one of each kind.
 WIDTHS: the two backward bodies once more at every edge of the launch's column-count ladder (256 / 260, 512 / 516, 1024 / 1028 and
 2048: V = 1, 2, 2, 3, 4, 8, 8) with (B, T) = (3, 5): M = 15, odd, four workgroups of which the last has three live waves; and
 384 columns with M = 10 (five row pairs) and M = 15 (no pairs)."""
+import itertools
+
 import numpy as np
 import pytest
 import torch
@@ -93,10 +95,19 @@ def test_table_keeps_the_expected_share(ops, rate):
 
 
 # ------------------------------------------------------------------------------------------------ the residual GEMM
-@pytest.mark.parametrize("p", [0.0, 0.5], ids=["nodrop", "drop0.5"])
-@pytest.mark.parametrize("K", [64, 192])
-@pytest.mark.parametrize("N", [64, 192, 384])
-@pytest.mark.parametrize("B,T", SHAPES, ids=str)
+def exact_cases(axes, extra):
+    """SHAPES x N x K x the named axes (value, id) as one list of cases, then `extra`.  The last case of each exact test is
+    N % 8 == 4 on the 8-wave tiles (16 x 5 = 80 tiles of 256 x 256): the accumulator-layout stores of the first main loop under
+    the row-scale forms of the residual epilogue, which the smaller cases do not reach."""
+    cases = [(B, T, N, K) + tuple(v for v, _ in combo) + ("-".join(str(x) for x in (B, T, N, K) + tuple(i for _, i in combo)),)
+             for B, T in SHAPES for N in (64, 192, 384) for K in (64, 192) for combo in itertools.product(*axes)]
+    return [pytest.param(*c[:-1], id=c[-1]) for c in cases + [extra]]
+
+
+DROPS = [(0.0, "nodrop"), (0.5, "drop0.5")]
+
+
+@pytest.mark.parametrize("B,T,N,K,p", exact_cases([DROPS], (20, 195, 1028, 64, 0.5, "20-195-1028-64-drop0.5")))
 def test_gemm_rows_exact(ops, L, B, T, N, K, p):
     """path rate 0.5 (scale exactly 2), element dropout off and at 0.5 (scale exactly 2): every value is an integer below 2^24"""
     M = B * T

@@ -21,7 +21,7 @@ import torch
 
 import _gemm_exact as X
 from _util import rel_l2
-from test_gpu_droppath import SHAPES, WIDTHS, bits, scales_for
+from test_gpu_droppath import DROPS, SHAPES, WIDTHS, bits, exact_cases, scales_for
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -51,11 +51,8 @@ def row_tables(B, rate, start, with_rows):
 
 
 # ------------------------------------------------------------------------------------------------ the residual GEMM
-@pytest.mark.parametrize("with_rows", [False, True], ids=["norows", "rows0.5"])
-@pytest.mark.parametrize("p", [0.0, 0.5], ids=["nodrop", "drop0.5"])
-@pytest.mark.parametrize("K", [64, 192])
-@pytest.mark.parametrize("N", [64, 192, 384])
-@pytest.mark.parametrize("B,T", SHAPES, ids=str)
+@pytest.mark.parametrize("B,T,N,K,p,with_rows", exact_cases([DROPS, [(False, "norows"), (True, "rows0.5")]],
+                                                            (20, 195, 1028, 64, 0.5, True, "20-195-1028-64-drop0.5-rows0.5")))
 def test_gemm_ls_exact(ops, L, B, T, N, K, p, with_rows):
     """row scale in {0, 2}, dropout scale 2, gamma a multiple of 1/4 up to 3: every value is a multiple of 1/4 below 2^24 / 4"""
     M = B * T

@@ -20,7 +20,7 @@ def build():
     os.makedirs(OUT, exist_ok=True)
     hipcc, flags = "/opt/rocm/bin/hipcc", ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17"]
     objs = []
-    for src, extra in (("gemm_nt.hip", ["-DVITSSL_NT_STAMPS"]), ("error.cpp", [])):
+    for src, extra in (("gemm_nt.hip", ["-DVITSSL_NT_STAMPS"]), ("device_state.hip", []), ("error.cpp", [])):
         obj = os.path.join(OUT, src + ".stamps.o")
         subprocess.run([hipcc] + flags + extra + ["-x", "hip", "-c", os.path.join(CSRC, src), "-o", obj], check=True)
         objs.append(obj)

@@ -18,7 +18,7 @@ def build():
     os.makedirs(OUT, exist_ok=True)
     hipcc, flags = "/opt/rocm/bin/hipcc", ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17"]
     objs = []
-    for src, extra in (("gemm_tn.hip", ["-DVITSSL_TN_STAMPS"] + sys.argv[2:]), ("gemm_nt.hip", []), ("error.cpp", [])):   # (gemm_nt.hip: the CU-count helpers)
+    for src, extra in (("gemm_tn.hip", ["-DVITSSL_TN_STAMPS"] + sys.argv[2:]), ("device_state.hip", []), ("error.cpp", [])):   # (device_state.hip: the CU-count helpers)
         obj = os.path.join(OUT, src + ".tstamps.o")
         subprocess.run([hipcc] + flags + extra + ["-x", "hip", "-c", os.path.join(CSRC, src), "-o", obj], check=True)
         objs.append(obj)

@@ -16,6 +16,8 @@ void vitssl_set_error(const char* fmt, ...);
 // (default 0).  A collective library's kernels cannot co-reside with those workgroups (they take the whole register
 // file and 129 KiB of LDS of their CU), so under data parallelism a few CUs can be left to the all-reduce.
 int vitssl_persistent_cus(void);
+// remembers the workgroup count of the last ping-pong NT GEMM launch for vitssl_debug_last_nt_grid (csrc/device_state.hip, like the above)
+void vitssl_note_nt_grid(int grid);
 
 // ---------------------------------------------------------------- host-side knob caches
 // Entry points run on the Python main thread AND on autograd's backward thread (include/vitssl_hip.h promises re-entrancy): the

@@ -1,5 +1,5 @@
 // LayerScale (include/vitssl_layerscale.h): the kernels live where the residual adds and their backward live -- the EPI_RESID_LS
-// epilogue of csrc/gemm_nt.hip and the LS instantiations of ln_bwd_kernel in csrc/layernorm.hip.  What stands alone is the sizing
+// epilogue of csrc/nt_epilogue.h and the LS instantiations of ln_bwd_kernel in csrc/layernorm.hip.  What stands alone is the sizing
 // of the workspace of the two backward entry points, which keep four column sums where vitssl_layernorm_bwd keeps three.
 #include "../../include/vitssl_layerscale.h"
 #include "common.h"
