@@ -75,6 +75,7 @@ def test_layernorm_row_pairs(ops, rows):
 
 
 def _layernorm_case(ops, rows, cols):
+    # (aggregate bars on similar rows; per row, per column sum and bit for bit: tests/test_gpu_layernorm_rows.py)
     torch.manual_seed(cols + rows)
     x = torch.randn(rows, cols) * 2 + 0.5
     gamma = torch.rand(cols) + 0.5
