@@ -178,20 +178,22 @@ def simmim_fp8_case(_ops, B, img, patch, D, H, F):
         engine.set_linear_operands("bf16")
 
 
-def vit_case(_ops, B, img, patch, D, H, F, classes):
-    """Supervised ViT (conv patch embedding + CLS token, MLP head): logits, attention maps, the cross-entropy value, and every
-    gradient of a LINEAR functional sum(logits * R) against the oracle.  The linear functional hands both sides the same
+def vit_case(_ops, B, img, patch, D, H, F, classes, global_pool="cls"):
+    """Supervised ViT (conv patch embedding + CLS token, MLP head reading the CLS token or, global_pool="avg", the mean of the
+    patch tokens: tests/_pool_ref.py restates the oracle's forward with that choice, bit for bit its own for "cls"): logits,
+    attention maps, the cross-entropy value, and every gradient of a LINEAR functional sum(logits * R) against the oracle.  The linear functional hands both sides the same
     d(logits): with cross entropy on a few samples and classes, sum_b (softmax - onehot) cancels and a 0.15 % difference of the
     logits becomes 5-14 % on every bias-type gradient (triaged in round 4 on B = 5, 2 classes: tools/probes/triage_vit_case.py;
     the head bias gradient there is an exact fp32 column sum of autograd's own d(logits) and still sits 7 % from the oracle's)."""
     import torch
     from _util import rel_l2
+    import _pool_ref
     from oracle import vit_oracle as O
     from vit_core import ViT
     dev = torch.device("cuda:0")
     torch.manual_seed(B * 1000 + img + classes)
     model = ViT(num_classes=classes, num_blocks=2, input_shape=(3, img, img), embed_dim=D, patch_size=patch, num_heads=H,
-                mlp_dim=F, dropout=0.0)
+                mlp_dim=F, dropout=0.0, global_pool=global_pool)
     sd = {k: v.detach().clone() for k, v in model.state_dict().items()}
     model = model.to(dev).train()
     x = torch.rand(B, 3, img, img)
@@ -203,7 +205,7 @@ def vit_case(_ops, B, img, patch, D, H, F, classes):
     worst = {}
     for emu in ("bf16", None):
         leaves = {k: v.clone().requires_grad_(True) for k, v in sd.items()}
-        lo, pr = O.vit_forward(leaves, x, patch, H, emu=emu, return_attn=True)
+        lo, pr = _pool_ref.vit_forward(leaves, x, patch, H, global_pool, emu, return_attn=True)
         # (a handful of logits near zero: 2e-2 against the bf16-emulating mode, 4e-2 against fp32)
         assert rel_l2(logits, lo) < (2e-2 if emu else 4e-2) and rel_l2(attn, pr) < 2e-2, (emu, rel_l2(logits, lo), rel_l2(attn, pr))
         assert abs(float(ce) - float(O.cross_entropy_mean(lo, labels))) < 1e-2 * abs(float(ce)) + 1e-3
@@ -297,6 +299,8 @@ def run(seed=0, kinds="nt,nt,tn,attn,ln,nt8,tn8,tnb", budget_s=120.0, max_cases=
             patch = rng.choice([8, 16])
             H = rng.randint(1, 3)
             args = (rng.randint(1, 6), patch * rng.randint(2, 15 if patch == 8 else 8), patch, 64 * H, H, 64 * rng.randint(1, 6), rng.randint(2, 40))
+            # what the head reads, from a generator of the case's own: the sweep's stream, and so every later case, stays what it was
+            args += (random.Random(repr(args)).choice(["cls", "avg"]),)
             fn = vit_case
         elif kind == "dino":
             patch = rng.choice([8, 16])

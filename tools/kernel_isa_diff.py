@@ -4,7 +4,7 @@ no GPU is opened).
 
     python tools/kernel_isa_diff.py REV FILE [--show N] [--define NAME[=VALUE] ...]
 
-REV's vit-ssl_amd/csrc, include and include_ext are materialised in a temporary directory; both sides of FILE (a name under
+REV's vit-ssl_amd/csrc, include, include_ext and include_addons are materialised in a temporary directory; both sides of FILE (a name under
 csrc/) are compiled with __graft_entry__.FLAGS plus the file's PER_FILE_FLAGS and `--cuda-device-only -S`; the assembly is
 split per kernel symbol; comments, .loc / .file / .cfi / .p2align lines and the function ordinal of .LBB labels are dropped.
 Per kernel: `same` (identical line for line) or the number of differing lines, `sorted` (the sorted instruction lists are
@@ -23,7 +23,7 @@ import tempfile
 from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TREES = ("vit-ssl_amd/csrc", "include", "include_ext")
+TREES = ("vit-ssl_amd/csrc", "include", "include_ext", "include_addons")
 META_KEYS = (("VGPR", "vgpr_count"), ("AGPR", "agpr_count"), ("SGPR", "sgpr_count"), ("scratch", "private_segment_fixed_size"),
              ("vspill", "vgpr_spill_count"), ("sspill", "sgpr_spill_count"), ("LDS", "group_segment_fixed_size"),
              ("kernarg", "kernarg_segment_size"))

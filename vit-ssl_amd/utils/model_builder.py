@@ -144,8 +144,12 @@ def build_model(config):
     init = cfg_get(config, "model", "layer_scale_init")    # optional: LayerScale (absent or null: no new parameter, key or launch)
     if init is not None:
         backbone["layer_scale_init"] = init                # (checked by the models: a finite float > 0, else ValueError)
+    pool = cfg_get(config, "model", "global_pool")         # optional: cls | avg, what the ViT's head reads (absent: cls)
+    if pool is not None and mode not in ("supervised", "finetune"):
+        raise ValueError(f"mode '{mode}': model.global_pool belongs to the supervised / finetune ViT; remove the key")
+    head = {} if pool is None else {"global_pool": pool}   # (checked by ViT: anything but cls / avg is a ValueError)
     makers = {
-        "supervised": lambda: ViT(num_classes=m("num_classes"), **backbone),
+        "supervised": lambda: ViT(num_classes=m("num_classes"), **backbone, **head),
         "simmim": lambda: SimMIMViT(mask_ratio=m("mask_ratio"), **backbone),
         "dino": lambda: DINOViT(output_dim=m("output_dim"), center_momentum=m("center_momentum"), **backbone),
         "mae": lambda: _make_mae(m, backbone),

@@ -1,10 +1,13 @@
-"""Patch-embed (+CLS, +pos) -> encoder stack -> CLS feature, on a flat store.
+"""Patch-embed (+CLS, +pos) -> encoder stack -> CLS feature (or the mean of the patch tokens), on a flat store.
 Shared by ViT (vit_core/vit.py:33-45) and the DINO backbones
 (vit_core/ssl/dino/model.py:34-45)."""
 import torch
 
 from . import _runtime as R
 from ._runtime import BF16, F32, L, ops
+
+
+POOLS = ("cls", "avg")
 
 
 class BackboneRuntime:
@@ -38,8 +41,11 @@ class BackboneRuntime:
         ops.bicubic_resize_fwd(pos[0, 1:], full[1:], self.grid[0], self.grid[1], gh, gw)
         return full, (gh, gw)
 
-    def forward(self, x, training: bool, seed: int, save: bool, slot: str, return_attn=False, dynamic=False):
-        """x: fp32 [B, C, Himg, Wimg] -> (cls features fp32 [B, D], attn probs or None)."""
+    def forward(self, x, training: bool, seed: int, save: bool, slot: str, return_attn=False, dynamic=False, pool: str = "cls"):
+        """x: fp32 [B, C, Himg, Wimg] -> (features fp32 [B, D], attn probs or None).  `pool`: "cls" = the CLS row of the last
+        block's output, "avg" = the fp32 mean of its patch rows (csrc/pool.hip); a saving forward records it for `backward`."""
+        if pool not in POOLS:
+            raise ValueError(f"pool = {pool!r} is none of {POOLS}")
         st, ws = self.store, self.ws
         x = R.as_f32(x)
         B, C, Hi, Wi = x.shape
@@ -64,9 +70,9 @@ class BackboneRuntime:
         x0.view(B, T, self.D)[:, 0] = st.view(self.names["cls"]) + pos[0]
         xL, probs = self.stack.forward(x0, B, T, training, seed, save=save, slot=slot, return_attn=return_attn)
         feats = torch.empty(B, self.D, dtype=F32, device=dev)
-        ops.gather_cls_f32(xL, feats, B, T, self.D)
+        (ops.gather_cls_f32 if pool == "cls" else ops.pool_tokens_fwd)(xL, feats, B, T, self.D)
         if save:
-            self.rec[slot] = dict(B=B, T=T, tokens=tokens, patches=patches, pos_graph=pos_graph)
+            self.rec[slot] = dict(B=B, T=T, tokens=tokens, patches=patches, pos_graph=pos_graph, pool=pool)
         return feats, probs
 
     def forget(self, slot: str):
@@ -76,7 +82,8 @@ class BackboneRuntime:
         self.stack._saved.pop(slot, None)
 
     def backward(self, dfeats, slot: str, reducer=None, input_grad_only=False, proj_wgrad=True):
-        """dfeats: fp32 [B, D] gradient wrt the CLS features; accumulates parameter grads.
+        """dfeats: fp32 [B, D] gradient wrt the features (scattered by the pooling mode the forward recorded); accumulates
+        parameter grads.
         `input_grad_only`: the blocks are frozen (EncoderStack.backward); `proj_wgrad=False`: so is the patch projection,
         its weight-gradient GEMM is not launched."""
         st, ws = self.store, self.ws
@@ -85,7 +92,7 @@ class BackboneRuntime:
         dev = dfeats.device
         gv = st.gview
         g = ws.get(f"{slot}.g", (B * T, self.D), F32, dev)
-        ops.scatter_cls_f32(R.as_f32(dfeats), g, B, T, self.D)
+        (ops.scatter_cls_f32 if rec["pool"] == "cls" else ops.pool_tokens_bwd)(R.as_f32(dfeats), g, B, T, self.D)
         g = self.stack.backward(g, slot=slot, reducer=reducer, input_grad_only=input_grad_only)
         dproj = ws.get(f"{slot}.dproj", (B * tokens, self.D), BF16, dev)
         if rec["pos_graph"] is None:

@@ -1,5 +1,6 @@
 """Supervised ViT (reference: vit_core/vit.py:9-45): ConvolutionalPatchEmbedding ->
-encoder blocks -> CLS token -> MLPHead, run as one engine schedule on a flat store.
+encoder blocks -> CLS token (or, with global_pool="avg", the mean of the patch tokens) -> MLPHead, run as one engine schedule
+on a flat store.
 
 Two ways to train, as for SimMIMViT:
   * reference style: ``loss = criterion(model(x), y); loss.backward()`` (one torch.autograd.Function around the engine);
@@ -17,7 +18,7 @@ from torch.autograd import Function
 
 from . import _runtime as R
 from ._runtime import BF16, F32, L, _round_up, ops
-from ._backbone import BackboneRuntime
+from ._backbone import POOLS, BackboneRuntime
 from .encoder_block import EncoderBlock, check_layer_scale_init
 from .mlp_head import MLPHead
 from .patch_embedding import ConvolutionalPatchEmbedding
@@ -105,7 +106,7 @@ class _ViTRuntime:
         st.refresh_weights()
         seed = R.next_seed() if self.bb.stack.needs_seed(training) else 0
         feats, probs = self.bb.forward(x, training, seed, save=save if save_backbone is None else save_backbone, slot="a",
-                                       return_attn=return_attn)
+                                       return_attn=return_attn, pool=self.model.global_pool)
         B, dev = feats.shape[0], feats.device
         h = g(tag + "h", (B, self.D), BF16, dev)
         mean, rstd = g(tag + "mean", (B,), F32, dev), g(tag + "rstd", (B,), F32, dev)
@@ -219,10 +220,16 @@ class ViT(nn.Module):
         mlp_dim: int = 3072,
         dropout: float = 0.1,
         *,
+        global_pool: str = "cls",
         layer_scale_init: Optional[float] = None,
         drop_path_rate: float = 0.0,
     ):
         super().__init__()
+        # what the head reads (timm's global_pool): "cls" = the CLS token, "avg" = the mean of the patch tokens (the MAE
+        # fine-tune recipe; classification_head.norm is then its fc_norm).  Not a parameter, buffer or state_dict key
+        if global_pool not in POOLS:
+            raise ValueError(f'ViT: global_pool = {global_pool!r} is neither "cls" nor "avg"')
+        self.global_pool = global_pool
         # LayerScale (timm's init_values): None = no new parameter, key or launch; else a finite float > 0 (ValueError otherwise)
         self.layer_scale_init = check_layer_scale_init(layer_scale_init)
         self.encoder_blocks = nn.ModuleList(

@@ -16,6 +16,12 @@ HEADERS = {key: os.path.join(_INCLUDE, f"vitssl_{key}.h")
 # twelve-header ABI); EXT_REGISTRY below has one table per key
 _INCLUDE_EXT = os.path.normpath(os.path.join(_HERE, "..", "..", "include_ext"))
 EXT_HEADERS = {"mae": os.path.join(_INCLUDE_EXT, "vitssl_mae.h")}
+# add-on tables: every vitssl_<key>.h under include_addons/, keys from the directory listing in sorted order (the two
+# directories above are pinned by their tests; a new feature adds its header here and its table to _ADDON_ABI below);
+# ADDON_REGISTRY below has one table per key
+_INCLUDE_ADDONS = os.path.normpath(os.path.join(_HERE, "..", "..", "include_addons"))
+ADDON_HEADERS = {m.group(1): os.path.join(_INCLUDE_ADDONS, m.group(0))
+                 for m in (re.fullmatch(r"vitssl_(\w+)\.h", f) for f in sorted(os.listdir(_INCLUDE_ADDONS))) if m}
 
 
 class VitsslError(RuntimeError):
@@ -261,6 +267,16 @@ _EXT_ABI = {
 # extension key -> function name -> (restype, argtypes), the form of REGISTRY
 EXT_REGISTRY = {key: {name: p if isinstance(p, tuple) else (C.c_int, p) for name, p in table.items()} for key, table in _EXT_ABI.items()}
 
+_ADDON_ABI = {
+    # include_addons/vitssl_pool.h: global average pooling of the patch tokens on the fp32 stream, forward and backward
+    "pool": {
+        "vitssl_pool_tokens_fwd": [_vp, _vp, _i, _i, _i, _vp],
+        "vitssl_pool_tokens_bwd": [_vp, _vp, _i, _i, _i, _vp],
+    },
+}
+# add-on key -> function name -> (restype, argtypes), the form of REGISTRY; a header without a table in _ADDON_ABI is a KeyError
+ADDON_REGISTRY = {key: {name: p if isinstance(p, tuple) else (C.c_int, p) for name, p in _ADDON_ABI[key].items()} for key in ADDON_HEADERS}
+
 DROPPATH_SITE_BIT = 0x80000000          # VITSSL_DROPPATH_SITE_BIT
 DROPPATH_MAX_SITES = 128                # VITSSL_DROPPATH_MAX_SITES
 LAMB_ALWAYS_ADAPT, LAMB_TRUST_CLIP = 1, 2          # VITSSL_LAMB_ALWAYS_ADAPT, VITSSL_LAMB_TRUST_CLIP
@@ -269,8 +285,11 @@ _lib = None
 
 
 def header_path(key):
-    """include/vitssl_<key>.h, or include_ext/vitssl_<key>.h for an extension key."""
-    return HEADERS[key] if key in HEADERS else EXT_HEADERS[key]
+    """include/vitssl_<key>.h, include_ext/vitssl_<key>.h for an extension key, include_addons/vitssl_<key>.h for an add-on key."""
+    for table in (HEADERS, EXT_HEADERS):
+        if key in table:
+            return table[key]
+    return ADDON_HEADERS[key]
 
 
 def header_text(key):
@@ -315,7 +334,8 @@ def lib():
     if l.vitssl_version() != ABI_VERSION:        # int vitssl_version(void): ctypes' defaults call it right before anything is bound
         raise VitsslError(f"{LIB_PATH} implements C-ABI version {l.vitssl_version()}, these bindings expect {ABI_VERSION}: "
                           "rebuild it (python __graft_entry__.py)")
-    for table in list(REGISTRY.values()) + list(EXT_REGISTRY.values()):      # the extension tables after the registry
+    # the extension tables after the registry, the add-on tables after those
+    for table in list(REGISTRY.values()) + list(EXT_REGISTRY.values()) + list(ADDON_REGISTRY.values()):
         for name, (restype, argtypes) in table.items():
             fn = getattr(l, name)  # AttributeError if the symbol is missing
             fn.restype, fn.argtypes = restype, argtypes

@@ -512,6 +512,16 @@ def scatter_cls_f32(gcls, g, B, T, D):
     call("vitssl_scatter_cls_f32", _chk(gcls, F32, "gcls", (B, D)), _chk(g, F32, "g", (B * T, D)), B, T, D, _stream())
 
 
+def pool_tokens_fwd(x, out, B, T, D):
+    """out[b] = the fp32 mean of image b's patch rows x[b*T + 1 .. b*T + T-1] (global average pooling; the CLS row is not read)."""
+    call("vitssl_pool_tokens_fwd", _chk(x, F32, "x", (B * T, D)), _chk(out, F32, "out", (B, D)), B, T, D, _stream())
+
+
+def pool_tokens_bwd(dout, g, B, T, D):
+    """g[b*T] = 0 and g[b*T + t] = dout[b] / (T - 1) for t >= 1: every element of g is written."""
+    call("vitssl_pool_tokens_bwd", _chk(dout, F32, "dout", (B, D)), _chk(g, F32, "g", (B * T, D)), B, T, D, _stream())
+
+
 def embed_bwd(dtok, mask, dproj, dpos, dmask_token, dbias, dcls, B, tokens, tok_offset, D):
     T_out = tokens + tok_offset
     wsn = int(L.lib().vitssl_embed_bwd_workspace_floats(B, tokens, tok_offset, D))
