@@ -8,6 +8,7 @@ fp32 oracle at the tolerance e4m3's 3 mantissa bits allow (stated per assert).""
 import pytest
 import torch
 
+from _e4m3 import check_image
 from _util import rel_l2
 
 pytestmark = pytest.mark.gpu
@@ -186,6 +187,7 @@ def test_attention_fwd_fp8_image():
     # only at double-rounding ties)
     same = (out8.cpu().view(torch.uint8) == _q8_torch(out.cpu().float()).view(torch.uint8)).float().mean()
     assert float(same) > 0.95    # expected ~0.97: 1 in 2^5 values sits where the two roundings disagree
+    check_image(out8, out, 1.0, "attn_fwd_fp8")    # and per element: the other 3 % are the neighbouring byte at a rounding boundary
 
 
 # one or two lengths per backward kernel: fused (37: NS = 2, two waves; 128: NS = 4, full last tile), persistent (197),
@@ -212,6 +214,7 @@ def test_attention_bwd_fp8_image(N):
     same = (d8.cpu().view(torch.uint8) == _q8_torch(d1.cpu().float() * 2.0 ** 13).view(torch.uint8)).float().mean()
     assert float(same) > 0.95
     assert rel_l2(_f32(d8) / 2.0 ** 13, d1) < 4e-2
+    check_image(d8, d1, 2.0 ** 13, f"attn_bwd_fp8 N = {N}")
     # without the bf16 image (the engine's calls after its first backward): the same e4m3 image and maximum, bit for bit
     d8n = torch.empty_like(d8)
     amaxn = torch.zeros(1, device=DEV)

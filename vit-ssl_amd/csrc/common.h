@@ -187,16 +187,36 @@ __device__ __forceinline__ unsigned pack_bf2(float lo, float hi) {
 }
 __device__ __forceinline__ float round_bf(float f) { return bf2f(f2bf(f)); }
 
-// four fp32 -> four OCP e4m3fn bytes (round to nearest even, saturating at +-448: the
-// conversion instruction is given clamped inputs), element 0 in the low byte
+// clamp to +-448 with IEEE-754 minimum / maximum (v_maximum3_f32, v_minimum3_f32): a NaN stays a NaN.  v_med3_f32, v_max_f32 and
+// v_min_f32 return the other operand instead, which turned a NaN into -448.
+__device__ __forceinline__ float clamp_e4m3(float x) {
+  return __builtin_elementwise_minimum(__builtin_elementwise_maximum(x, -448.f), 448.f);
+}
+
+// four fp32 -> four OCP e4m3fn bytes (round to nearest even; +-inf and everything beyond +-448 saturate to +-448: the
+// conversion instruction is given clamped inputs; NaN -> a NaN byte), element 0 in the low byte
 __device__ __forceinline__ unsigned pack_fp8x4(float a, float b, float c, float d) {
-  a = __builtin_amdgcn_fmed3f(a, -448.f, 448.f);
-  b = __builtin_amdgcn_fmed3f(b, -448.f, 448.f);
-  c = __builtin_amdgcn_fmed3f(c, -448.f, 448.f);
-  d = __builtin_amdgcn_fmed3f(d, -448.f, 448.f);
-  int w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
-  w = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
+  int w = __builtin_amdgcn_cvt_pk_fp8_f32(clamp_e4m3(a), clamp_e4m3(b), 0, false);
+  w = __builtin_amdgcn_cvt_pk_fp8_f32(clamp_e4m3(c), clamp_e4m3(d), w, true);
   return (unsigned)w;
+}
+
+// The same, and a NaN keeps its sign (0x7F | sign, as torch's conversion): the conversion instruction's NaN byte is 0xFF whatever
+// the sign.  The top byte of an fp32 NaN (sign, seven exponent ones) is the e4m3 NaN of that sign; a wave that holds a NaN (two
+// unordered compares and one scalar branch find out) patches those bytes.  For the stand-alone quantisers (csrc/fp8.hip), which
+// cast given data; the epilogues, whose NaNs are computed, use pack_fp8x4.
+__device__ __forceinline__ unsigned e4m3_nan_byte(unsigned w, float x, int i) {
+  return x != x ? (w & ~(0xffu << (8 * i))) | ((__float_as_uint(x) >> 24) << (8 * i)) : w;
+}
+__device__ __forceinline__ unsigned pack_fp8x4_nan_sign(float a, float b, float c, float d) {
+  unsigned w = pack_fp8x4(a, b, c, d);
+  if (__builtin_amdgcn_ballot_w64(__builtin_isunordered(a, b) | __builtin_isunordered(c, d)) != 0) {
+    w = e4m3_nan_byte(w, a, 0);
+    w = e4m3_nan_byte(w, b, 1);
+    w = e4m3_nan_byte(w, c, 2);
+    w = e4m3_nan_byte(w, d, 3);
+  }
+  return w;
 }
 
 // ---------------------------------------------------------------- wave reductions (64 lanes)

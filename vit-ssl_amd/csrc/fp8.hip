@@ -25,15 +25,15 @@ __global__ __launch_bounds__(Q_THREADS) void quantize_fp8_kernel(const bf16_t* _
       for (int r = 0; r < 8; ++r) m = fmaxf(m, fabsf(f[r]));
     }
     u32x2 o;
-    o[0] = pack_fp8x4(f[0] * qs, f[1] * qs, f[2] * qs, f[3] * qs);
-    o[1] = pack_fp8x4(f[4] * qs, f[5] * qs, f[6] * qs, f[7] * qs);
+    o[0] = pack_fp8x4_nan_sign(f[0] * qs, f[1] * qs, f[2] * qs, f[3] * qs);
+    o[1] = pack_fp8x4_nan_sign(f[4] * qs, f[5] * qs, f[6] * qs, f[7] * qs);
     *(u32x2*)(y + 8 * i) = o;
   }
   if (blockIdx.x == 0 && threadIdx.x < (n & 7)) {
     const long long i = (n8 << 3) + threadIdx.x;
     const float f = bf2f(x[i]);
     m = fmaxf(m, fabsf(f));
-    y[i] = (unsigned char)(pack_fp8x4(f * qs, 0.f, 0.f, 0.f) & 0xffu);
+    y[i] = (unsigned char)(pack_fp8x4_nan_sign(f * qs, 0.f, 0.f, 0.f) & 0xffu);
   }
   if (qamax) {               // kernel-argument uniform
     m = wave_max(m);
@@ -94,7 +94,7 @@ __global__ __launch_bounds__(Q_THREADS) void fp8_weight_amax_kernel(const vitssl
 
 // k = floor(log2(448 / amax)), clamped so that 2^k and 2^-k are normal floats
 __device__ __forceinline__ int fp8_scale_exp(float amax) {
-  if (!(amax > 0.f) || !(amax < 3.0e38f)) return 0;
+  if (!(amax > 0.f) || !(amax <= 3.402823466e38f)) return 0;   // zero, +inf (a NaN never gets here: fmaxf drops it)
   int e;
   const float fr = frexpf(amax, &e);           // amax = fr * 2^e, fr in [0.5, 1)
   // 448 = 0.875 * 2^9: 448 / amax = (0.875 / fr) * 2^(9 - e), and 0.875 / fr is in (0.875, 1.75]
@@ -135,7 +135,7 @@ __global__ __launch_bounds__(Q_THREADS) void fp8_weight_quant_kernel(const vitss
         for (int e = 0; e < 4 && c + e < C; ++e) v[e] = src[e];
       }
     }
-    const unsigned w = pack_fp8x4(v[0] * sc, v[1] * sc, v[2] * sc, v[3] * sc);
+    const unsigned w = pack_fp8x4_nan_sign(v[0] * sc, v[1] * sc, v[2] * sc, v[3] * sc);
     *(unsigned*)&tile[rr + ty][tx] = w;
     if (dst && r < R) {
       if (vec_c && c + 3 < C) *(unsigned*)(dst + (long long)r * C + c) = w;

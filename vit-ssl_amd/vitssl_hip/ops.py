@@ -105,7 +105,8 @@ def _scalar(t, name):
 
 def quantize_fp8(x, y8, scale=None, amax=None):
     """y8 = e4m3(clamp(x * scale, +-448)) of a bf16 tensor; `scale` / `amax` are optional 1-element device tensors
-    (amax receives max(amax, max|x|))."""
+    (amax receives max(amax, max|x|)).  NaN maps to NaN (0x7F | sign, as torch's conversion), +-inf and overflow map to +-448;
+    the recorded maximum ignores NaN (an infinity makes it +inf)."""
     call("vitssl_quantize_fp8_scaled", _chk(x, BF16, "x"), _chk(y8, FP8, "y8", x.shape), x.numel(), _scalar(scale, "scale"),
          _scalar(amax, "amax"), _stream())
 
@@ -405,6 +406,8 @@ def gemm_fp8_tn_batch(jobs):
 
 
 def attn_fwd(qkv, out, lse, B, N, H, dh, probs=None, out_fp8=None):
+    """`out_fp8` (fp8 path): also the e4m3 image of the fp32 values `out` is rounded from, at unit scale.  NaN maps to NaN (a NaN
+    byte; its sign is not kept), +-inf and overflow map to +-448."""
     ev = _prof_begin()
     _attn_fwd(qkv, out, lse, B, N, H, dh, probs, out_fp8)
     _prof_end(ev, f"attn_fwd B{B} N{N} H{H}", 4.0 * B * H * N * N * dh)
@@ -421,7 +424,8 @@ def _attn_fwd(qkv, out, lse, B, N, H, dh, probs=None, out_fp8=None):
 
 
 def attn_bwd(qkv, out, dout, lse, dqkv, delta_ws, B, N, H, dh, dqkv_fp8=None, scale=None, amax=None):
-    """`dqkv_fp8` (fp8 path): also the e4m3 image e4m3(dqkv * scale), with max|dqkv| recorded in `amax`."""
+    """`dqkv_fp8` (fp8 path): also the e4m3 image e4m3(dqkv * scale), with max|dqkv| recorded in `amax`.  NaN maps to NaN (a NaN
+    byte; its sign is not kept), +-inf and overflow map to +-448; the recorded maximum ignores NaN."""
     ev = _prof_begin()
     if dqkv_fp8 is not None:
         call("vitssl_attn_bwd_fp8", _chk(qkv, BF16, "qkv", (B * N, 3 * H * dh)), _chk(out, BF16, "out", (B * N, H * dh)),
